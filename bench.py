@@ -213,6 +213,32 @@ def counter_figures(workload, N, Bg, kernel_ms, build_id):
     return traffic, counters, counters_note, valu_busy, executed
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, out, lo, winner):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<name>.npy in float64 -- the rollout
+    outputs of this rank's candidates (J, mu, Sig, cost_mu, cost_var; first axis = candidate) and the winner (best_J, best_index,
+    best_actions).  candidate_index.npy holds the global index of every stored candidate: all of them while the files fit in
+    DUMP_BYTES, otherwise a sample drawn with a fixed seed, so two builds store the same candidates."""
+    best_J, best_i, best_act = winner
+    host = {"best_J": np.array([best_J], dtype=np.float64), "best_index": np.array([best_i], dtype=np.float64),
+            "best_actions": np.asarray(best_act, dtype=np.float64)}
+    B = out["J"].shape[0]
+    row_bytes = 8 * (1 + sum(v[0].numel() for v in out.values()))          # + the candidate's index
+    budget = DUMP_BYTES - sum(a.nbytes for a in host.values()) - 1024 * (len(out) + len(host) + 1)   # (.npy headers)
+    if B * row_bytes <= budget:
+        idx = np.arange(B)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(B, budget // row_bytes, replace=False))
+    sel = torch.as_tensor(idx, device=out["J"].device)
+    host.update({k: v.index_select(0, sel).cpu().numpy().astype(np.float64) for k, v in out.items()})
+    host["candidate_index"] = (idx + lo).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def refresh_line(path):
     """--refresh-line: the counter-derived fields of a stored bench line recomputed from profiles/pmc_*.json with the functions above
     (the counters of a shape are collected AFTER its line when a launch is long: config 5).  Nothing measured is touched."""
@@ -258,6 +284,9 @@ def main():
                          "multi-GPU line (per_rank block) before the first real N-GPU run; its numbers mean nothing")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="engine option for an A/B run (gpmpc_set_option; recorded in config.engine_options)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (rank 0's rollout outputs, the winner) as DIR/<name>.npy in "
+                         "float64, at most 64 MB in all: see dump_outputs")
     args = ap.parse_args()
     if args.refresh_line:
         refresh_line(args.refresh_line)
@@ -440,23 +469,13 @@ def main():
             el_max = float(tmax.item())
         return el_max, el, last
 
-    # The timed region of the contract is ONE window of --steps steps.  With sub-millisecond steps that window is a few
-    # milliseconds and one slow launch moves the line by several per cent, so short windows are repeated
-    # inside the same run and the line reports the MEDIAN window (`windows` holds every window and their spread); every rank
-    # takes the same decision from the same estimate (rank-0's, broadcast).
-    n_windows = 1
-    est = torch.tensor([est_step_ms], dtype=torch.float64, device=device)
-    if use_dist:
-        dist.broadcast(est, src=0)
-    if float(est.item()) * args.steps < 400.0:
-        n_windows = 5
-    windows = []
-    for _ in range(n_windows):
-        el_max, el_loc, (best_J, best_i, best_act) = timed_window()
-        windows.append((el_max, el_loc))
-    order = sorted(range(n_windows), key=lambda i: windows[i][0])
-    elapsed, elapsed_local = windows[order[n_windows // 2]]
+    # The timed region of the contract is ONE window of exactly --steps steps, and `ms_per_step` is its time per step: callers
+    # size later runs from it.  With sub-millisecond steps, ask for enough steps to fill a few hundred milliseconds.
+    elapsed, elapsed_local, (best_J, best_i, best_act) = timed_window()
     out = bufs["out"]
+    if args.dump_outputs and rank == 0:
+        # before anything below launches again into the same buffers
+        dump_outputs(args.dump_outputs, out, lo, (best_J, best_i, best_act))
 
     # batch independence at THIS batch size (before anything re-prepares the model): the batch launched in REVERSE order must give
     # every candidate the same trajectory bit for bit (same launch configuration, every candidate in another slot, chunk and
@@ -601,11 +620,9 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_first_window": windows[0][0] / args.steps * 1e3,      # BENCH_r01-r04 reported a single window: this is that figure
-            # every timed window of --steps steps of this run (ms per step, max over ranks, in run order); `value` and
-            # `ms_per_step` are the median window
-            "windows": {"n": n_windows, "ms_per_step": [wd[0] / args.steps * 1e3 for wd in windows],
-                        "spread": (max(wd[0] for wd in windows) - min(wd[0] for wd in windows)) / elapsed},
+            # the two fields below keep the layout of earlier lines, which took the median of five windows of short runs
+            "ms_per_step_first_window": elapsed / args.steps * 1e3,
+            "windows": {"n": 1, "ms_per_step": [elapsed / args.steps * 1e3], "spread": 0.0},
             "higher_is_better": True,
             "scaling": scaling,
             "vs_baseline": None,

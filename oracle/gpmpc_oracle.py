@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- fp64 numpy restatement of the reference GP-MPC hot path.
 
-Every function cites the reference lines it follows (paths relative to
-/root/reference/rl_gp_mpc/).  The restatement keeps the reference's *formulation*
+Every function cites the reference lines it follows (paths relative to the
+reference's rl_gp_mpc/ package).  The restatement keeps the reference's *formulation*
 (B / t / R / Q / maha as written there, LU solves and determinants) but
 
 * carries a leading candidate axis ``B`` (the reference evaluates one action

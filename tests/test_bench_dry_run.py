@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,3 +47,36 @@ def test_weak_scaling_line_and_ragged_strong_split_at_world_3():
     d = _run(3, ["--workload", "c4", "--candidates-total", "1000"], 30211 + os.getpid() % 300)
     assert d["scaling"] == "strong" and [r["candidates"] for r in d["per_rank"]] == [334, 333, 333]
     assert abs(d["value"] - 1000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+
+
+def _dumped(path):
+    files = {f[:-4]: np.load(os.path.join(path, f)) for f in os.listdir(path)}
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(os.path.getsize(os.path.join(path, f)) for f in os.listdir(path)) <= 64_000_000
+    return files
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs at config 2: every candidate's rollout outputs and the winner the timed path returned."""
+    from oracle import synth
+    d = _run(1, ["--workload", "c2", "--dump-outputs", str(tmp_path)], 30511 + os.getpid() % 300)
+    f = _dumped(tmp_path)
+    assert set(f) == {"J", "mu", "Sig", "cost_mu", "cost_var", "candidate_index", "best_J", "best_index", "best_actions"}
+    assert f["J"].shape == (256,) and f["mu"].shape == (256, 26, 3) and f["Sig"].shape == (256, 26, 3, 3)
+    assert np.array_equal(f["candidate_index"], np.arange(256))
+    best = int(np.argmin(f["J"]))
+    assert f["best_index"][0] == best == d["best_index"] and f["best_J"][0] == f["J"][best] == d["best_J"]
+    assert np.array_equal(f["best_actions"], synth.named("c2", B=256).actions[best])
+
+
+def test_dump_outputs_of_a_large_batch_are_a_fixed_sample(tmp_path):
+    """Past 64 MB the per-candidate arrays hold a seeded sample of the candidates: two runs store the same files."""
+    runs = []
+    for k in range(2):
+        _run(1, ["--workload", "c5", "--candidates-total", "1024", "--steps", "2", "--dump-outputs", str(tmp_path / str(k))],
+             30811 + os.getpid() % 300)
+        runs.append(_dumped(tmp_path / str(k)))
+    idx = runs[0]["candidate_index"]
+    assert 0 < len(idx) < 1024 and np.all(np.diff(idx) > 0) and idx[-1] < 1024
+    assert runs[0]["Sig"].shape == (len(idx), 51, 16, 16)
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])

@@ -414,7 +414,8 @@ def test_exchange_off_the_compute_stream_costs_the_step_nothing():
     def line(extra):
         best = None
         for _ in range(2):              # best of two: the comparison is between code paths, not between clock states
-            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--steps", "200", "--warmup", "5"] + extra,
+            # (one timed window of 1000 steps: ~0.4 s, long enough that one slow launch does not move the ratio)
+            out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--steps", "1000", "--warmup", "5"] + extra,
                                  capture_output=True, text=True, timeout=600, env=env)
             assert out.returncode == 0, out.stderr[-2000:]
             d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -310,6 +310,15 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                                             trajectories=True, stage_costs=False)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()
 
+    def predict(self, inputs, include_noise=True):
+        """GP posterior at the model inputs (M, E) -> (mean, var), DEVICE tensors (M, D): what the reference's model plot gets
+        from likelihood(model(x)) (static_3d_graph.py:77-80, 116) -- the exact posterior, with each GP's noise added when
+        `include_noise` (without it: the latent function's variance)."""
+        if self.x_mem is None:
+            raise RuntimeError("call prepare_inference(inputs, state_changes) before predict")
+        out = self.engine.predict(inputs, noises=self.noises.detach().cpu().numpy() if include_noise else None)
+        return out["mean"], out["var"]
+
     # -- state / training ------------------------------------------------------------------
     def save_state(self):
         return SavedState(inputs=self.x_mem, states_change=self.y_mem,

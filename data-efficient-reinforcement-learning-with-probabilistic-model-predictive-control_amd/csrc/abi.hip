@@ -81,7 +81,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -113,6 +113,11 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
         const int v = (int)value;
         if (v < 0 || v > 64 || (v & 3)) { h->err = "grad_chunk_rows: 0 (auto) or a multiple of 4 up to 64"; return GPMPC_ERR_ARG; }
         h->opt_grad_chunk = v;
+    }
+    else if (!strcmp(name, "predict_chunk_rows")) {
+        const long long v = value;
+        if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
+        h->opt_predict_chunk = (int)v;
     }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
@@ -187,6 +192,20 @@ int gpmpc_read_factors(gpmpc_t* g, double* iK_dst, double* beta_dst, void* strea
     if (iK_dst) GPMPC_HIP_CHECK(h, hipMemcpyAsync(iK_dst, h->iK.p, DN * h->N * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (beta_dst) GPMPC_HIP_CHECK(h, hipMemcpyAsync(beta_dst, h->beta.p, DN * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return GPMPC_OK;
+}
+
+int gpmpc_predict(gpmpc_t* g, const double* Xq, int M, int D, int E, const double* noises_host, double* mean_out,
+                  double* var_out, void* stream) {
+    Range roctx_range("gpmpc_predict");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "predict before prepare / set_factors / mll");
+    if (D != h->D || E != h->E) return bad(g, "predict: D / E differ from the cached model");
+    if (M < 0) return bad(g, "predict: M < 0");
+    if (M > 0 && !Xq) return bad(g, "null argument");
+    if (M == 0) return GPMPC_OK;
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_predict(h, Xq, M, noises_host, mean_out, var_out, (hipStream_t)stream);
 }
 
 int gpmpc_mll(gpmpc_t* g, const double* X, const double* Y, const double* ls, const double* os, const double* noise,

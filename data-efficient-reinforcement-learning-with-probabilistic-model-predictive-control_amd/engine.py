@@ -166,6 +166,27 @@ class HipEngine:
         self._check(self.lib.gpmpc_read_factors(self._h, iK.data_ptr(), beta.data_ptr(), self._stream()))
         return iK, beta
 
+    def predict(self, Xq, noises=None, mean=True, var=True):
+        """GP posterior at the query inputs Xq (M, E) from the cached model: dict(mean (M, D), var (M, D)) of device tensors
+        (only the requested ones).  `noises` (D,): added to the variance, as likelihood(model(x)) does.  Asynchronous on the
+        current stream."""
+        Xq = self._dev(Xq)
+        if Xq.dim() != 2:
+            raise ValueError(f"expected query inputs of shape (M, E), got {tuple(Xq.shape)}")
+        M, E = Xq.shape
+        D = self.D
+        nz = _host(noises, (D,)) if noises is not None else None
+        out = {}
+        if mean:
+            out["mean"] = torch.empty((M, D), dtype=torch.float64, device=self.device)
+        if var:
+            out["var"] = torch.empty((M, D), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_predict(self._h, Xq.data_ptr(), M, D, E, _hp(nz) if nz is not None else None,
+                                           out["mean"].data_ptr() if mean else None,
+                                           out["var"].data_ptr() if var else None, self._stream()))
+        self._keep_predict = Xq              # alive until the asynchronous call has read it
+        return out
+
     # -- a6 ----------------------------------------------------------------------------
     def set_cost(self, target, W, W_T, kappa, clip_to_zero=False, state_min=None, state_max=None):
         W_T = _host(W_T)

@@ -63,12 +63,29 @@ int gpmpc_get_factors(gpmpc_t* h, const double** iK_dev, const double** beta_dev
 int gpmpc_read_factors(gpmpc_t* h, double* iK_dst_dev, double* beta_dst_dev, void* stream);
 
 /*
+ * gpmpc_predict  <->  the model plot's likelihood(model(x)) on its grid and on the memory points (static_3d_graph.py:77-80, 116):
+ * the exact posterior of each zero-mean ScaleKernel(RBFKernel(ard)) GP (gp_model.py:388-397) with the cached factors iK_a, beta_a
+ * (:425-430); it is also predict_next_state_change (:112-180) at zero input variance, whose S is then diagonal with these entries.
+ *   Xq_dev (M,E)        query inputs in the model-input space of the cached memory (state | action | time when the model has one)
+ *   mean_out_dev (M,D)  k_a(x*)^T beta_a
+ *   var_out_dev (M,D)   sigma2_a - k_a(x*)^T iK_a k_a(x*)  (+ noises_host[a] when noises_host (D) is non-NULL, as likelihood(...) adds)
+ * with k_a(x*)_i = sigma2_a exp(-1/2 sum_e (x*_e - x_ie)^2 / l_ae^2).  The exact posterior, not gpytorch's fast_pred_var (LOVE)
+ * approximation the plot enables; the variance is not clamped, as in the reference's formula.  Either output may be NULL; without
+ * var_out_dev no matrix product is run (the mean is a GEMV).  A point's results are bitwise the same whatever M is and wherever it
+ * sits in the batch.  Asynchronous on `stream`; uses whatever prepare / set_factors / mll cached last; M = 0 launches nothing.
+ * GPMPC_ERR_ARG: no cached model, D / E different from the cached model, M < 0.
+ */
+int gpmpc_predict(gpmpc_t* h, const double* Xq_dev, int M, int D, int E, const double* noises_host, double* mean_out_dev,
+                  double* var_out_dev, void* stream);
+
+/*
  * Options.  Behaviour: "incremental" (0/1, default 1: reuse / border-update the cached factors), "refresh_every" (32: border
  * updates between full factorisations), "cluster" (few-candidate cooperative form: 0 auto, 1 never, 2..32 workgroups per
  * candidate), "threads" (fused-horizon workgroup: 0 auto, 256 / 512 / 1024), "pair_tiles" (batch-major rollout path: 0 auto,
  * 1 always, 2 never).  Dispatch hooks of the parity tests: "rows_per_chunk", "cols_per_lane", "force_path" (1 direct exp,
  * 2 element-wise Taylor), "force_separable", "force_global_scratch", "grad_separable" / "grad_tiles" / "grad_stream" /
- * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n".  Measurement (A/B) switches of single
+ * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
+ * query rows per internal chunk: 0 auto, else a multiple of 64).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);

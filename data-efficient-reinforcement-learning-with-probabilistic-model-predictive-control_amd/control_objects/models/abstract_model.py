@@ -25,6 +25,11 @@ class AbstractStateTransitionModel(abc.ABC):
     def save_state(self):
         """Everything a training process needs (memory + hyper-parameters), picklable."""
 
+    def predict_next_state_change(self, input_mu, input_var):
+        """Moment-matched one-step prediction at a Gaussian model input (mean (E,), covariance (E, E)) ->
+        (mean state change (1, D), its covariance (D, D), Sigma^-1 Cov[input, change] (E, D))."""
+        raise NotImplementedError(f"{type(self).__name__} does not predict at uncertain inputs")
+
     def load_state(self, saved_state):
         raise NotImplementedError(f"{type(self).__name__} does not restore saved states")
 

@@ -319,6 +319,22 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         out = self.engine.predict(inputs, noises=self.noises.detach().cpu().numpy() if include_noise else None)
         return out["mean"], out["var"]
 
+    def predict_next_state_change(self, input_mu, input_var):
+        """Same signature / return as the reference (:112-180): one Gaussian model input, mean (E,) and covariance (E, E) ->
+        (M.t() (1, D), S (D, D), V.t() (E, D)) CPU float64 tensors -- the moment-matched mean state change, its covariance and
+        Sigma^-1 Cov[x, delta]."""
+        mu = _t(input_mu).reshape(1, -1)
+        var = _t(input_var).reshape(1, mu.shape[1], mu.shape[1])
+        out = self.predict_next_state_change_batch(mu, var)
+        return out["M"].cpu(), out["S"][0].cpu(), out["V"][0].cpu()
+
+    def predict_next_state_change_batch(self, input_mu, input_var=None):
+        """predict_next_state_change at P independent inputs: input_mu (P, E), input_var (P, E, E) or None (deterministic
+        inputs) -> dict of DEVICE tensors M (P, D), S (P, D, D), V (P, E, D)."""
+        if self.x_mem is None:
+            raise RuntimeError("call prepare_inference(inputs, state_changes) before predict_next_state_change")
+        return self.engine.moments(input_mu, input_var)
+
     # -- state / training ------------------------------------------------------------------
     def save_state(self):
         return SavedState(inputs=self.x_mem, states_change=self.y_mem,

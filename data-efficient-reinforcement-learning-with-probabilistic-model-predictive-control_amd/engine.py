@@ -187,6 +187,27 @@ class HipEngine:
         self._keep_predict = Xq              # alive until the asynchronous call has read it
         return out
 
+    def moments(self, mu, var=None, S=True, V=True):
+        """Moment-matched one-step prediction (predict_next_state_change, gp_model.py:112-180) at P Gaussian inputs from the
+        cached model: mu (P, E), var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D), V (P, E, D)) of device tensors
+        (S / V only when requested).  Asynchronous on the current stream."""
+        mu = self._dev(mu)
+        if mu.dim() != 2:
+            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
+        P, E = mu.shape
+        D = self.D
+        vr = self._dev(var, (P, E, E)) if var is not None else None
+        out = {"M": torch.empty((P, D), dtype=torch.float64, device=self.device)}
+        if S:
+            out["S"] = torch.empty((P, D, D), dtype=torch.float64, device=self.device)
+        if V:
+            out["V"] = torch.empty((P, E, D), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_moments(self._h, mu.data_ptr(), vr.data_ptr() if vr is not None else None, P, D, E,
+                                           out["M"].data_ptr(), out["S"].data_ptr() if S else None,
+                                           out["V"].data_ptr() if V else None, self._stream()))
+        self._keep_moments = (mu, vr)        # alive until the asynchronous call has read them
+        return out
+
     # -- a6 ----------------------------------------------------------------------------
     def set_cost(self, target, W, W_T, kappa, clip_to_zero=False, state_min=None, state_max=None):
         W_T = _host(W_T)

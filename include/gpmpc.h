@@ -79,13 +79,35 @@ int gpmpc_predict(gpmpc_t* h, const double* Xq_dev, int M, int D, int E, const d
                   double* var_out_dev, void* stream);
 
 /*
+ * gpmpc_moments  <->  predict_next_state_change(input_mu, input_var) (gp_model.py:112-180) at P independent Gaussian model inputs
+ * N(m_p, Sigma_p): the moment-matched one-step prediction of the state change, with a general symmetric E x E Sigma_p (any block
+ * may be non-zero: state, action and time inputs alike; the rollouts only ever pass a state-block one).
+ *   mu_dev (P,E)       input means, in the model-input space of the cached memory (state | action | time when the model has one)
+ *   var_dev (P,E,E)    input covariances, or NULL for all zero
+ *   M_out_dev (P,D)    mean state change (the reference's M.t())
+ *   S_out_dev (P,D,D)  its covariance (S), or NULL: then the pairwise pass is not run at all
+ *   V_out_dev (P,E,D)  Sigma^-1 Cov[x, delta] = dM/dm (V.t()), or NULL
+ * Reads the factors cached by the last prepare / set_factors / mll (X, lengthscales, outputscales, iK, beta).  Sigma is used as
+ * given: it is assumed symmetric positive semi-definite, and is not checked -- a Sigma that is not gives NaN, as in the reference.
+ * A point's M, S and V are bitwise the same whatever P is, wherever the point sits in the batch, whatever its neighbours are and
+ * however the call chunks the batch internally; M and V keep their bits when S_out / V_out are NULL.  The points are processed in
+ * chunks whose workspace stays within 32 MB (or one point's need if that is more: 18 MB at N = 4096, D = 16, E = 20), whatever
+ * P is.  Touches no rollout / gradient workspace and no gpmpc_last_* state.  Asynchronous on `stream`; P = 0 launches nothing.
+ * GPMPC_ERR_ARG: no cached model, D / E different from the cached model, P < 0.  GPMPC_ERR_LIMIT: D > GPMPC_MAX_D or
+ * E > GPMPC_MAX_E.
+ */
+int gpmpc_moments(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P, int D, int E, double* M_out_dev,
+                  double* S_out_dev, double* V_out_dev, void* stream);
+
+/*
  * Options.  Behaviour: "incremental" (0/1, default 1: reuse / border-update the cached factors), "refresh_every" (32: border
  * updates between full factorisations), "cluster" (few-candidate cooperative form: 0 auto, 1 never, 2..32 workgroups per
  * candidate), "threads" (fused-horizon workgroup: 0 auto, 256 / 512 / 1024), "pair_tiles" (batch-major rollout path: 0 auto,
  * 1 always, 2 never).  Dispatch hooks of the parity tests: "rows_per_chunk", "cols_per_lane", "force_path" (1 direct exp,
  * 2 element-wise Taylor), "force_separable", "force_global_scratch", "grad_separable" / "grad_tiles" / "grad_stream" /
  * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
- * query rows per internal chunk: 0 auto, else a multiple of 64).  Measurement (A/B) switches of single
+ * query rows per internal chunk: 0 auto, else a multiple of 64), "moments_chunk_points" (gpmpc_moments' points per internal
+ * chunk: 0 auto).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);

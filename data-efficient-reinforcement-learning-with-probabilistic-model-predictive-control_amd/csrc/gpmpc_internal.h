@@ -117,6 +117,7 @@ struct RolloutArgs {
     // problem
     const double* actions;  // (B, H, A)
     int N, D, A, E, H, B;
+    int B_plan;              // batch the kernel form is planned for (0: B): a slice of a population plans like the population
     int include_time;
     double time0;
     // outputs (nullable)

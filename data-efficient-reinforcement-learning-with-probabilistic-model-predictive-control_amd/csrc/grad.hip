@@ -342,8 +342,10 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
         // Row-chunk length from the schedule model (moment_schedule.h), as a function of the MODEL'S SHAPE ONLY -- evaluated for the
         // throughput configuration (the pairs the element-wise pass keeps when the separable pass takes the off-diagonal ones,
         // two workgroups per CU where they fit, no spreading over blockIdx.z) whatever the batch at hand: every pair's sums are
-        // then formed in the same order for any batch size, grouping and workgroup shape (the lockstep L-BFGS restarts rely on
-        // one candidate's gradient being bit-identical alone and inside a batch).
+        // then formed in the same order for any batch size, grouping and workgroup shape.  The objective and gradient of a
+        // candidate as a whole are bit-identical alone and inside a batch only while both launches take the same forms: the
+        // cooperative forward and the few-candidate moment launch, i.e. 2 B H <= CUs (tests/test_gpu_batch_invariance.py); past
+        // that the forward's and the moment pass's summation orders change with the batch (1e-9 relative at N = 200, B = 128).
         int want = CH0;
         if (h->opt_grad_chunk > 0) want = h->opt_grad_chunk < CH0 ? h->opt_grad_chunk : CH0;
         else {

@@ -164,6 +164,9 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     const int N = a.N, D = a.D, A = a.A, E = a.E;
     const int P = D * (D + 1) / 2;
     const int DP = padded_dim(D);
+    // every batch-size rule below reads Bp, never a.B: a slice planned for its whole population takes the population's form
+    // (same chunk lengths, same summation order), while the grid still covers the a.B candidates launched
+    const int Bp = a.B_plan > a.B ? a.B_plan : a.B;
     if (DP < 0) { h->err = "D exceeds GPMPC_MAX_D"; return GPMPC_ERR_LIMIT; }
 
     // workgroup size: one candidate per workgroup.  Measured on MI355X (config 2..4 shapes, B = 256..2048):
@@ -177,8 +180,8 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // (N = 50, H = 15, tools/gpu_bench_ab.sh: B = 512: 1.85 / 2.61 / 2.16 M rollouts/s with 1024 / 512 / 256 threads,
         // B = 2048: 2.03 / 3.08 / 3.18 M, B = 8192: 2.08 / 3.27 / 3.51 M; at N = 200 1024 threads win at every B).
         if (N <= 64) {
-            if (a.B >= 8 * h->num_cu) nt = 256;
-            else if (a.B >= 2 * h->num_cu) nt = 512;
+            if (Bp >= 8 * h->num_cu) nt = 256;
+            else if (Bp >= 2 * h->num_cu) nt = 512;
         }
     }
     // Mid-size memories with many workgroups per CU: two workgroups of 8 wavefronts share a CU (half the LDS each: the row
@@ -186,7 +189,7 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     // (round 4, profiles/r04h_share_cu.txt, config-2 shape N = 200): B = 512 equal, B = 1024 +2.6 %, B = 4096 +7.9 % (606 -> 654 k
     // rollouts/s); N = 500: -4 % at B = 1024, +2.6 % at 4096; N = 50: equal.  Hence from 8 workgroups per CU on, N in (64, 256].
     bool share_cu = false;
-    if (h->opt_threads == 0 && h->opt_lds_kb == 0 && N > 64 && N <= 256 && D <= 4 && a.B >= 8 * h->num_cu && h->opt_pair_tiles != 1) {
+    if (h->opt_threads == 0 && h->opt_lds_kb == 0 && N > 64 && N <= 256 && D <= 4 && Bp >= 8 * h->num_cu && h->opt_pair_tiles != 1) {
         nt = 512;
         share_cu = true;
     }
@@ -218,7 +221,7 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     bool tiled = false;
     if (!gs && cols2 && DP <= 4 && nt == 1024 && h->opt_pair_tiles != 2) {
         const double tri_bytes = 4.0 * D * (double)N * N;          // upper triangles of the D tables
-        tiled = h->opt_pair_tiles == 1 || (tri_bytes >= 6.0e6 && a.B >= 2 * h->num_cu);
+        tiled = h->opt_pair_tiles == 1 || (tri_bytes >= 6.0e6 && Bp >= 2 * h->num_cu);
         tiled = tiled && tile_path_supported(h, a);
     }
     const int Pg = tiled ? (P - D > 0 ? P - D : 1) : P;           // pairs the per-candidate kernel keeps row records for
@@ -255,9 +258,10 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     // fit the chip one workgroup per CU -- every member must be resident, they wait for each other once per horizon step.
     // Candidates are placed in groups of 8 (one per XCD), so the grid is 8 x cluster x ceil(B / 8) workgroups.
     int cluster = 1;
-    const int groups8 = (a.B + 7) / 8;
+    const int groups8 = (a.B + 7) / 8;            // launched
+    const int groups8p = (Bp + 7) / 8;            // planned: the cluster size and whether the form fits at all
     bool want_cluster = !gs && !tiled && cols2 && DP <= 4 && !share_cu && h->opt_lds_kb == 0 &&
-                        h->opt_cluster != 1 && a.H < 8191 && 8 * groups8 * 2 <= h->num_cu;
+                        h->opt_cluster != 1 && a.H < 8191 && 8 * groups8p * 2 <= h->num_cu;
     auto choose_layout = [&](bool cl) {
         G = 0;
         // X^T in LDS when it is small next to the budget (<= 32 KiB) and the layout still fits
@@ -292,7 +296,7 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // 0.128 / 0.128, N = 80 0.129 / 0.151, N = 130 0.133 / 0.179; D = 2: N = 100 0.117 / 0.103, N = 150 equal, N = 200 0.139 / 0.173;
         // D = 1: N = 200 0.118 / 0.112, N = 400 0.139 / 0.203; D = 4: N = 100 0.184 / 0.334); with fewer members per candidate from
         // ~24 items on, as before
-        const int cap = h->num_cu / (8 * groups8);
+        const int cap = h->num_cu / (8 * groups8p);
         const int items = D * wtri, P_off = D * (D - 1) / 2;
         const int cs_floor = (P_off + 2 * D > 9) ? P_off + 2 * D : 9;
         const bool roomy = cap >= cs_floor;

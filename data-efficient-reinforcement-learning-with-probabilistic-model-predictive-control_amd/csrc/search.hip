@@ -318,6 +318,7 @@ int run_cem_local(Handle* h, RolloutArgs& a, int B_total, int b0, int it, int n_
     hipLaunchKernelGGL(cem_map_kernel, dim3((Bl * A + 255) / 256), dim3(256), 0, s, Bl, H, A, mapper, mc, ap, X, acts);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     RolloutArgs ai = a;
+    ai.B_plan = B_total;                 // every slice takes the form (and so the summation order) of the whole population
     rc = launch_rollout(h, ai, s);
     if (rc) return rc;
     hipLaunchKernelGGL(cem_elites_kernel, dim3(1), dim3(1024), 0, s, Bl, n, n_elite, b0, J, X, elites_out_dev);

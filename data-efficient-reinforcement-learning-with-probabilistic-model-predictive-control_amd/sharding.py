@@ -319,7 +319,8 @@ def sharded_cem_search(engine, mu0, S0, B_total, H, A, iterations, n_elite, seed
     iteration every rank draws and evaluates its contiguous slice of the B_total candidates (the draws are keyed by the
     GLOBAL candidate index, so the union of the slices is the single-GPU population), ONE all_gather of the slices' elite
     records (n_elite x (2 + H A) doubles per rank, RCCL on the compute stream: the refit needs them), and every rank refits
-    on the union -- all ranks end with the same state, the one the single-GPU search reaches on the same draws.
+    on the union -- all ranks end with the same state, the one the single-GPU search reaches on the same draws, bit for bit
+    at any cut: every slice plans its rollout's kernel form for the whole population (tests/test_gpu_batch_invariance.py).
     Nothing is read back between iterations.  Returns (best vector (H*A,) numpy, best J)."""
     multi = _active(group)
     world = dist.get_world_size(group) if multi else 1

@@ -42,6 +42,7 @@ SIGNATURES = {
     "gpmpc_read_factors": (C.c_int, [_P, _P, _P, _P]),
     "gpmpc_predict": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_last_prepare_mode": (C.c_int, [_P]),
     "gpmpc_last_rollout_path": (C.c_int, [_P]),
     "gpmpc_last_grad_path": (C.c_int, [_P]),

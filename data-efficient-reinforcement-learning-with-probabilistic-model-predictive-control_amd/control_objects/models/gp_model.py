@@ -29,6 +29,32 @@ def _t(v):
     return torch.as_tensor(np.asarray(v), dtype=F64) if not isinstance(v, torch.Tensor) else v.to(F64)
 
 
+class _MomentsFunction(torch.autograd.Function):
+    """engine.moments as an autograd node: (mu (P, E), var (P, E, E) or None) -> (M, S, V); its backward is
+    engine.moments_backward (gpmpc_moments_backward).  The covariance's gradient is the symmetric part.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, engine, mu, var):
+        ctx.engine = engine
+        ctx.set_materialize_grads(False)          # an unused output is a NULL upstream gradient (no S: no pairwise pass)
+        ctx.save_for_backward(mu, var)
+        out = engine.moments(mu, var)
+        return out["M"], out["S"], out["V"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, M_bar, S_bar, V_bar):
+        mu, var = ctx.saved_tensors
+        want_mu, want_var = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if M_bar is None and S_bar is None and V_bar is None:
+            return None, None, None
+        g = ctx.engine.moments_backward(mu.detach(), var.detach() if var is not None else None, M_bar, S_bar, V_bar,
+                                        mu_bar=want_mu, var_bar=want_var)
+        mu_bar = g["mu_bar"].to(device=mu.device, dtype=mu.dtype) if want_mu else None
+        var_bar = g["var_bar"].to(device=var.device, dtype=var.dtype) if want_var else None
+        return None, mu_bar, var_bar
+
+
 class SavedState:
     """In-memory snapshot shipped to the training process (reference gp_model.py:13-36)."""
 
@@ -322,7 +348,10 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
     def predict_next_state_change(self, input_mu, input_var):
         """Same signature / return as the reference (:112-180): one Gaussian model input, mean (E,) and covariance (E, E) ->
         (M.t() (1, D), S (D, D), V.t() (E, D)) CPU float64 tensors -- the moment-matched mean state change, its covariance and
-        Sigma^-1 Cov[x, delta]."""
+        Sigma^-1 Cov[x, delta].  Differentiable like the reference: when grad mode is on and input_mu or input_var requires
+        grad, the outputs carry a grad_fn and backward() reaches the inputs (CPU or device) through gpmpc_moments_backward.
+        input_var's gradient is the symmetric part of the reference's.  Hyper-parameters and the memory get no gradient, and
+        double backward raises."""
         mu = _t(input_mu).reshape(1, -1)
         var = _t(input_var).reshape(1, mu.shape[1], mu.shape[1])
         out = self.predict_next_state_change_batch(mu, var)
@@ -330,10 +359,17 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
 
     def predict_next_state_change_batch(self, input_mu, input_var=None):
         """predict_next_state_change at P independent inputs: input_mu (P, E), input_var (P, E, E) or None (deterministic
-        inputs) -> dict of DEVICE tensors M (P, D), S (P, D, D), V (P, E, D)."""
+        inputs) -> dict of DEVICE tensors M (P, D), S (P, D, D), V (P, E, D).  Differentiable as predict_next_state_change is
+        when grad mode is on and an input requires grad (input_var None: the mean's gradient only)."""
         if self.x_mem is None:
             raise RuntimeError("call prepare_inference(inputs, state_changes) before predict_next_state_change")
-        return self.engine.moments(input_mu, input_var)
+        grads = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (input_mu, input_var))
+        if not grads:
+            return self.engine.moments(input_mu, input_var)
+        mu = _t(input_mu)
+        var = _t(input_var) if input_var is not None else None
+        M, S, V = _MomentsFunction.apply(self.engine, mu, var)
+        return {"M": M, "S": S, "V": V}
 
     # -- state / training ------------------------------------------------------------------
     def save_state(self):

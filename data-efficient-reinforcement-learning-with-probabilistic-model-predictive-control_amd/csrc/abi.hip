@@ -81,7 +81,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->momws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->momws, &h->mombws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -122,6 +122,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "moments_chunk_points")) {
         if (value < 0 || value > (1 << 24)) { h->err = "moments_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
         h->opt_moments_chunk = (int)value;
+    }
+    else if (!strcmp(name, "moments_backward_chunk_points")) {
+        if (value < 0 || value > (1 << 24)) { h->err = "moments_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
+        h->opt_moments_bwd_chunk = (int)value;
     }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
@@ -228,6 +232,24 @@ int gpmpc_moments(gpmpc_t* g, const double* mu, const double* var, int P, int D,
     if (P == 0) return GPMPC_OK;
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_moments(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+}
+
+int gpmpc_moments_backward(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, const double* M_bar,
+                           const double* S_bar, const double* V_bar, double* mu_bar_out, double* var_bar_out, void* stream) {
+    Range roctx_range("gpmpc_moments_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "moments_backward before prepare / set_factors / mll");
+    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
+        h->err = "moments_backward: D or E beyond the compiled limits";
+        return GPMPC_ERR_LIMIT;
+    }
+    if (D != h->D || E != h->E) return bad(g, "moments_backward: D / E differ from the cached model");
+    if (P < 0) return bad(g, "moments_backward: P < 0");
+    if (P > 0 && !mu) return bad(g, "null argument");
+    if (P == 0) return GPMPC_OK;
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_moments_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
 }
 
 int gpmpc_mll(gpmpc_t* g, const double* X, const double* Y, const double* ls, const double* os, const double* noise,

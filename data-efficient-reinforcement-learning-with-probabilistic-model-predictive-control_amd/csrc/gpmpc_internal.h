@@ -212,6 +212,7 @@ struct Handle {
     Buf tgradws;  // gradient's tile pass: records of a block of (candidate, step) items | per-tile partial moments
     Buf predws;   // gpmpc_predict: per-(query row, column block) partial sums of one chunk of query rows
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
+    Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -302,6 +303,7 @@ struct Handle {
     int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
+    int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int lds_limit = 160 * 1024;
     int num_cu = 256;
 };
@@ -356,6 +358,9 @@ int run_predict(Handle* h, const double* Xq, int M, const double* noises_host, d
 // moments.hip: moment-matched prediction at P Gaussian inputs from the cached model (Sig NULL = 0; S_out / V_out may be NULL)
 int run_moments(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                 hipStream_t s);
+// moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
+int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
+                         const double* Vb, double* mb_out, double* vb_out, hipStream_t s);
 // search.hip: cross-entropy search whose loop stays on the device (actions / J_out of `a` are set inside)
 int run_cem_search(Handle* h, RolloutArgs& a, int iterations, int n_elite, unsigned long long seed, const double* first_host,
                    int mapper, const double* max_change_host, const double* a_prev_host, const double* noise_dev,

@@ -208,6 +208,31 @@ class HipEngine:
         self._keep_moments = (mu, vr)        # alive until the asynchronous call has read them
         return out
 
+    def moments_backward(self, mu, var=None, M_bar=None, S_bar=None, V_bar=None, mu_bar=True, var_bar=True):
+        """Reverse-mode product of `moments` (autograd through predict_next_state_change, gp_model.py:112-180): mu (P, E),
+        var (P, E, E) or None (zero), upstream gradients M_bar (P, D), S_bar (P, D, D), V_bar (P, E, D), each None for zero ->
+        dict(mu_bar (P, E), var_bar (P, E, E)) of device tensors (each only when requested).  var_bar is the symmetric part of
+        the covariance gradient.  Without S_bar the pairwise pass is skipped.  Asynchronous on the current stream."""
+        mu = self._dev(mu)
+        if mu.dim() != 2:
+            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
+        P, E = mu.shape
+        D = self.D
+        vr = self._dev(var, (P, E, E)) if var is not None else None
+        Mb = self._dev(M_bar, (P, D)) if M_bar is not None else None
+        Sb = self._dev(S_bar, (P, D, D)) if S_bar is not None else None
+        Vb = self._dev(V_bar, (P, E, D)) if V_bar is not None else None
+        out = {}
+        if mu_bar:
+            out["mu_bar"] = torch.empty((P, E), dtype=torch.float64, device=self.device)
+        if var_bar:
+            out["var_bar"] = torch.empty((P, E, E), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_moments_backward(self._h, mu.data_ptr(), ptr(vr), P, D, E, ptr(Mb), ptr(Sb), ptr(Vb),
+                                                    ptr(out.get("mu_bar")), ptr(out.get("var_bar")), self._stream()))
+        self._keep_moments_backward = (mu, vr, Mb, Sb, Vb)   # alive until the asynchronous call has read them
+        return out
+
     # -- a6 ----------------------------------------------------------------------------
     def set_cost(self, target, W, W_T, kappa, clip_to_zero=False, state_min=None, state_max=None):
         W_T = _host(W_T)

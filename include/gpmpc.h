@@ -100,6 +100,29 @@ int gpmpc_moments(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P
                   double* S_out_dev, double* V_out_dev, void* stream);
 
 /*
+ * gpmpc_moments_backward  <->  torch autograd through predict_next_state_change (gp_model.py:112-180): the reverse-mode product
+ * (vector-Jacobian product) of gpmpc_moments at the same P inputs.  For upstream gradients M_bar, S_bar, V_bar it returns the
+ * gradients of <M_bar, M> + <S_bar, S> + <V_bar, V> with respect to the input mean and the input covariance.
+ *   mu_dev, var_dev    as in gpmpc_moments (var_dev NULL = all-zero covariances; the gradient at Sigma = 0 is still returned)
+ *   M_bar_dev (P,D)    upstream gradient of M, or NULL (= 0)
+ *   S_bar_dev (P,D,D)  upstream gradient of S, or NULL (= 0): then the pairwise pass is not run at all (O(N) per point)
+ *   V_bar_dev (P,E,D)  upstream gradient of V (the layout of V_out), or NULL (= 0)
+ *   mu_bar_out_dev (P,E)      d/d mu, or NULL (not written)
+ *   var_bar_out_dev (P,E,E)   d/d Sigma, its symmetric part, or NULL (not written)
+ * Outputs are overwritten, not accumulated into.  Sigma's gradient is the symmetric part sym(G) = (G + G^T) / 2: the reference's
+ * formula is not symmetric in Sigma away from symmetric matrices, so autograd's raw G is not symmetric, but <G, dSigma> =
+ * <sym(G), dSigma> for every symmetric dSigma; a caller that parametrises Sigma = A A^T gets 2 sym(G) A either way.  Hyper-
+ * parameters and the memory get no gradient.  A point's results are bitwise the same whatever P is, wherever the point sits,
+ * whatever its neighbours are and however the batch is chunked; the chunks' workspace stays within 32 MB (or one point's need if
+ * that is more: 29 MB at N = 4096, D = 16, E = 20).  Touches no rollout / gradient / gpmpc_moments workspace and no gpmpc_last_*
+ * state.  Asynchronous on `stream`; P = 0 launches nothing.  Errors as gpmpc_moments (GPMPC_ERR_ARG also for mu_dev NULL with
+ * P > 0).
+ */
+int gpmpc_moments_backward(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P, int D, int E, const double* M_bar_dev,
+                           const double* S_bar_dev, const double* V_bar_dev, double* mu_bar_out_dev, double* var_bar_out_dev,
+                           void* stream);
+
+/*
  * Options.  Behaviour: "incremental" (0/1, default 1: reuse / border-update the cached factors), "refresh_every" (32: border
  * updates between full factorisations), "cluster" (few-candidate cooperative form: 0 auto, 1 never, 2..32 workgroups per
  * candidate), "threads" (fused-horizon workgroup: 0 auto, 256 / 512 / 1024), "pair_tiles" (batch-major rollout path: 0 auto,
@@ -107,7 +130,7 @@ int gpmpc_moments(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P
  * 2 element-wise Taylor), "force_separable", "force_global_scratch", "grad_separable" / "grad_tiles" / "grad_stream" /
  * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
  * query rows per internal chunk: 0 auto, else a multiple of 64), "moments_chunk_points" (gpmpc_moments' points per internal
- * chunk: 0 auto).  Measurement (A/B) switches of single
+ * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);

@@ -55,6 +55,53 @@ class _MomentsFunction(torch.autograd.Function):
         return None, mu_bar, var_bar
 
 
+class _TrajectoryFunction(torch.autograd.Function):
+    """engine.rollout as an autograd node: (actions (B, H, A), obs_mu (D,), obs_var (D, D)) -> the rollout's outputs named by
+    ctx.keys (mu, Sig and, where the rollout returns them, cost_mu, cost_var, J; copied into `keys_out`); its backward is engine.rollout_backward
+    (gpmpc_rollout_backward, which recomputes the forward).  The shared initial state's gradients are the sums over the
+    candidates; obs_var's is the symmetric part.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, engine, include_time, time0, stage_costs, keys_out, actions, obs_mu, obs_var):
+        ctx.engine, ctx.include_time, ctx.time0 = engine, include_time, time0
+        ctx.set_materialize_grads(False)          # an unused output is a NULL upstream gradient
+        ctx.save_for_backward(actions, obs_mu, obs_var)
+        out = engine.rollout(actions, obs_mu.detach().cpu().numpy(), obs_var.detach().cpu().numpy(), include_time, time0,
+                             True, stage_costs)
+        ctx.keys = tuple(k for k in ("mu", "Sig", "cost_mu", "cost_var", "J") if k in out)
+        keys_out[:] = ctx.keys
+        return tuple(out[k] for k in ctx.keys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        actions, obs_mu, obs_var = ctx.saved_tensors
+        seeds = dict(zip(ctx.keys, grads))
+        want_act, want_mu, want_var = ctx.needs_input_grad[5:8]
+        if all(g is None for g in grads):
+            return None, None, None, None, None, None, None, None
+        g = ctx.engine.rollout_backward(actions.detach(), obs_mu.detach().cpu().numpy(), obs_var.detach().cpu().numpy(),
+                                        ctx.include_time, ctx.time0, mu_bar=seeds.get("mu"), Sig_bar=seeds.get("Sig"),
+                                        cost_mu_bar=seeds.get("cost_mu"), cost_var_bar=seeds.get("cost_var"),
+                                        J_bar=seeds.get("J"), want_initial=want_mu or want_var)
+        act_bar = g["actions_bar"].to(device=actions.device, dtype=actions.dtype) if want_act else None
+        # one reduction over the candidates (a fixed order for a given B)
+        mu_bar = g["mu0_bar"].sum(0).reshape(obs_mu.shape).to(device=obs_mu.device, dtype=obs_mu.dtype) if want_mu else None
+        var_bar = g["S0_bar"].sum(0).reshape(obs_var.shape).to(device=obs_var.device, dtype=obs_var.dtype) if want_var else None
+        return None, None, None, None, None, act_bar, mu_bar, var_bar
+
+
+def _check_trajectory_grad_shape(D, A, include_time):
+    """The shapes gpmpc_rollout_backward covers (D <= 8 with A (+ time) <= 6, and 8 < D <= 16): raised at the forward, not at
+    backward()."""
+    if (D <= 8 and A + int(bool(include_time)) <= 6) or 8 < D <= 16:
+        return
+    from ..._lib import GPMPC_ERR_LIMIT, GpmpcError
+    raise GpmpcError(GPMPC_ERR_LIMIT, f"predict_trajectory gradients: D = {D}, A = {A}{' + time' if include_time else ''} is "
+                     "outside the gradient kernels (D <= 8 with A (+ time) <= 6, or 8 < D <= 16); differentiate such shapes by "
+                     "chaining predict_next_state_change, whose gradients cover them")
+
+
 class SavedState:
     """In-memory snapshot shipped to the training process (reference gp_model.py:13-36)."""
 
@@ -303,14 +350,31 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
     def predict_trajectory_batch(self, actions, obs_mu, obs_var, len_horizon=None, current_time_idx=0,
                                  trajectories=True, stage_costs=True):
         """actions (B,H,A) -> dict of DEVICE tensors: J (B,), mu (B,H+1,D), Sig (B,H+1,D,D),
-        cost_mu / cost_var (B,H+1).  Costs need set_cost() first."""
+        cost_mu / cost_var (B,H+1).  Costs need set_cost() first.  Differentiable like the reference's predict_trajectory
+        followed by get_rewards_trajectory: when grad mode is on and actions, obs_mu or obs_var requires grad, mu, Sig and
+        (with set_cost) cost_mu, cost_var and J carry a grad_fn, and backward() reaches the inputs (CPU or device, each
+        gradient in its input's dtype) through gpmpc_rollout_backward, which recomputes the forward.  obs_mu and obs_var are
+        shared by the candidates: their gradients are the sums over the batch, obs_var's the symmetric part of the
+        reference's.  The time input, hyper-parameters and memory get no gradient, and double backward raises.  Shapes outside
+        the gradient kernels (D <= 8 with A (+ time) <= 6, or 8 < D <= 16) raise GpmpcError(GPMPC_ERR_LIMIT) here, before any
+        launch; chain predict_next_state_change to differentiate those."""
         if self._cost_key is None and stage_costs:
             raise RuntimeError("call set_cost(reward_config) before predicting costs")
+        grads = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (actions, obs_mu, obs_var))
         actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
         if len_horizon is not None and actions.shape[1] != len_horizon:
             raise ValueError("actions.shape[1] != len_horizon")
-        return self.engine.rollout(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model,
-                                   float(current_time_idx), trajectories, stage_costs)
+        if not grads:
+            return self.engine.rollout(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model,
+                                       float(current_time_idx), trajectories, stage_costs)
+        _check_trajectory_grad_shape(self.dim_state, actions.shape[2], self.config.include_time_model)
+        keys = []
+        outs = _TrajectoryFunction.apply(self.engine, self.config.include_time_model, float(current_time_idx), stage_costs, keys,
+                                         actions, _t(obs_mu), _t(obs_var))
+        out = dict(zip(keys, outs))
+        if not trajectories:
+            del out["mu"], out["Sig"]
+        return out
 
     def objective_and_gradient_batch(self, actions, obs_mu, obs_var, current_time_idx=0, trajectories=False):
         """actions (B,H,A) -> dict of DEVICE tensors: J (B,), grad (B,H,A) = dJ/d(actions) (analytic; what the
@@ -331,7 +395,10 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                                                self.config.include_time_model, float(current_time_idx))
 
     def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx):
-        """Same signature / return shapes as the reference (:60-110): ((H+1,D), (H+1,D,D)) CPU tensors."""
+        """Same signature / return shapes as the reference (:60-110): ((H+1,D), (H+1,D,D)) CPU tensors.  Differentiable like
+        the reference: when grad mode is on and actions, obs_mu or obs_var requires grad, both outputs carry a grad_fn and
+        backward() reaches the inputs through gpmpc_rollout_backward (see predict_trajectory_batch); obs_var's gradient is the
+        symmetric part of the reference's."""
         out = self.predict_trajectory_batch(_t(actions)[None], obs_mu, obs_var, len_horizon, current_time_idx,
                                             trajectories=True, stage_costs=False)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()

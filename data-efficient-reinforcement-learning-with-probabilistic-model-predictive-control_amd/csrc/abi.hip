@@ -347,6 +347,23 @@ int gpmpc_rollout_grad(gpmpc_t* g, const double* actions, const double* mu0, con
     return launch_rollout_grad(H_(g), a, grad_out, (hipStream_t)stream);
 }
 
+int gpmpc_rollout_backward(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
+                           int include_time, double time0, const double* mu_bar, const double* Sig_bar, const double* cm_bar,
+                           const double* cv_bar, const double* J_bar, double* actions_bar_out, double* mu0_bar_out,
+                           double* S0_bar_out, void* stream) {
+    Range roctx_range("gpmpc_rollout_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!actions_bar_out) return bad(g, "null argument");
+    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
+    RolloutArgs a;
+    // the trajectory's cotangents alone need no cost settings; a cost or objective seed needs gpmpc_set_cost for this (D, A)
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "gradient needs A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return launch_rollout_grad(H_(g), a, actions_bar_out, (hipStream_t)stream, &sd);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // One evaluation for a host-side optimiser: the action sequence travels to the device in the forward kernel's argument block (no
 // DMA engine start-up, no launch of its own for 200 bytes), the results come back through a pinned, device-mapped host buffer

@@ -340,8 +340,17 @@ bool tile_moments_fusable(Handle* h, const RolloutArgs& a);
 bool tile_moments_supported(Handle* h, const RolloutArgs& a, int NSP);
 int launch_tile_moments(Handle* h, const RolloutArgs& a, double* mom, int* done, int NSP, int NXP, hipStream_t s);
 // grad.hip
-int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s);
-int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s);     // grad_wide.hip: 8 < D <= 16
+// Cotangents of gpmpc_rollout_backward (each NULL = 0) and its initial-state outputs (each NULL = not written); `cost`: a cost or
+// objective seed is given (the forward then computes the stage costs, the sweep reads the loaded cost settings)
+struct RolloutSeeds {
+    const double* mu; const double* Sig; const double* cm; const double* cv; const double* J;
+    double* mu0_bar; double* S0_bar;
+    bool cost;
+};
+// seeds == NULL: gpmpc_rollout_grad's LCB gradient; otherwise the same launch sequence with the seeded reverse sweep
+int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s, const RolloutSeeds* seeds = nullptr);
+int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s,          // grad_wide.hip: 8 < D <= 16
+                             const RolloutSeeds* seeds = nullptr);
 int launch_argmin_to(Handle* h, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
                      hipStream_t s);
 // prepare.hip

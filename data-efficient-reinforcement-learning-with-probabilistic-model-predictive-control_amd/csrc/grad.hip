@@ -50,13 +50,14 @@ __global__ __launch_bounds__(NT) void few_candidate_moments_kernel(const GradArg
                    cs.cm, cs.cv, cs.J);
 }
 
+// (cs.cost NULL: no stage costs are wanted -- the grid stops before the cost slice)
 template <int DP, int NXP>
 int launch_few_candidate_moments(Handle* h, const GradArgs& g, const CostSlice& cs, size_t lds_bytes, hipStream_t s) {
     constexpr int NT = DP <= 3 ? 1024 : kMomThreads;
     auto kern = few_candidate_moments_kernel<DP, NXP, NT>;
     int rc = allow_full_lds(h, reinterpret_cast<const void*>(kern));
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(g.H, g.B, g.gz + 2), dim3(NT), lds_bytes, s, g, cs);
+    hipLaunchKernelGGL(kern, dim3(g.H, g.B, g.gz + (cs.cost ? 2 : 1)), dim3(NT), lds_bytes, s, g, cs);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     return GPMPC_OK;
 }
@@ -67,9 +68,9 @@ int launch_few_candidate_moments_dp(Handle* h, const GradArgs& g, const CostSlic
     return g.NXP == 2 ? launch_few_candidate_moments<DP, 2>(h, g, cs, lds_bytes, s) : launch_few_candidate_moments<DP, 6>(h, g, cs, lds_bytes, s);
 }
 
-template <int DP, int NT>
-int launch_sweep(Handle* h, const GradArgs& g, size_t lds_bytes, hipStream_t s) {
-    auto kern = (g.D == DP) ? adjoint_sweep_kernel<DP, NT, DP> : adjoint_sweep_kernel<DP, NT, 0>;
+template <int DP, int NT, bool SEEDED>
+int launch_sweep(Handle* h, const std::conditional_t<SEEDED, SeededGradArgs, GradArgs>& g, size_t lds_bytes, hipStream_t s) {
+    auto kern = (g.D == DP) ? adjoint_sweep_kernel<DP, NT, DP, SEEDED> : adjoint_sweep_kernel<DP, NT, 0, SEEDED>;
     int rc = allow_full_lds(h, reinterpret_cast<const void*>(kern));
     if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(g.B), dim3(NT), lds_bytes, s, g);
@@ -99,13 +100,26 @@ int launch_moments_dp(Handle* h, const GradArgs& g, size_t lds_bytes, hipStream_
     return g.NXP == 2 ? launch_moments<DP, 2>(h, g, lds_bytes, s) : launch_moments<DP, 6>(h, g, lds_bytes, s);
 }
 
+template <bool SEEDED>
+int dispatch_sweep(Handle* h, const std::conditional_t<SEEDED, SeededGradArgs, GradArgs>& g, int DP, int sweep_nt, size_t lds,
+                   hipStream_t s) {
+    switch (DP) {
+        case 2:  return sweep_nt == 512 ? launch_sweep<2, 512, SEEDED>(h, g, lds, s) : (sweep_nt == 256 ? launch_sweep<2, 256, SEEDED>(h, g, lds, s) : launch_sweep<2, 64, SEEDED>(h, g, lds, s));
+        case 3:  return sweep_nt == 512 ? launch_sweep<3, 512, SEEDED>(h, g, lds, s) : (sweep_nt == 256 ? launch_sweep<3, 256, SEEDED>(h, g, lds, s) : launch_sweep<3, 64, SEEDED>(h, g, lds, s));
+        case 4:  return sweep_nt == 512 ? launch_sweep<4, 512, SEEDED>(h, g, lds, s) : (sweep_nt == 256 ? launch_sweep<4, 256, SEEDED>(h, g, lds, s) : launch_sweep<4, 64, SEEDED>(h, g, lds, s));
+        case 6:  return launch_sweep<6, 256, SEEDED>(h, g, lds, s);
+        default: return launch_sweep<8, 256, SEEDED>(h, g, lds, s);
+    }
+}
+
 }  // namespace
 
-int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s) {
+int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s, const RolloutSeeds* seeds) {
     const int N = a.N, D = a.D, A = a.A, E = a.E, H = a.H, B = a.B;
     const int NX = E - D, P = D * (D + 1) / 2;
     h->last_grad_path = 0;
-    if (D > 8) { h->last_grad_path = 8; return launch_rollout_grad_wide(h, a, grad_out, s); }
+    if (D > 8) { h->last_grad_path = 8; return launch_rollout_grad_wide(h, a, grad_out, s, seeds); }
+    const bool costs = !seeds || seeds->cost;      // (a backward of the trajectory alone: no stage costs, no cost settings read)
     int DP = 0;
     for (int v : {2, 3, 4, 6, 8}) if (D <= v) { DP = v; break; }
     if (DP == 0 || NX > 6) { h->err = "gradient: supported for D <= 8 with A (+ time) <= 6, and for 8 < D <= 16"; return GPMPC_ERR_LIMIT; }
@@ -160,7 +174,7 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
         const SweepLayout Lp = make_sweep_layout(D, A, E, H, NSP, sweep_nt / 64, 0, H);
         if ((size_t)Lp.total * 8 <= 96 * 1024) pre_steps = H;
     }
-    const SweepLayout SL = make_sweep_layout(D, A, E, H, NSP, sweep_nt / 64, DP <= 4 ? 0 : kSweepAug, pre_steps);
+    const SweepLayout SL = make_sweep_layout(D, A, E, H, NSP, sweep_nt / 64, DP <= 4 ? 0 : kSweepAug, pre_steps, seeds ? H + 1 : 0);
     if ((size_t)SL.total * 8 > (size_t)h->lds_limit) { h->err = "gradient: horizon too long for the reverse sweep's LDS"; return GPMPC_ERR_LIMIT; }
     // memories whose per-point arrays do not fit the LDS (or on request) take the streaming moment pass
     bool stream = (G == 0) || h->opt_grad_stream == 1;
@@ -184,7 +198,7 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
     g.mom = h->gradws.p;
     g.msum = g.mom + n_mom;
     int* sep_flags = reinterpret_cast<int*>(g.msum + n_ms + n_cv);
-    if (!a.cv_out) a.cv_out = g.msum + n_ms;
+    if (!a.cv_out && costs) a.cv_out = g.msum + n_ms;
 
     // Diagonal pairs batch-major (pair_tile_grad_kernel.h) once the tables T_a are large and the batch fills the chip.  When the
     // forward itself takes the batch-major path, its tile pass forms these moments on the way (the same E_ij would otherwise be
@@ -294,7 +308,7 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
         h->last_grad_path |= 2;
     }
     const bool merged = cost_pending && g.sepdone == nullptr && !want_tiles && gz >= 1;
-    if (cost_pending && !merged) {
+    if (cost_pending && !merged && costs) {
         // (the separable / tile passes took pairs after all: the costs as their own launch)
         rc = launch_traj_cost(h, a, want_cm, a.cv_out, want_J, s);
         if (rc) return rc;
@@ -382,7 +396,7 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
     if (merged) {
         g.mean_done = 1;
         h->last_grad_path |= 32 | 64;
-        const CostSlice cs{a.cost, a.kappa, a.clip, a.use_constraints, want_cm, a.cv_out, want_J};
+        const CostSlice cs{costs ? a.cost : nullptr, a.kappa, a.clip, a.use_constraints, want_cm, a.cv_out, want_J};
         switch (DP) {
             case 2:  rc = launch_few_candidate_moments_dp<2>(h, g, cs, mom_lds, s); break;
             case 3:  rc = launch_few_candidate_moments_dp<3>(h, g, cs, mom_lds, s); break;
@@ -398,12 +412,14 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
     }
     }
     if (rc) return rc;
-    switch (DP) {
-        case 2:  rc = sweep_nt == 512 ? launch_sweep<2, 512>(h, g, (size_t)SL.total * 8, s) : (sweep_nt == 256 ? launch_sweep<2, 256>(h, g, (size_t)SL.total * 8, s) : launch_sweep<2, 64>(h, g, (size_t)SL.total * 8, s)); break;
-        case 3:  rc = sweep_nt == 512 ? launch_sweep<3, 512>(h, g, (size_t)SL.total * 8, s) : (sweep_nt == 256 ? launch_sweep<3, 256>(h, g, (size_t)SL.total * 8, s) : launch_sweep<3, 64>(h, g, (size_t)SL.total * 8, s)); break;
-        case 4:  rc = sweep_nt == 512 ? launch_sweep<4, 512>(h, g, (size_t)SL.total * 8, s) : (sweep_nt == 256 ? launch_sweep<4, 256>(h, g, (size_t)SL.total * 8, s) : launch_sweep<4, 64>(h, g, (size_t)SL.total * 8, s)); break;
-        case 6:  rc = launch_sweep<6, 256>(h, g, (size_t)SL.total * 8, s); break;
-        default: rc = launch_sweep<8, 256>(h, g, (size_t)SL.total * 8, s); break;
+    if (seeds) {
+        SeededGradArgs sg;
+        static_cast<GradArgs&>(sg) = g;
+        sg.host_n = 0;
+        sg.sd = SweepSeeds{seeds->mu, seeds->Sig, seeds->cm, seeds->cv, seeds->J, seeds->mu0_bar, seeds->S0_bar};
+        rc = dispatch_sweep<true>(h, sg, DP, sweep_nt, (size_t)SL.total * 8, s);
+    } else {
+        rc = dispatch_sweep<false>(h, g, DP, sweep_nt, (size_t)SL.total * 8, s);
     }
     if (rc) return rc;
     return GPMPC_OK;

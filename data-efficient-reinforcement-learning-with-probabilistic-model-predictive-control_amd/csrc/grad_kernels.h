@@ -16,6 +16,8 @@
 //
 // The derivation is written out in DESIGN.md (section 4.4); a numpy statement of it lives with the tests.
 #pragma once
+#include <type_traits>
+
 #include "rollout_kernel.h"
 
 namespace gpmpc_hip {
@@ -56,6 +58,31 @@ struct GradArgs {
     double* host_out; const double* host_src; int host_n;
     unsigned long long* host_flag; unsigned long long host_flag_value;
 };
+
+// The seeded sweeps (gpmpc_rollout_backward): caller-given cotangents of the trajectory and its costs (each NULL = 0) and the
+// adjoints of the initial state (each NULL = not written).  Only the SEEDED instantiations take them (SeededGradArgs,
+// SeededWideArgs): the argument block of every other kernel is the one gpmpc_rollout_grad always had.
+struct SweepSeeds {
+    const double* mu;    // (B, H+1, D)
+    const double* Sig;   // (B, H+1, D, D)
+    const double* cm;    // (B, H+1)
+    const double* cv;    // (B, H+1)
+    const double* J;     // (B)
+    double* mu0_bar;     // (B, D)
+    double* S0_bar;      // (B, D, D)
+};
+struct SeededGradArgs : GradArgs { SweepSeeds sd; };
+
+// Cost weights of step t in the seeded sweep, the LCB's 1/(H+1) and -kappa / (2 sqrt(cv_t) (H+1)) generalised:
+//   wm = cost_mu_bar_t + J_bar / (H+1),  wv = cost_var_bar_t + J_bar (-kappa / (2 sqrt(cv_t))) / (H+1)
+// with J_bar = 1 alone every weight is the double the unseeded sweep uses (absent terms are not added at all).
+__device__ inline void seeded_cost_weights(bool has_cm, double cmb, bool has_cv, double cvb, bool has_J, double jb, double kappa,
+                                           double cv, double inv_n, double& wm, double& wv) {
+    wm = has_J ? jb * inv_n : 0.0;
+    if (has_cm) wm = has_J ? cmb + wm : cmb;
+    wv = has_J ? jb * (-kappa / (2.0 * sqrt(cv)) * inv_n) : 0.0;
+    if (has_cv) wv = has_J ? cvb + wv : cvb;
+}
 
 __host__ __device__ inline int tri_index(int d, int e, int DP) { return d * DP - (d * (d - 1)) / 2 + (e - d); }   // d <= e
 
@@ -642,7 +669,7 @@ constexpr int kSweepPrefetch = (DP <= 4 && NT >= 256) ? (DP == 4 ? 2 : 1) : (DP 
 
 struct SweepLayout {
     int c_ils2, c_var, cost, gmu, gSig, gu, ctmp, mubar, Sigbar, Sacc, mbar, m, Sig, ms, mom, Ai, cc, M, y, V, Sb, Vb, Mb, cb, s0b,
-        s1b, Gs, Aib, Ab, mba, Ri, Z, rdet, RZ, Kq, mq, aug, pre, tmu, tSig, tact, tcv, total;
+        s1b, Gs, Aib, Ab, mba, Ri, Z, rdet, RZ, Kq, mq, aug, pre, tmu, tSig, tact, tcv, scm, scv, total;
 };
 
 __host__ __device__ inline int sweep_pre_words(int D) {        // per step: Ai, c, Ri, Z, rdet, y, V, M
@@ -650,7 +677,8 @@ __host__ __device__ inline int sweep_pre_words(int D) {        // per step: Ai, 
     return D * DD + D + 2 * P * DD + P + 2 * DD + D;
 }
 
-__host__ __device__ inline SweepLayout make_sweep_layout(int D, int A, int E, int H, int NSP, int nwaves, int naug, int pre_steps) {
+__host__ __device__ inline SweepLayout make_sweep_layout(int D, int A, int E, int H, int NSP, int nwaves, int naug, int pre_steps,
+                                                         int seed_steps = 0) {
     SweepLayout L;
     const int P = D * (D + 1) / 2, DD = D * D, n = D + A, NX = E - D;
     int o = 0;
@@ -668,6 +696,7 @@ __host__ __device__ inline SweepLayout make_sweep_layout(int D, int A, int E, in
     // the candidate's stored trajectory, actions and cost variances, staged once: the prologue's cost adjoints read them in
     // dependent inner loops (from global memory they were ~30 k of its ~60 k cycles at config 2)
     take(L.tmu, (H + 1) * D); take(L.tSig, (H + 1) * DD); take(L.tact, H * A); take(L.tcv, H + 1);
+    take(L.scm, seed_steps); take(L.scv, seed_steps);     // seeded sweep: the cost seeds of every step (0: unseeded)
     L.total = o;
     return L;
 }
@@ -741,8 +770,12 @@ __device__ inline void cost_adjoint_wave(int lane, int D, int A, bool terminal, 
 // kernel at config 2, 58 of 123 us at B = 1); the other wavefronts leave before the sweep.
 // DX = exact state dimension at compile time (0: runtime p.D <= DP): the index arithmetic of this latency-bound kernel
 // (divisions by D and D*D, pair decoding) then folds into constants.
-template <int DP, int NT, int DX>
-__global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
+// SEEDED (gpmpc_rollout_backward): the adjoints start from the caller's cotangents p.sd instead of the LCB's fixed weights
+// (seeded_cost_weights; trajectory seeds added to gmu / gSig after the cost part), and after t = 0 the adjoints of the initial
+// mean and covariance are written to p.sd.mu0_bar / S0_bar.  Every SEEDED branch is compile-time: the unseeded instantiations
+// (gpmpc_rollout_grad, gpmpc_objective_grad_host) compile to the same code as without them.
+template <int DP, int NT, int DX, bool SEEDED = false>
+__global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const std::conditional_t<SEEDED, SeededGradArgs, GradArgs> p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NW = NT / kWave;
     // threads of the reverse sweep proper.  D <= 4: four wavefronts when the launch has them -- the independent loops of a phase (e.g.
@@ -793,7 +826,7 @@ __global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
     const int NG = D + DD + NX;
     const int T2 = tri_count(D), NM = mean_moment_count(D, NX);
     const int LD = 2 * D;
-    const SweepLayout L = make_sweep_layout(D, A, E, H, NSP, NW, DP <= 4 ? 0 : kSweepAug, p.pre_steps);
+    const SweepLayout L = make_sweep_layout(D, A, E, H, NSP, NW, DP <= 4 ? 0 : kSweepAug, p.pre_steps, SEEDED ? H + 1 : 0);
     double* c_ils2 = smem + L.c_ils2; double* c_var = smem + L.c_var; double* c_cost = smem + L.cost;
     double* gmu = smem + L.gmu; double* gSig = smem + L.gSig; double* gu = smem + L.gu; double* ctmp = smem + L.ctmp;
     double* mubar = smem + L.mubar; double* Sigbar = smem + L.Sigbar; double* Sacc = smem + L.Sacc; double* mbar = smem + L.mbar;
@@ -816,19 +849,44 @@ __global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
     const double* traj_mu = p.mu + (size_t)c * (H + 1) * D;
     const double* traj_Sig = p.Sig + (size_t)c * (H + 1) * DD;
     const double* act = p.actions + (size_t)c * H * A;
-    const double* cvv = p.cv + (size_t)c * (H + 1);
     const double inv_n = 1.0 / (double)(H + 1);
     auto pair_of = [&](int q, int& a, int& b) { decode_tri(q, D, a, b); };
+    // seeded sweep: which seeds the caller gave (absent ones are neither read nor added); the costs and their variances are read
+    // only when a cost seed / the objective's seed needs them (the forward then computed them)
+    SweepSeeds sd{};
+    if constexpr (SEEDED) sd = p.sd;
+    [[maybe_unused]] const bool has_mu = SEEDED && sd.mu, has_Sg = SEEDED && sd.Sig, has_cm = SEEDED && sd.cm;
+    [[maybe_unused]] const bool has_cv = SEEDED && sd.cv, has_J = SEEDED && sd.J;
+    const bool cost_on = !SEEDED || has_cm || has_cv || has_J;
+    const bool cv_on = !SEEDED || has_J;
+    const double* costp = cost_on ? p.cost : p.ils2;                // (a dummy never stored when off)
+    const double* cvv = cv_on ? p.cv + (size_t)c * (H + 1) : p.ils2;
 
     double* s_tmu = smem + L.tmu; double* s_tSig = smem + L.tSig; double* s_tact = smem + L.tact; double* s_tcv = smem + L.tcv;
+    [[maybe_unused]] double* s_scm = smem + L.scm; [[maybe_unused]] double* s_scv = smem + L.scv;
+    [[maybe_unused]] double jb = 0.0, sv_mu = 0.0, sv_Sig = 0.0;
+    const int n_mu = (H + 1) * D, n_Sig = (H + 1) * DD;
+    [[maybe_unused]] const double* seed_mu = has_mu ? sd.mu + (size_t)c * n_mu : p.ils2;
+    [[maybe_unused]] const double* seed_Sig = has_Sg ? sd.Sig + (size_t)c * n_Sig : p.ils2;
     {
         // constants and the stored trajectory: the first element of every array per thread with all loads in flight together (one
         // copy loop after the other is one global round trip after the other: seven of them, ~5 k cycles, round 6)
-        const int nc = n + n * n + DD + 2 * D, n_mu = (H + 1) * D, n_Sig = (H + 1) * DD, n_act = H * A, n_cv = H + 1;
+        const int nc = cost_on ? n + n * n + DD + 2 * D : 0, n_act = H * A, n_cv = cv_on ? H + 1 : 0;
         __builtin_amdgcn_sched_barrier(0);
-        const double v0 = p.ils2[tid < D * E ? tid : 0], v1 = p.var[tid < D ? tid : 0], v2 = p.cost[tid < nc ? tid : 0];
+        const double v0 = p.ils2[tid < D * E ? tid : 0], v1 = p.var[tid < D ? tid : 0], v2 = costp[tid < nc ? tid : 0];
         const double v3 = traj_mu[tid < n_mu ? tid : 0], v4 = traj_Sig[tid < n_Sig ? tid : 0];
         const double v5 = act[tid < n_act ? tid : 0], v6 = cvv[tid < n_cv ? tid : 0];
+        [[maybe_unused]] double v7 = 0.0, v8 = 0.0;
+        if constexpr (SEEDED) {          // the seeds' first elements in the same flight
+            const double* scm = has_cm ? sd.cm + (size_t)c * (H + 1) : p.ils2;
+            const double* scv = has_cv ? sd.cv + (size_t)c * (H + 1) : p.ils2;
+            const int n_scm = has_cm ? H + 1 : 0, n_scv = has_cv ? H + 1 : 0;
+            v7 = scm[tid < n_scm ? tid : 0];
+            v8 = scv[tid < n_scv ? tid : 0];
+            sv_mu = seed_mu[tid < (has_mu ? n_mu : 0) ? tid : 0];
+            sv_Sig = seed_Sig[tid < (has_Sg ? n_Sig : 0) ? tid : 0];
+            jb = has_J ? sd.J[c] : 0.0;
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (tid < D * E) c_ils2[tid] = v0;
         if (tid < D) c_var[tid] = v1;
@@ -837,8 +895,15 @@ __global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
         if (tid < n_Sig) s_tSig[tid] = v4;
         if (tid < n_act) s_tact[tid] = v5;
         if (tid < n_cv) s_tcv[tid] = v6;
+        if constexpr (SEEDED) {
+            if (tid < H + 1) { s_scm[tid] = v7; s_scv[tid] = v8; }
+            for (int i = tid + NT; i < H + 1; i += NT) {
+                s_scm[i] = has_cm ? sd.cm[(size_t)c * (H + 1) + i] : 0.0;
+                s_scv[i] = has_cv ? sd.cv[(size_t)c * (H + 1) + i] : 0.0;
+            }
+        }
         for (int i = tid + NT; i < D * E; i += NT) c_ils2[i] = p.ils2[i];
-        for (int i = tid + NT; i < nc; i += NT) c_cost[i] = p.cost[i];
+        for (int i = tid + NT; i < nc; i += NT) c_cost[i] = costp[i];
         for (int i = tid + NT; i < n_mu; i += NT) s_tmu[i] = traj_mu[i];
         for (int i = tid + NT; i < n_Sig; i += NT) s_tSig[i] = traj_Sig[i];
         for (int i = tid + NT; i < n_act; i += NT) s_tact[i] = act[i];
@@ -847,13 +912,30 @@ __global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
     sync_all();
     GPMPC_STRACE(10);
     // cost adjoints of every time step (independent of the sweep): one wavefront per step
-    for (int t = wave; t <= H; t += NW) {
+    for (int t = wave; t <= H && cost_on; t += NW) {
         const bool terminal = (t == H);
-        const double wv = -p.kappa / (2.0 * sqrt(s_tcv[t])) * inv_n;
+        double wm = inv_n, wv;
+        if constexpr (SEEDED) seeded_cost_weights(has_cm, s_scm[t], has_cv, s_scv[t], has_J, jb, p.kappa, s_tcv[t], inv_n, wm, wv);
+        else wv = -p.kappa / (2.0 * sqrt(s_tcv[t])) * inv_n;
         cost_adjoint_wave(lane, D, A, terminal, s_tmu + t * D, s_tSig + t * DD, s_tact + (terminal ? 0 : t) * A, target,
-                          terminal ? WT : Wst, smin, smax, p.use_constraints != 0, inv_n, wv, ctmp + wave * (2 * n * n + 3 * n),
+                          terminal ? WT : Wst, smin, smax, p.use_constraints != 0, wm, wv, ctmp + wave * (2 * n * n + 3 * n),
                           gmu + t * D, gSig + t * DD, terminal ? ctmp + wave * (2 * n * n + 3 * n) : gu + t * A);
         wave_lds_sync();
+    }
+    if constexpr (SEEDED) {
+        // trajectory seeds after the cost part (no cost seed: the cost part is 0); Sig_bar is symmetrised where gSig is used
+        sync_all();
+        for (int i = tid; i < n_mu; i += NT) {
+            double v = cost_on ? gmu[i] : 0.0;
+            if (has_mu) v += (i == tid) ? sv_mu : seed_mu[i];
+            gmu[i] = v;
+        }
+        for (int i = tid; i < n_Sig; i += NT) {
+            double v = cost_on ? gSig[i] : 0.0;
+            if (has_Sg) v += (i == tid) ? sv_Sig : seed_Sig[i];
+            gSig[i] = v;
+        }
+        if (!cost_on) for (int i = tid; i < H * A; i += NT) gu[i] = 0.0;
     }
     sync_all();
     GPMPC_STRACE(11);
@@ -1225,6 +1307,11 @@ __global__ __launch_bounds__(NT) void adjoint_sweep_kernel(const GradArgs p) {
         for (int i = tid - W2; i < A; i += NL) if (i >= 0) p.grad[((size_t)c * H + t) * A + i] = mbar[D + i] + gu[t * A + i];
         sync();
         GPMPC_STRACE(9);
+    }
+    if constexpr (SEEDED) {
+        // adjoints of the initial state (Sigbar is symmetric bit for bit: both halves are formed from the same sums)
+        if (sd.mu0_bar) for (int i = tid; i < D; i += NL) sd.mu0_bar[(size_t)c * D + i] = mubar[i];
+        if (sd.S0_bar) for (int i = tid; i < DD; i += NL) sd.S0_bar[(size_t)c * DD + i] = Sigbar[i];
     }
     if (p.host_n > 0 && c == 0) {
         // results to the host's pinned mirror (the gradient just stored by other lanes of this workgroup: loads that bypass the L1),

@@ -6,7 +6,7 @@
 namespace gpmpc_hip {
 
 // State dimensions beyond 8 (config 5): the matrix-core moment pass + the pair-walking reverse sweep of grad_wide_kernel.h.
-int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s) {
+int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s, const RolloutSeeds* seeds) {
     const int N = a.N, D = a.D, A = a.A, E = a.E, H = a.H, B = a.B;
     const int NX = E - D, P = D * (D + 1) / 2;
     if (D > 16 || NX > 16) { h->err = "gradient: supported for D <= 16"; return GPMPC_ERR_LIMIT; }
@@ -19,7 +19,7 @@ int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStr
     const size_t n_mom = (size_t)B * H * P * NSP, n_cv = (size_t)B * (H + 1);
     int rc = grow(h, h->gradws, n_mom + n_cv);
     if (rc) return rc;
-    if (!a.cv_out) a.cv_out = h->gradws.p + n_mom;
+    if (!a.cv_out && (!seeds || seeds->cost)) a.cv_out = h->gradws.p + n_mom;
     rc = launch_rollout(h, a, s);            // forward: trajectory, costs, J
     if (rc) return rc;
     WideArgs w;
@@ -36,14 +36,18 @@ int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStr
         hipLaunchKernelGGL(kern, dim3(P, H, B), dim3(kWideThreads), (size_t)ML.total * 8, s, w);
         GPMPC_HIP_CHECK(h, hipGetLastError());
     }
-    {
-        auto kern = wide_adjoint_sweep_kernel<16>;
-        rc = allow_full_lds(h, reinterpret_cast<const void*>(kern));
-        if (rc) return rc;
-        hipLaunchKernelGGL(kern, dim3(B), dim3(kWideSweepThreads), (size_t)SL.total * 8, s, w);
+    auto sweep = [&](auto kern, const auto& args) -> int {
+        int r = allow_full_lds(h, reinterpret_cast<const void*>(kern));
+        if (r) return r;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(kWideSweepThreads), (size_t)SL.total * 8, s, args);
         GPMPC_HIP_CHECK(h, hipGetLastError());
-    }
-    return GPMPC_OK;
+        return GPMPC_OK;
+    };
+    if (!seeds) return sweep(wide_adjoint_sweep_kernel<16>, w);
+    SeededWideArgs sw;
+    static_cast<WideArgs&>(sw) = w;
+    sw.sd = SweepSeeds{seeds->mu, seeds->Sig, seeds->cm, seeds->cv, seeds->J, seeds->mu0_bar, seeds->S0_bar};
+    return sweep(wide_adjoint_sweep_kernel<16, true>, sw);
 }
 
 }  // namespace gpmpc_hip

@@ -57,6 +57,7 @@ struct WideArgs {
     const double* xrange;   // (2, E) per-dimension min | max of the memory points
     int force_path;         // 1: direct exp everywhere (tests)
 };
+struct SeededWideArgs : WideArgs { SweepSeeds sd; };      // the seeded sweep's arguments (grad_kernels.h)
 
 __host__ __device__ inline int wide_nsp(int D, int NX) { return rnd2(1 + D + D * D + NX); }
 
@@ -710,8 +711,33 @@ __host__ __device__ inline WideSweepLayout make_wide_sweep_layout(int D, int A, 
     return L;
 }
 
-template <int DP>
-__global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(const WideArgs p) {
+// Seeded sweep, wave 0: the stage-cost partials of step t with the seeds' weights (seeded_cost_weights), then the trajectory
+// seeds; without a cost seed the cost part is 0 (the cost settings are not read)
+__device__ inline void wide_seeded_stage(int lane, const WideArgs& p, const SweepSeeds& sd, int c, int t, bool terminal,
+                                         const double* act, const double* c_cost, double inv_n, const double* s_mu,
+                                         const double* s_Sig, double* s_ctmp, double* s_gmu, double* s_gSig, double* s_gu) {
+    const int D = p.D, A = p.A, H = p.H, DD = D * D, n = D + A;
+    const bool cost_on = sd.cm || sd.cv || sd.J;
+    const size_t ct = (size_t)c * (H + 1) + t;
+    if (cost_on) {
+        const double* target = c_cost; const double* Wm = c_cost + n; const double* WT = Wm + n * n;
+        const double* smin = WT + DD; const double* smax = smin + D;
+        double wm, wv;
+        seeded_cost_weights(sd.cm, sd.cm ? sd.cm[ct] : 0.0, sd.cv, sd.cv ? sd.cv[ct] : 0.0, sd.J, sd.J ? sd.J[c] : 0.0, p.kappa,
+                            sd.J ? p.cv[ct] : 1.0, inv_n, wm, wv);
+        cost_adjoint_wave(lane, D, terminal ? 0 : A, terminal, s_mu, s_Sig, terminal ? s_mu : act, target, terminal ? WT : Wm, smin,
+                          smax, !terminal && p.use_constraints != 0, wm, wv, s_ctmp, s_gmu, s_gSig, s_gu);
+    }
+    wave_lds_sync();
+    for (int i = lane; i < D; i += 64) s_gmu[i] = (cost_on ? s_gmu[i] : 0.0) + (sd.mu ? sd.mu[ct * D + i] : 0.0);
+    for (int i = lane; i < DD; i += 64) s_gSig[i] = (cost_on ? s_gSig[i] : 0.0) + (sd.Sig ? sd.Sig[ct * DD + i] : 0.0);
+    if (!cost_on) for (int k = lane; k < A; k += 64) s_gu[k] = 0.0;
+}
+
+// SEEDED: the caller's cotangents instead of the LCB's weights, the initial state's adjoints written after t = 0 (as
+// adjoint_sweep_kernel<..., SEEDED>; compile-time, the unseeded instantiation is the one gpmpc_rollout_grad always ran)
+template <int DP, bool SEEDED = false>
+__global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(const std::conditional_t<SEEDED, SeededWideArgs, WideArgs> p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NT = kWideSweepThreads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -730,9 +756,12 @@ __global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(c
     double* s_G1 = s_small + 4 * D; double* s_AiG1 = s_small + 5 * D; double* s_sc = s_small + 8 * D;   // scalars: c, s0, cb, s0b
     const int CW = D + NX + 2;                                    // words per point of the chunk
 
+    SweepSeeds sd{};
+    if constexpr (SEEDED) sd = p.sd;
+    const bool cost_on = !SEEDED || sd.cm || sd.cv || sd.J;
     for (int i = tid; i < D * E; i += NT) c_ils2[i] = p.ils2[i];
     for (int i = tid; i < D; i += NT) c_var[i] = p.var[i];
-    for (int i = tid; i < n + n * n + DD + 2 * D; i += NT) c_cost[i] = p.cost[i];
+    if (cost_on) for (int i = tid; i < n + n * n + DD + 2 * D; i += NT) c_cost[i] = p.cost[i];
     __syncthreads();
     const double* target = c_cost; const double* Wm = c_cost + n; const double* WT = Wm + n * n;
     const double* smin = WT + DD; const double* smax = smin + D;
@@ -745,9 +774,12 @@ __global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(c
         for (int i = lane; i < D; i += 64) s_mu[i] = muH[i];
         for (int i = lane; i < DD; i += 64) s_Sig[i] = SgH[i];
         wave_lds_sync();
-        const double cvH = p.cv[(size_t)c * (H + 1) + H];
-        cost_adjoint_wave(lane, D, 0, true, s_mu, s_Sig, s_mu, target, WT, smin, smax, false, inv_n,
-                          -p.kappa / (2.0 * sqrt(cvH)) * inv_n, s_ctmp, s_gmu, s_gSig, s_gu);
+        if constexpr (SEEDED) wide_seeded_stage(lane, p, sd, c, H, true, s_mu, c_cost, inv_n, s_mu, s_Sig, s_ctmp, s_gmu, s_gSig, s_gu);
+        else {
+            const double cvH = p.cv[(size_t)c * (H + 1) + H];
+            cost_adjoint_wave(lane, D, 0, true, s_mu, s_Sig, s_mu, target, WT, smin, smax, false, inv_n,
+                              -p.kappa / (2.0 * sqrt(cvH)) * inv_n, s_ctmp, s_gmu, s_gSig, s_gu);
+        }
         wave_lds_sync();
         for (int i = lane; i < D; i += 64) s_mubar[i] = s_gmu[i];
         for (int i = lane; i < DD; i += 64) { const int r = i / D, cc = i - r * D; s_Sbar[i] = 0.5 * (s_gSig[i] + s_gSig[cc * D + r]); }
@@ -996,10 +1028,15 @@ __global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(c
         __syncthreads();
         // ---- stage cost of step t, hand-over to step t - 1 -------------------------------------------------------------
         if (wave == 0) {
-            const double cvt = p.cv[(size_t)c * (H + 1) + t];
-            const double* act = p.actions + ((size_t)c * H + t) * A;
-            cost_adjoint_wave(lane, D, A, false, s_mu, s_Sig, act, target, Wm, smin, smax, p.use_constraints != 0, inv_n,
-                              -p.kappa / (2.0 * sqrt(cvt)) * inv_n, s_ctmp, s_gmu, s_gSig, s_gu);
+            if constexpr (SEEDED)
+                wide_seeded_stage(lane, p, sd, c, t, false, p.actions + ((size_t)c * H + t) * A, c_cost, inv_n, s_mu, s_Sig, s_ctmp,
+                                  s_gmu, s_gSig, s_gu);
+            else {
+                const double cvt = p.cv[(size_t)c * (H + 1) + t];
+                const double* act = p.actions + ((size_t)c * H + t) * A;
+                cost_adjoint_wave(lane, D, A, false, s_mu, s_Sig, act, target, Wm, smin, smax, p.use_constraints != 0, inv_n,
+                                  -p.kappa / (2.0 * sqrt(cvt)) * inv_n, s_ctmp, s_gmu, s_gSig, s_gu);
+            }
             wave_lds_sync();
             for (int k = lane; k < A; k += 64) p.grad[((size_t)c * H + t) * A + k] = s_mbar[D + k] + s_gu[k];
             for (int i = lane; i < D; i += 64) s_mubar[i] = s_mbar[i] + s_gmu[i];
@@ -1013,6 +1050,11 @@ __global__ __launch_bounds__(kWideSweepThreads) void wide_adjoint_sweep_kernel(c
         __syncthreads();
         for (int i = tid; i < DD; i += NT) s_Sbar[i] = s_Vb[i];
         __syncthreads();
+    }
+    if constexpr (SEEDED) {
+        // adjoints of the initial state (s_Sbar is symmetric bit for bit: both halves are formed from the same sums)
+        if (sd.mu0_bar) for (int i = tid; i < D; i += NT) sd.mu0_bar[(size_t)c * D + i] = s_mubar[i];
+        if (sd.S0_bar) for (int i = tid; i < DD; i += NT) sd.S0_bar[(size_t)c * DD + i] = s_Sbar[i];
     }
 }
 

@@ -307,6 +307,36 @@ class HipEngine:
                                                 out["cost_var"].data_ptr() if trajectories else None, self._stream()))
         return out
 
+    def rollout_backward(self, actions, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None, cost_mu_bar=None,
+                         cost_var_bar=None, J_bar=None, want_initial=True):
+        """Reverse-mode product of `rollout` (autograd through predict_trajectory + get_rewards_trajectory, gp_model.py:60-110,
+        setpoint_distance_reward_mapper.py:144-149): actions (B,H,A), the shared initial state mu0 (D,), S0 (D,D) and the upstream
+        gradients mu_bar (B,H+1,D), Sig_bar (B,H+1,D,D), cost_mu_bar / cost_var_bar (B,H+1), J_bar (B,), each None for zero ->
+        dict of device tensors actions_bar (B,H,A) and, with `want_initial`, mu0_bar (B,D) and S0_bar (B,D,D) per candidate
+        (S0_bar the symmetric part).  The forward is recomputed inside the call (gpmpc_rollout_backward).  Cost / J seeds need
+        set_cost; shapes outside the gradient kernels raise GpmpcError(GPMPC_ERR_LIMIT).  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
+        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
+        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
+        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
+        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
+        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
+        if want_initial:
+            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
+            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_rollout_backward(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
+                                                    float(time0), ptr(mb), ptr(Sb), ptr(cmb), ptr(cvb), ptr(Jb),
+                                                    out["actions_bar"].data_ptr(), ptr(out.get("mu0_bar")),
+                                                    ptr(out.get("S0_bar")), self._stream()))
+        self._keep_rollout_backward = (actions, mb, Sb, cmb, cvb, Jb)   # alive until the asynchronous call has read them
+        return out
+
     def objective_grad_host(self, actions, mu0, S0, include_time=False, time0=0.0):
         """ONE action sequence (H, A) on the host -> objective, gradient, trajectory and stage costs on the host
         (gpmpc_objective_grad_host: the sequence travels as a kernel argument, the results through a pinned host buffer,

@@ -178,6 +178,38 @@ int gpmpc_rollout_grad(gpmpc_t* h, const double* actions_dev, const double* mu0_
 int gpmpc_last_grad_path(gpmpc_t* h);
 
 /*
+ * gpmpc_rollout_backward  <->  torch autograd through predict_trajectory (gp_model.py:60-110) and get_rewards_trajectory
+ * (setpoint_distance_reward_mapper.py:144-149) -- what compute_mean_lcb_trajectory (gp_mpc_controller.py:229-285) differentiates
+ * with its LCB, for any upstream cost: the reverse-mode product (vector-Jacobian product) of gpmpc_rollout for B candidates.
+ * It returns the gradients of
+ *     sum_t <mu_bar_t, mu_t> + <Sig_bar_t, Sig_t> + cost_mu_bar_t cost_mu_t + cost_var_bar_t cost_var_t  +  J_bar J
+ * (mu_t, Sig_t, cost_mu_t, cost_var_t, J: what gpmpc_rollout writes for the same inputs and the same loaded cost) with respect to
+ * each candidate's actions and to the initial mean and covariance, per candidate (a shared initial state's gradient is the sum
+ * over B).  Inputs as gpmpc_rollout; cotangents (each NULL = 0):
+ *   mu_bar_dev (B,H+1,D)  Sig_bar_dev (B,H+1,D,D)  cost_mu_bar_dev (B,H+1)  cost_var_bar_dev (B,H+1)  J_bar_dev (B)
+ * Outputs, overwritten (not accumulated into):
+ *   actions_bar_out_dev (B,H,A)  required
+ *   mu0_bar_out_dev (B,D)        or NULL (not written)
+ *   S0_bar_out_dev (B,D,D)       or NULL (not written): the symmetric part sym(G) = (G + G^T) / 2 of the covariance gradient, by
+ *                                the rule of gpmpc_moments_backward; Sig_bar is symmetrised on entry (exact: every Sig_t is a
+ *                                symmetric function of its inputs)
+ * clip_to_zero is pass-through for J (as gpmpc_rollout_grad); the time input is not differentiated.  The cost cotangents weigh the
+ * stage-cost partials as the LCB does: wm_t = cost_mu_bar_t + J_bar / (H+1), wv_t = cost_var_bar_t + J_bar (-kappa /
+ * (2 sqrt(cost_var_t))) / (H+1); with J_bar = 1 alone actions_bar_out is bit for bit gpmpc_rollout_grad's grad_out.
+ * The call runs gpmpc_rollout_grad's launch sequence for that B (forward rollout, the same moment passes and dispatch rules)
+ * and then the reverse sweep in a seeded form: the forward is RECOMPUTED inside the call, so nothing is kept between an autograd
+ * forward and its backward (the entry is stateless).  Coverage as gpmpc_rollout_grad: D <= 8 with A (+ time) <= 6, and
+ * 8 < D <= 16; otherwise GPMPC_ERR_LIMIT.  GPMPC_ERR_ARG: actions_bar_out_dev NULL, A < 1, or a cost / J cotangent without
+ * gpmpc_set_cost for this (D, A) (the trajectory's cotangents alone need no cost settings).  gpmpc_last_grad_path reports the
+ * moment passes that ran.  Shares gpmpc_rollout_grad's workspace: stream-ordered, not concurrent with gpmpc_rollout /
+ * gpmpc_rollout_grad / gpmpc_objective_grad_host on one handle.  Asynchronous on `stream`.
+ */
+int gpmpc_rollout_backward(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B, int H, int A,
+                           int include_time, double time0, const double* mu_bar_dev, const double* Sig_bar_dev,
+                           const double* cost_mu_bar_dev, const double* cost_var_bar_dev, const double* J_bar_dev,
+                           double* actions_bar_out_dev, double* mu0_bar_out_dev, double* S0_bar_out_dev, void* stream);
+
+/*
  * gpmpc_objective_grad_host  <->  ONE call of compute_mean_lcb_trajectory (gp_mpc_controller.py:229-285) as scipy's L-BFGS-B
  * makes it (:133-141: one action sequence per evaluation, host arrays in, (float, host gradient) out): gpmpc_rollout_grad for
  * B = 1 with host buffers on both sides; returns when the results are in *result_host (the last kernel raises a completion word

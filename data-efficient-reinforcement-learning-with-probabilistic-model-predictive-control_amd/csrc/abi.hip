@@ -131,9 +131,7 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
     else if (!strcmp(name, "grad_separable")) h->opt_grad_sep = (int)value;
     else if (!strcmp(name, "grad_tiles")) h->opt_grad_tiles = (int)value;
-    else if (!strcmp(name, "grad_fuse")) h->opt_grad_fuse = (int)value;
     else if (!strcmp(name, "grad_mean")) h->opt_grad_mean = (int)value;
-    else if (!strcmp(name, "grad_merge")) h->opt_grad_merge = (int)value;
     else if (!strcmp(name, "prepare_overlap")) h->opt_prepare_overlap = (int)value;
     else if (!strcmp(name, "prepare_fuse")) h->opt_prepare_fuse = (int)value;
     else if (!strcmp(name, "prepare_invcols")) h->opt_prepare_invcols = (int)value;
@@ -148,8 +146,6 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "outer2")) h->opt_outer2 = (int)value;
     else if (!strcmp(name, "refresh_every")) h->opt_refresh_every = (int)value;
     else if (!strcmp(name, "pair_tiles")) h->opt_pair_tiles = (int)value;
-    else if (!strcmp(name, "tile_chunk")) h->opt_tile_chunk = (int)value;
-    else if (!strcmp(name, "tile_overlap")) h->opt_tile_overlap = (int)value;
     else if (!strcmp(name, "cluster_debug")) h->opt_cl_dbg = (int)value;
     else if (!strcmp(name, "cluster")) {
         if (value < 0 || value > 32) { h->err = "cluster: 0 (auto), 1 (never) or 2..32 workgroups per candidate"; return GPMPC_ERR_ARG; }
@@ -379,11 +375,6 @@ __global__ __launch_bounds__(64) void upload_kernel(double* dst, int n, const Up
 int gpmpc_objective_grad_host(gpmpc_t* g, const double* actions_host, const double* mu0, const double* S0, int H, int A,
                               int include_time, double time0, const double** result_host, void* stream) {
     Range roctx_range("gpmpc_objective_grad_host");
-#if defined(GPMPC_HOST_TIMING)
-    static double acc[4] = {0, 0, 0, 0}; static int calls = 0;
-    auto now = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; };
-    const double T0 = now();
-#endif
     if (!g) return GPMPC_ERR_ARG;
     if (!actions_host || !result_host) return bad(g, "null argument");
     Handle* h = H_(g);
@@ -438,10 +429,6 @@ int gpmpc_objective_grad_host(gpmpc_t* g, const double* actions_host, const doub
     const unsigned long long seq = ++h->hio_seq;
     const bool sweep_exports = D <= 8;               // (the wide-state sweep, 8 < D <= 16, has no export: a synchronisation and a copy)
     h->hx_out = h->hio_host_dev; h->hx_src = out_dev; h->hx_n = sweep_exports ? (int)n_out : 0;
-#if defined(GPMPC_HOST_TIMING)
-    const double T1 = now();
-    g_host_timing_fwd = 0.0;
-#endif
     rc = launch_rollout_grad(h, a, grad, s);
     h->hx_n = 0;
     if (rc) return rc;
@@ -451,9 +438,6 @@ int gpmpc_objective_grad_host(gpmpc_t* g, const double* actions_host, const doub
         *result_host = h->hio_host;
         return GPMPC_OK;
     }
-#if defined(GPMPC_HOST_TIMING)
-    const double T2 = now();
-#endif
     volatile unsigned long long* flag = h->hio_flag;
     for (unsigned spins = 1; *flag != seq; ++spins) {
         __builtin_ia32_pause();
@@ -468,14 +452,6 @@ int gpmpc_objective_grad_host(gpmpc_t* g, const double* actions_host, const doub
         }
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-#if defined(GPMPC_HOST_TIMING)
-    const double T3 = now();
-    acc[0] += T1 - T0; acc[1] += g_host_timing_fwd - T1; acc[2] += T2 - g_host_timing_fwd; acc[3] += T3 - T2;
-    if (++calls % 200 == 0) {
-        fprintf(stderr, "HOST TIMING us: set-up %.2f | plan + forward launch %.2f | remaining launches %.2f | wait %.2f\n", acc[0] / 200, acc[1] / 200, acc[2] / 200, acc[3] / 200);
-        acc[0] = acc[1] = acc[2] = acc[3] = 0;
-    }
-#endif
     *result_host = h->hio_host;
     return GPMPC_OK;
 }

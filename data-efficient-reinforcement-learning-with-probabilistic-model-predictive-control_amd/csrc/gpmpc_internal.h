@@ -97,9 +97,6 @@ struct ClusterMap {
 
 // ---------------------------------------------------------------------------------------
 // Kernel argument block of the rollout kernel (passed by value, < 4 KiB).
-#if defined(GPMPC_HOST_TIMING)
-inline double g_host_timing_fwd = 0.0;        // (timing experiment builds: when the forward launch of a gradient call was submitted)
-#endif
 constexpr int kInlineActs = 64;
 struct RolloutArgs {
     // cached model (device)
@@ -136,7 +133,6 @@ struct RolloutArgs {
     int force_path;          // 0 auto, 1 always direct exp, 2 Taylor but never separable (tests)
     int force_sep;           // 1: separable whenever the degree allows, ignoring the cost model (tests)
     int x_in_lds;            // 1: X^T is copied to LDS once per launch (the per-point pass reads it every step)
-    int exact_dim;           // 2: never use the compile-time-D instantiation (A/B); otherwise whenever D == DP
     int cols2;               // 1: two adjacent columns per lane in the pairwise pass (halves the LDS broadcast traffic)
     // tiling
     int G;        // output pairs per group
@@ -166,7 +162,6 @@ struct RolloutArgs {
     unsigned xch_tag0;           // tags of this launch: xch_tag0 + step + 1 (unique over the life of the buffer)
     unsigned long long* xch;
     unsigned long long* xch_uc;  // the same layout in uncached device memory (members on several XCDs; the placement prologue)
-    int defer_cost;              // 1: launch_rollout leaves the stage costs / objective to its caller (the few-candidate gradient launch folds them into its moment launch)
     int cl_dbg;                  // timing experiments of the exchange (-DGPMPC_CL_DEBUG builds only)
     // one sequence from the host (gpmpc_objective_grad_host): the actions ride in this block instead of an upload launch; the
     // fused-horizon kernel takes them from here and leaves a copy at `act_store` (= actions) for the gradient's kernels
@@ -216,7 +211,7 @@ struct Handle {
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
-    hipStream_t side_stream = nullptr;   // batch-major path: the point pass of a step runs beside the tile kernel
+    hipStream_t side_stream = nullptr;   // prepare: the inverse's launches beside the factorisation's
     hipEvent_t ev_params = nullptr, ev_points = nullptr;
     // incremental factorisation: what the cached factors were computed from, and border-update scratch
     Buf Xc, Yc;   // (N, E), (N, D) copies of the memory points of the last prepare
@@ -283,15 +278,8 @@ struct Handle {
     int opt_tile128 = 1;             // large N: 128 x 128 tiles (8 wavefronts) for the tiled products; 0: 64 x 64 (A/B)
     int opt_outer_block = 1;         // large N: outer panels of 128 columns + LDS-tiled products; 0: the 32-wide path only (A/B, tests)
     int opt_pair_tiles = 0;          // batch-major pairwise pass of the diagonal pairs: 0 auto (by N, D, B), 1 always (D <= 4), 2 never
-    int opt_tile_chunk = 0;          // candidates per workgroup of the batch-major pass (0: chosen from the batch)
-    int opt_tile_overlap = 0;        // batch-major path: 1 = point pass on a side stream, concurrent with the tile kernel.  Measured at config 4
-                                     // (round 3): 77.9 ms either way -- the two kernels do overlap (rocprofv3: 2.58 ms and 1.41 ms side by side instead
-                                     // of 2.14 + 0.49 ms) but the fp64 pipe is already at the ~76 % of its nominal rate an FMA loop reaches
     int last_rollout_path = 0;       // what the last rollout launch used: 0 fused-horizon kernel, 1 streaming kernel, 2 batch-major tiles
-    int last_fused_tiles = 0;        // 1: the last batch-major forward also formed the gradient's tile moments (RolloutArgs::grad_mom)
-    int opt_grad_merge = 1;          // few candidates: element-wise moments + mean moments + stage costs in ONE launch (0: three launches, A/B)
     int opt_grad_mean = 1;           // moment pass (D <= 4): the mean part by mean_moments_kernel (lanes over points); 0: inside the pass (A/B, tests)
-    int opt_grad_fuse = 1;           // gradient: form the diagonal pairs' tile moments inside the batch-major forward (0: separate pass, A/B)
     int last_grad_path = 0;          // moment passes of the last gpmpc_rollout_grad: bit 0 separable off-diagonal pairs, bit 1 tile moments of
                                      // the diagonal pairs, bit 2 streaming element-wise pass, bit 3 the wide (8 < D <= 16) pass
     int opt_prepare_inv_batch = 4;   // 32-wide panel path: row blocks of L^-1 per side-stream launch (1: one launch per row block)
@@ -327,17 +315,75 @@ inline int allow_full_lds(Handle* h, const void* kernel) {
     return GPMPC_OK;
 }
 
+// exact division by multiply-high: for d >= 2, umulhi(x, ceil(2^32 / d)) == x / d whenever x * d < 2^32 (0 encodes d == 1: no division)
+inline unsigned magic_div(unsigned d) { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + d - 1) / d); }
+
+// The upper triangles of the D tables T_a no longer stay in an XCD's 4 MiB L2 from this size on: the batch-major passes of the
+// diagonal pairs (pair_tile_kernel.h, pair_tile_grad_kernel.h) amortise a tile over many candidates instead.
+constexpr double kTileTableBytes = 6.0e6;
+inline bool tables_outgrow_l2(int N, int D) { return 4.0 * D * (double)N * N >= kTileTableBytes; }
+
+// ---------------------------------------------------------------------------------------
+// Kernel form of a rollout launch (rollout.hip: plan_rollout).  Planned from the shape, the PLANNED batch Bp, the handle's options
+// and device limits alone -- never from the launched batch: a slice of a population takes the population's form (same chunk
+// lengths, same summation order) while the grid still covers the candidates launched.
+struct RolloutRequest {        // what a gradient launch asks of its forward
+    bool fused_tiles;          // the batch-major tile pass also forms the diagonal pairs' moments (RolloutArgs::grad_mom)
+    bool costs_to_caller;      // the stage costs / objective are left to the caller (the few-candidate moment launch)
+};
+struct RolloutPlan {
+    int DP;                    // padded state dimension of the instantiation
+    int nt;                    // threads per workgroup
+    int path;                  // 0 fused-horizon kernel, 1 streaming kernel, 2 batch-major tiles (Handle::last_rollout_path)
+    int cols2, G, CH, RC, x_in_lds;          // the RolloutArgs fields of the same names
+    size_t lds_bytes;
+    int cluster, cl_slots, xch_n;            // cooperative form (cluster 1: the plain kernel)
+    ClusterMap cmap;
+    unsigned magic_N, magic_wpp, magic_pt;
+    int CM, sep_kmax;
+    bool fused_tiles;          // the request, where the form honours it (batch-major only)
+    bool costs_to_caller;
+    const char* err;           // why the shape is over a limit (GPMPC_ERR_LIMIT)
+};
+
+// Kernel forms of a gradient launch with D <= 8 (grad.hip: plan_rollout_grad), the forward's included.
+struct MomTiling {             // moment pass: pairs per group, rows per chunk, row chunks, work-item slots per pair, pair groups, LDS
+    int G, CH, RC, wpp, gz;
+    size_t lds;
+};
+struct GradPlan {
+    int DP, NXP, RS, NSP;
+    int sweep_nt, pre_steps;   // reverse sweep: threads, steps whose state-independent algebra runs up front
+    size_t sweep_lds;
+    bool stream;               // streaming element-wise pass (per-point arrays beyond the LDS), else LDS-resident
+    size_t gs_lds;
+    MomTiling first;           // what the launches before the element-wise pass see (64-row chunks, all pairs)
+    MomTiling pass;            // the element-wise pass: re-planned for the pairs left and the schedule model's chunk (LDS-resident)
+    bool share_cu;             // two 512-thread workgroups per CU
+    bool tiles, fused;         // diagonal pairs batch-major; formed by the forward's tile pass
+    bool sep;                  // off-diagonal pairs in separable form on the matrix cores, with:
+    int sep_kmax, sep_NA, sep_NE, sep_PS, sep_wave_words;
+    size_t sep_lds;
+    int pairs_left;            // pairs the element-wise pass works on
+    bool few, merged;          // few candidates; element-wise + mean moments + stage costs in one launch
+    int path;                  // Handle::last_grad_path
+    RolloutPlan fwd;
+};
+
 // rollout.hip
+int ensure_rollout_tables(Handle* h, int N, int D);      // what the plan reads: monomial tables, the batch-major path's bands
+int plan_rollout(const Handle& h, int N, int D, int A, int E, int H, int Bp, const RolloutRequest& req, RolloutPlan& p);
+int launch_rollout(Handle* h, RolloutArgs& a, const RolloutPlan& p, hipStream_t s);
 int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s);
 int launch_argmin(Handle* h, const double* J, int B, long long first, hipStream_t s);
 int launch_traj_cost(Handle* h, const RolloutArgs& a, double* cm, double* cv, double* J, hipStream_t s);     // stage costs + objective of the stored trajectory
 // pair_tile.hip: the batch-major pass of horizon step t (a.mu_out / a.Sig_out hold the state), a.tile_part / a.ntiles set on return
-bool tile_path_supported(Handle* h, const RolloutArgs& a);
+int ensure_sep_table(Handle* h, int D);
+bool tile_path_fits(const Handle& h, int N, int D, int E);          // (reads the table of ensure_sep_table)
 int tile_workspace(Handle* h, RolloutArgs& a);
 int launch_tile_state_init(Handle* h, const RolloutArgs& a, hipStream_t s);
 int launch_pair_tiles(Handle* h, const RolloutArgs& a, int t, hipStream_t s);
-bool tile_moments_fusable(Handle* h, const RolloutArgs& a);
-bool tile_moments_supported(Handle* h, const RolloutArgs& a, int NSP);
+bool tile_moments_supported(const Handle& h, int D, int E, int NSP);
 int launch_tile_moments(Handle* h, const RolloutArgs& a, double* mom, int* done, int NSP, int NXP, hipStream_t s);
 // grad.hip
 // Cotangents of gpmpc_rollout_backward (each NULL = 0) and its initial-state outputs (each NULL = not written); `cost`: a cost or
@@ -347,6 +393,8 @@ struct RolloutSeeds {
     double* mu0_bar; double* S0_bar;
     bool cost;
 };
+// (updates the schedule model's memo, Handle::chunk_key / chunk_rows)
+int plan_rollout_grad(Handle* h, int N, int D, int A, int E, int H, int B, int Bp, bool seeded, GradPlan& p);
 // seeds == NULL: gpmpc_rollout_grad's LCB gradient; otherwise the same launch sequence with the seeded reverse sweep
 int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s, const RolloutSeeds* seeds = nullptr);
 int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s,          // grad_wide.hip: 8 < D <= 16

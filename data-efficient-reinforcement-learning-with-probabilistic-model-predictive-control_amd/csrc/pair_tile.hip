@@ -55,7 +55,7 @@ static void band_weights(const SepBand& b, std::vector<double>& w) {
     }
 }
 
-static int ensure_sep_table(Handle* h, int D) {
+int ensure_sep_table(Handle* h, int D) {
     if (h->septab_D == D && h->septab) return GPMPC_OK;
     SepTable T{};
     std::vector<double> w;
@@ -92,48 +92,44 @@ static int ensure_sep_table(Handle* h, int D) {
     return GPMPC_OK;
 }
 
-static void step_geometry(const Handle* h, const RolloutArgs& a, StepArgs& t) {
-    const int DP = tile_dp(a.D);
-    const int P = a.D * (a.D + 1) / 2;
-    t.nb = (a.N + kTileW - 1) / kTileW;
+// Records and tiles of a step (independent of the batch).
+static void step_geometry(const Handle& h, int N, int D, int E, StepArgs& t) {
+    const int DP = tile_dp(D);
+    const int P = D * (D + 1) / 2;
+    t.nb = (N + kTileW - 1) / kTileW;
     t.ntiles = t.nb * (t.nb + 1) / 2;
     t.PR = DP * DP + 2;
     t.PRP = 4 * DP * DP + 2;
-    t.off_mean = (a.E + 1) & ~1;
-    t.off_pair = t.off_mean + a.D * t.PR;
+    t.off_mean = (E + 1) & ~1;
+    t.off_pair = t.off_mean + D * t.PR;
     t.CS = t.off_pair + P * t.PRP;
-    t.ksep = h->sep_ks;
-    t.mom_stride = (h->sep_cmax + 1) & ~1;
-    t.PO = (P + a.D * (a.D + 1) + 1) & ~1;
-    // Candidates per tile workgroup.  All workgroups cost the same (cch candidates + a prologue worth ~8: the tile's 128 KiB,
-    // the points' inputs), 2 are resident per CU, so the launch takes ceil(workgroups / slots) rounds: pick the chunk that
-    // minimises rounds x (cch + 8) -- a last round that is 16 % full cost config 4 3 % (tile_chunk 72 vs 64: 80.0 vs 78.0 ms).
-    int cch = h->opt_tile_chunk;
-    if (cch <= 0) {
-        const long long nta = (long long)t.ntiles * a.D, slots = 2LL * h->num_cu;
-        long long best = -1;
-        for (int c = 16; c <= 128; c += 2) {
-            const long long wgs = nta * ((a.B + c - 1) / c);
-            const long long cost = ((wgs + slots - 1) / slots) * (c + 8);
-            if (best < 0 || cost < best) { best = cost; cch = c; }
-        }
-    }
-    cch = (cch + 1) & ~1;
-    if (cch > 256) cch = 256;
-    t.cch = cch;
-    t.nchunk = (a.B + cch - 1) / cch;
+    t.ksep = h.sep_ks;
+    t.mom_stride = (h.sep_cmax + 1) & ~1;
+    t.PO = (P + D * (D + 1) + 1) & ~1;
 }
 
-// Whether the LDS layouts of the step kernels fit this shape (launch_rollout asks before it chooses the path).
-bool tile_path_supported(Handle* h, const RolloutArgs& a) {
-    if (a.D > 4) return false;
-    if (ensure_sep_table(h, a.D)) return false;
+// Candidates (or trajectory items) per workgroup of a tile kernel.  All workgroups cost the same (c candidates + a prologue worth
+// ~8: the tile's 128 KiB, the points' inputs) and `slots` of them are resident at once, so the launch takes ceil(workgroups /
+// slots) rounds: pick the chunk that minimises rounds x (c + 8) -- a last round that is 16 % full cost config 4 3 % (a chunk
+// of 72 vs 64: 80.0 vs 78.0 ms).
+constexpr int kTileChunkMax = 128;
+static void tile_chunk(StepArgs& t, long long nta, int B, long long slots) {
+    long long best = -1;
+    for (int c = 16; c <= kTileChunkMax; c += 2) {
+        const long long cost = ((nta * ((B + c - 1) / c) + slots - 1) / slots) * (c + 8);
+        if (best < 0 || cost < best) { best = cost; t.cch = c; }
+    }
+    t.nchunk = (B + t.cch - 1) / t.cch;
+}
+
+// Whether the LDS layouts of the step kernels fit this shape (plan_rollout asks before it chooses the path).
+bool tile_path_fits(const Handle& h, int N, int D, int E) {
+    if (D > 4 || !h.septab || h.septab_D != D) return false;
     StepArgs t{};
-    step_geometry(h, a, t);
-    const int DP = tile_dp(a.D);
-    const size_t tile_lds = (size_t)make_tile_layout(DP, a.E, t.cch).total * sizeof(double);
-    const size_t point_lds = (size_t)make_point_layout(a.N, a.D, a.E, t.CS, t.mom_stride).total * sizeof(double);
-    return tile_lds <= (size_t)h->lds_limit && point_lds <= (size_t)h->lds_limit;
+    step_geometry(h, N, D, E, t);
+    const size_t tile_lds = (size_t)make_tile_layout(tile_dp(D), E, kTileChunkMax).total * sizeof(double);
+    const size_t point_lds = (size_t)make_point_layout(N, D, E, t.CS, t.mom_stride).total * sizeof(double);
+    return tile_lds <= (size_t)h.lds_limit && point_lds <= (size_t)h.lds_limit;
 }
 
 // Workspace of the batch-major path: step records | per-tile partial sums | hand-over flags.
@@ -141,19 +137,13 @@ int tile_workspace(Handle* h, RolloutArgs& a) {
     int rc = ensure_sep_table(h, a.D);
     if (rc) return rc;
     StepArgs t{};
-    step_geometry(h, a, t);
+    step_geometry(*h, a.N, a.D, a.E, t);
     const size_t nrec = (size_t)a.B * t.CS, npart = (size_t)a.B * a.D * t.ntiles, nflag = ((size_t)a.B + 1) / 2, npo = (size_t)a.B * t.PO;
     rc = grow(h, h->tilews, nrec + npart + nflag + npo);
     if (rc) return rc;
     a.tile_part = h->tilews.p + nrec;
     a.ntiles = t.ntiles;
     a.slow = reinterpret_cast<const int*>(h->tilews.p + nrec + npart);
-    if (!h->side_stream) {
-        // not blocking against the NULL stream: the dependencies between the two streams are the two events below
-        GPMPC_HIP_CHECK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        GPMPC_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming));
-        GPMPC_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_points, hipEventDisableTiming));
-    }
     return GPMPC_OK;
 }
 
@@ -165,10 +155,9 @@ int launch_tile_state_init(Handle* h, const RolloutArgs& a, hipStream_t s) {
 }
 
 // One horizon step: all D x D algebra (params), the per-candidate point pass, the N x N tiles of the diagonal pairs, then the
-// D x D end of the step.  Option "tile_overlap" runs the point pass on a side stream beside the tile kernel (one workgroup of
-// each fits a CU together: registers and LDS).  They do run concurrently, but the step takes the same time (config 4: 77.9 ms per
-// batch both ways): the tile kernel already keeps the fp64 pipe at 77 % of its nominal issue rate (2.27 GHz measured), which is
-// what an 8-chain FMA loop reaches on this part (profiles/fma_loop_microbench.txt: 58.6 of 78.6 TFLOP/s), so the default is one stream.
+// D x D end of the step, on one stream.  (The point pass beside the tile kernel on a second stream did run concurrently but the
+// step took the same time, config 4: 77.9 ms per batch both ways: the tile kernel already keeps the fp64 pipe at 77 % of its
+// nominal issue rate, what an 8-chain FMA loop reaches on this part, profiles/fma_loop_microbench.txt.)
 struct TileFuse {          // gradient launch: where the fused tile pass leaves the diagonal pairs' moments
     double* tmom;          // (B, D, ntiles, kTgMom) per-tile partial moments of this step (workspace)
     double* mom;           // (B, H, P, NSP)
@@ -179,14 +168,8 @@ struct TileFuse {          // gradient launch: where the fused tile pass leaves 
 template <int DP>
 static int launch_step_dp(Handle* h, const StepArgs& t, const TileFuse* fuse, hipStream_t s) {
     const int P = t.D * (t.D + 1) / 2;
-    const bool overlap = h->opt_tile_overlap != 0;
-    hipStream_t sp = overlap ? h->side_stream : s;
     hipLaunchKernelGGL(step_params_kernel<DP>, dim3((t.B * (t.D + P) + 255) / 256), dim3(256), 0, s, t);
     GPMPC_HIP_CHECK(h, hipGetLastError());
-    if (overlap) {
-        GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_params, s));
-        GPMPC_HIP_CHECK(h, hipStreamWaitEvent(sp, h->ev_params, 0));
-    }
     {
         auto kern = point_pass_kernel<DP>;
         int rc = allow_full_lds(h, reinterpret_cast<const void*>(kern));
@@ -194,10 +177,9 @@ static int launch_step_dp(Handle* h, const StepArgs& t, const TileFuse* fuse, hi
         const PointLayout L = make_point_layout(t.N, t.D, t.E, t.CS, t.mom_stride);
         const size_t lds = (size_t)L.total * sizeof(double);
         if (lds > (size_t)h->lds_limit) { h->err = "point pass: LDS layout too large"; return GPMPC_ERR_LIMIT; }
-        hipLaunchKernelGGL(kern, dim3(t.B), dim3(256), lds, sp, t);
+        hipLaunchKernelGGL(kern, dim3(t.B), dim3(256), lds, s, t);
         GPMPC_HIP_CHECK(h, hipGetLastError());
     }
-    if (overlap) GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_points, sp));
     if (fuse) {
         // gradient launch: the tile pass of this step forms the diagonal pairs' moments too (pair_tile_moments_kernel<DP, true>):
         // its W partials ARE the tile sums step_combine_kernel adds, written to t.part by the same kernel
@@ -205,20 +187,8 @@ static int launch_step_dp(Handle* h, const StepArgs& t, const TileFuse* fuse, hi
         int rc = allow_full_lds(h, reinterpret_cast<const void*>(kern));
         if (rc) return rc;
         StepArgs tg = t;
-        // one workgroup per CU here (2 wavefronts per SIMD): chunk = rounds x (chunk + prologue) over num_cu slots
-        int cch = h->opt_tile_chunk;
         const int nta = t.ntiles * t.D;
-        if (cch <= 0) {
-            long long best = -1;
-            for (int c = 16; c <= 128; c += 2) {
-                const long long wgs = (long long)nta * ((t.B + c - 1) / c);
-                const long long cost = ((wgs + h->num_cu - 1) / h->num_cu) * (c + 8);
-                if (best < 0 || cost < best) { best = cost; cch = c; }
-            }
-        }
-        cch = (cch + 1) & ~1;
-        tg.cch = cch;
-        tg.nchunk = (t.B + cch - 1) / cch;
+        tile_chunk(tg, nta, t.B, h->num_cu);           // one workgroup per CU here (2 wavefronts per SIMD)
         const size_t lds = (size_t)make_tile_grad_layout(DP, t.E).total * sizeof(double);
         if (lds > (size_t)h->lds_limit) { h->err = "pair tiles: input dimension too large for the LDS layout"; return GPMPC_ERR_LIMIT; }
         const int per_xcd = (nta + 7) / 8;
@@ -239,7 +209,6 @@ static int launch_step_dp(Handle* h, const StepArgs& t, const TileFuse* fuse, hi
         hipLaunchKernelGGL(kern, dim3(8 * per_xcd * t.nchunk), dim3(kTileWaves * 64), lds, s, t);
         GPMPC_HIP_CHECK(h, hipGetLastError());
     }
-    if (overlap) GPMPC_HIP_CHECK(h, hipStreamWaitEvent(s, h->ev_points, 0));
     hipLaunchKernelGGL(step_combine_kernel<DP>, dim3(t.B), dim3(64), 0, s, t);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     return GPMPC_OK;
@@ -248,7 +217,8 @@ static int launch_step_dp(Handle* h, const StepArgs& t, const TileFuse* fuse, hi
 // Horizon step `step` of the batch-major path for every candidate the separable forms cover (a.mu_out / a.Sig_out hold the state).
 int launch_pair_tiles(Handle* h, const RolloutArgs& a, int step, hipStream_t s) {
     StepArgs t{};
-    step_geometry(h, a, t);
+    step_geometry(*h, a.N, a.D, a.E, t);
+    tile_chunk(t, (long long)t.ntiles * a.D, a.B, 2LL * h->num_cu);       // two workgroups per CU
     t.Xt = a.Xt; t.beta = a.beta; t.Tm = a.Tm; t.ils2 = a.ils2; t.var = a.var; t.logvar = a.logvar; t.xrange = a.xrange;
     t.actions = a.actions;
     t.mu = a.mu_out; t.Sig = a.Sig_out;
@@ -279,13 +249,6 @@ int launch_pair_tiles(Handle* h, const RolloutArgs& a, int step, hipStream_t s) 
     }
 }
 
-// Whether a gradient launch may leave the diagonal pairs' moments to the batch-major forward (launch_rollout decides whether the
-// forward takes that path at all; h->last_fused_tiles says afterwards whether it did).
-bool tile_moments_fusable(Handle* h, const RolloutArgs& a) {
-    if (h->opt_grad_fuse == 0 || a.D < 2 || a.D > 4) return false;
-    return (size_t)make_tile_grad_layout(tile_dp(a.D), a.E).total * sizeof(double) <= (size_t)h->lds_limit;
-}
-
 // ------------------------------------------------------------------------------------------
 // Gradient: moments of the diagonal pairs of ALL (candidate, step) items of a stored trajectory, batch-major
 // (pair_tile_grad_kernel.h).  Items are taken in blocks so that the records and per-tile partial moments stay a
@@ -312,19 +275,7 @@ static int launch_tile_moments_dp(Handle* h, StepArgs t, long long items, double
         const int nb = (int)((items - i0 < block) ? items - i0 : block);
         t.B = nb;
         t.item0 = (int)i0;
-        // chunk: rounds x (chunk + prologue) over one workgroup per CU (2 waves per SIMD: ~200 VGPRs)
-        int cch = h->opt_tile_chunk;
-        if (cch <= 0) {
-            long long best = -1;
-            for (int c = 16; c <= 128; c += 2) {
-                const long long wgs = (long long)nta * ((nb + c - 1) / c);
-                const long long cost = ((wgs + h->num_cu - 1) / h->num_cu) * (c + 8);
-                if (best < 0 || cost < best) { best = cost; cch = c; }
-            }
-        }
-        cch = (cch + 1) & ~1;
-        t.cch = cch;
-        t.nchunk = (nb + cch - 1) / cch;
+        tile_chunk(t, nta, nb, h->num_cu);              // one workgroup per CU (2 waves per SIMD: ~200 VGPRs)
         const int P = t.D * (t.D + 1) / 2;
         hipLaunchKernelGGL((step_params_kernel<DP, true>), dim3((unsigned)(((long long)nb * (t.D + P) + 255) / 256)), dim3(256), 0, s, t);
         GPMPC_HIP_CHECK(h, hipGetLastError());
@@ -337,15 +288,14 @@ static int launch_tile_moments_dp(Handle* h, StepArgs t, long long items, double
     return GPMPC_OK;
 }
 
-bool tile_moments_supported(Handle* h, const RolloutArgs& a, int NSP) {
-    if (a.D < 2 || a.D > 4 || NSP > 64 || a.E - a.D > 8) return false;
-    const int DP = tile_dp(a.D);
-    return (size_t)make_tile_grad_layout(DP, a.E).total * sizeof(double) <= (size_t)h->lds_limit;
+bool tile_moments_supported(const Handle& h, int D, int E, int NSP) {
+    if (D < 2 || D > 4 || NSP > 64 || E - D > 8) return false;
+    return (size_t)make_tile_grad_layout(tile_dp(D), E).total * sizeof(double) <= (size_t)h.lds_limit;
 }
 
 int launch_tile_moments(Handle* h, const RolloutArgs& a, double* mom, int* done, int NSP, int NXP, hipStream_t s) {
     StepArgs t{};
-    step_geometry(h, a, t);
+    step_geometry(*h, a.N, a.D, a.E, t);
     const int DP = tile_dp(a.D);
     t.off_pair = t.off_mean;                       // compact records: inputs | the D diagonal pair problems
     t.CS = t.off_pair + a.D * t.PRP;

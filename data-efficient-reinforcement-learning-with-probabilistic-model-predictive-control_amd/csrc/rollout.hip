@@ -160,19 +160,25 @@ static int padded_dim(int D) {
     return -1;
 }
 
-int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
-    const int N = a.N, D = a.D, A = a.A, E = a.E;
+int ensure_rollout_tables(Handle* h, int N, int D) {
+    int rc = ensure_monomials(h, D);
+    if (rc) return rc;
+    // the bands of the batch-major path where plan_rollout may take it (a failed upload leaves the path unsupported: tile_path_fits)
+    if (D <= 4 && h->opt_pair_tiles != 2 && (h->opt_pair_tiles == 1 || tables_outgrow_l2(N, D))) (void)ensure_sep_table(h, D);
+    return GPMPC_OK;
+}
+
+int plan_rollout(const Handle& h, int N, int D, int A, int E, int H, int Bp, const RolloutRequest& req, RolloutPlan& p) {
+    p = RolloutPlan{};
     const int P = D * (D + 1) / 2;
     const int DP = padded_dim(D);
-    // every batch-size rule below reads Bp, never a.B: a slice planned for its whole population takes the population's form
-    // (same chunk lengths, same summation order), while the grid still covers the a.B candidates launched
-    const int Bp = a.B_plan > a.B ? a.B_plan : a.B;
-    if (DP < 0) { h->err = "D exceeds GPMPC_MAX_D"; return GPMPC_ERR_LIMIT; }
+    if (DP < 0) { p.err = "D exceeds GPMPC_MAX_D"; return GPMPC_ERR_LIMIT; }
+    p.DP = DP;
 
     // workgroup size: one candidate per workgroup.  Measured on MI355X (config 2..4 shapes, B = 256..2048):
     // 16 waves per candidate beat 8 even when the batch oversubscribes the 256 CUs (340k vs 265k
     // rollouts/s at B = 2048), so 1024 threads unless asked otherwise.
-    int nt = h->opt_threads;
+    int nt = h.opt_threads;
     if (nt != 256 && nt != 512 && nt != 1024) {
         nt = 1024;
         // Small memories with batches of several workgroups per CU: the pairwise pass of a step is a few hundred elements per
@@ -180,8 +186,8 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // (N = 50, H = 15, tools/gpu_bench_ab.sh: B = 512: 1.85 / 2.61 / 2.16 M rollouts/s with 1024 / 512 / 256 threads,
         // B = 2048: 2.03 / 3.08 / 3.18 M, B = 8192: 2.08 / 3.27 / 3.51 M; at N = 200 1024 threads win at every B).
         if (N <= 64) {
-            if (Bp >= 8 * h->num_cu) nt = 256;
-            else if (Bp >= 2 * h->num_cu) nt = 512;
+            if (Bp >= 8 * h.num_cu) nt = 256;
+            else if (Bp >= 2 * h.num_cu) nt = 512;
         }
     }
     // Mid-size memories with many workgroups per CU: two workgroups of 8 wavefronts share a CU (half the LDS each: the row
@@ -189,40 +195,32 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     // (round 4, profiles/r04h_share_cu.txt, config-2 shape N = 200): B = 512 equal, B = 1024 +2.6 %, B = 4096 +7.9 % (606 -> 654 k
     // rollouts/s); N = 500: -4 % at B = 1024, +2.6 % at 4096; N = 50: equal.  Hence from 8 workgroups per CU on, N in (64, 256].
     bool share_cu = false;
-    if (h->opt_threads == 0 && h->opt_lds_kb == 0 && N > 64 && N <= 256 && D <= 4 && Bp >= 8 * h->num_cu && h->opt_pair_tiles != 1) {
+    if (h.opt_threads == 0 && h.opt_lds_kb == 0 && N > 64 && N <= 256 && D <= 4 && Bp >= 8 * h.num_cu && h.opt_pair_tiles != 1) {
         nt = 512;
         share_cu = true;
     }
     const int nw = nt / 64;
-    int rcm = ensure_monomials(h, D);
-    if (rcm) return rcm;
-    const int CM = (h->opt_force_path == 0) ? h->mono_CM : 0;
-    a.xrange = h->xrange.p; a.mono_exp = h->mono_exp; a.mono_w = h->mono_w.p;
-    for (int k = 0; k < 16; ++k) a.mono_cum[k] = h->mono_cum[k];
-    a.sep_kmax = (h->opt_force_path == 0) ? h->sep_kmax : 0;
-    a.CM = CM;
-    a.force_path = h->opt_force_path;
-    a.force_sep = h->opt_force_sep;
-    a.exact_dim = 0;
+    const int CM = (h.opt_force_path == 0) ? h.mono_CM : 0;
+    p.CM = CM;
+    p.sep_kmax = (h.opt_force_path == 0) ? h.sep_kmax : 0;
 
     // LDS budget of a workgroup of the fused-horizon kernel: all of it, or (option "lds_limit_kb", sharing rule below) a share
     // that lets two workgroups of 8 wavefronts live on one CU
-    size_t lds_cap = (size_t)h->lds_limit;
-    if (h->opt_lds_kb > 0 && (size_t)h->opt_lds_kb * 1024 < lds_cap) lds_cap = (size_t)h->opt_lds_kb * 1024;
-    if (share_cu) lds_cap = (size_t)h->lds_limit / 2;
+    size_t lds_cap = (size_t)h.lds_limit;
+    if (h.opt_lds_kb > 0 && (size_t)h.opt_lds_kb * 1024 < lds_cap) lds_cap = (size_t)h.opt_lds_kb * 1024;
+    if (share_cu) lds_cap = (size_t)h.lds_limit / 2;
     // choose pairs-per-group G and row chunking for the LDS-resident variant
-    bool gs = h->opt_force_global != 0;
+    bool gs = h.opt_force_global != 0;
     int G = 0, CH = 0, RC = 0;
     size_t lds_bytes = 0;
     // two adjacent columns per lane where the one-column loop is bound by the LDS broadcast bandwidth (small D)
-    const bool cols2 = !gs && (h->opt_cols_per_lane == 2 || (h->opt_cols_per_lane == 0 && DP <= 4));
-    // Batch-major pass for the diagonal pairs (pair_tile_kernel.h) when the D tables T_a no longer stay in an XCD's 4 MiB L2
+    const bool cols2 = !gs && (h.opt_cols_per_lane == 2 || (h.opt_cols_per_lane == 0 && DP <= 4));
+    // Batch-major pass for the diagonal pairs (pair_tile_kernel.h) when the D tables T_a no longer stay in an XCD's L2
     // and the batch is large enough to amortise a tile over many candidates; the fused-horizon kernel otherwise.
     bool tiled = false;
-    if (!gs && cols2 && DP <= 4 && nt == 1024 && h->opt_pair_tiles != 2) {
-        const double tri_bytes = 4.0 * D * (double)N * N;          // upper triangles of the D tables
-        tiled = h->opt_pair_tiles == 1 || (tri_bytes >= 6.0e6 && Bp >= 2 * h->num_cu);
-        tiled = tiled && tile_path_supported(h, a);
+    if (!gs && cols2 && DP <= 4 && nt == 1024 && h.opt_pair_tiles != 2) {
+        tiled = h.opt_pair_tiles == 1 || (tables_outgrow_l2(N, D) && Bp >= 2 * h.num_cu);
+        tiled = tiled && tile_path_fits(h, N, D, E);
     }
     const int Pg = tiled ? (P - D > 0 ? P - D : 1) : P;           // pairs the per-candidate kernel keeps row records for
     const int NCu = cols2 ? (N + 1) / 2 : N;     // column units per row chunk
@@ -247,7 +245,7 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // N = 500: 32 rows 0.495 against 0.557 (16) at 16 members.  The chunk length depends on nothing but N (not on B or the
         // cluster size): every few-candidate launch sums in the same order.
         if (cl_chunks) rc = (N + (N < 384 ? 16 : 32) - 1) / (N < 384 ? 16 : 32);
-        if (h->opt_rows_per_chunk > 0) rc = (N + h->opt_rows_per_chunk - 1) / h->opt_rows_per_chunk;
+        if (h.opt_rows_per_chunk > 0) rc = (N + h.opt_rows_per_chunk - 1) / h.opt_rows_per_chunk;
         CH = (N + (int)rc - 1) / (int)rc;
         CH = (CH + 3) & ~3;                      // rows are processed in groups of 4
         if (CH > 64) CH = 64;                    // T_a carries 64 zero padding rows
@@ -258,10 +256,9 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
     // fit the chip one workgroup per CU -- every member must be resident, they wait for each other once per horizon step.
     // Candidates are placed in groups of 8 (one per XCD), so the grid is 8 x cluster x ceil(B / 8) workgroups.
     int cluster = 1;
-    const int groups8 = (a.B + 7) / 8;            // launched
-    const int groups8p = (Bp + 7) / 8;            // planned: the cluster size and whether the form fits at all
-    bool want_cluster = !gs && !tiled && cols2 && DP <= 4 && !share_cu && h->opt_lds_kb == 0 &&
-                        h->opt_cluster != 1 && a.H < 8191 && 8 * groups8p * 2 <= h->num_cu;
+    const int groups8p = (Bp + 7) / 8;            // the cluster size and whether the form fits at all
+    bool want_cluster = !gs && !tiled && cols2 && DP <= 4 && !share_cu && h.opt_lds_kb == 0 &&
+                        h.opt_cluster != 1 && H < 8191 && 8 * groups8p * 2 <= h.num_cu;
     auto choose_layout = [&](bool cl) {
         G = 0;
         // X^T in LDS when it is small next to the budget (<= 32 KiB) and the layout still fits
@@ -270,9 +267,9 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
             for (int g = Pg < 48 ? Pg : 48; g >= 1; --g) {
                 chunking(g);
                 const int wpp = (RC * NCu + 63) / 64;
-                Layout L = make_layout(N, D, A, E, g, DP, wpp, CM, CH, a.H * A, xl != 0, cl);
+                Layout L = make_layout(N, D, A, E, g, DP, wpp, CM, CH, H * A, xl != 0, cl);
                 if ((size_t)L.lds_total * 8 <= lds_cap) {
-                    G = g; lds_bytes = (size_t)L.lds_total * 8; a.x_in_lds = xl;
+                    G = g; lds_bytes = (size_t)L.lds_total * 8; p.x_in_lds = xl;
                     break;
                 }
             }
@@ -280,7 +277,6 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
             if (G != 0 && G < (Pg < 48 ? Pg : 48) && xl == 1) { G = 0; }
         }
     };
-    int cl_slots = 0;
     if (!gs && want_cluster) {
         // the cooperative form keeps all pairs in ONE group (one exchange per step) but a member holds per-point records only of the
         // pairs it owns items of (ClusterMap): its chunk length depends on N alone, so chunks, slots and cluster size come first
@@ -296,12 +292,12 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // 0.128 / 0.128, N = 80 0.129 / 0.151, N = 130 0.133 / 0.179; D = 2: N = 100 0.117 / 0.103, N = 150 equal, N = 200 0.139 / 0.173;
         // D = 1: N = 200 0.118 / 0.112, N = 400 0.139 / 0.203; D = 4: N = 100 0.184 / 0.334); with fewer members per candidate from
         // ~24 items on, as before
-        const int cap = h->num_cu / (8 * groups8p);
+        const int cap = h.num_cu / (8 * groups8p);
         const int items = D * wtri, P_off = D * (D - 1) / 2;
         const int cs_floor = (P_off + 2 * D > 9) ? P_off + 2 * D : 9;
         const bool roomy = cap >= cs_floor;
         int cs = 1;
-        if (h->opt_cluster >= 2) cs = h->opt_cluster;
+        if (h.opt_cluster >= 2) cs = h.opt_cluster;
         else if (items >= 24 || (roomy && items * D >= 18)) {
             cs = (items + 3) / 4;
             if (roomy && cs < cs_floor) cs = cs_floor;
@@ -310,19 +306,18 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         if (cs > cap) cs = cap;
         // (the pairs a member holds records of depend on how the cluster size divides the pairs: when the size of the rule does not
         //  fit the LDS, the next smaller ones are tried -- down to half of it; a size asked for by option is taken or not at all)
-        for (const int cs_min = h->opt_cluster >= 2 ? cs : (cs + 1) / 2; cs >= 2 && cs >= cs_min && cluster == 1; --cs) {
-            ClusterMap& cmap = a.cmap;
-            cmap.plan(cs, D, wpp_c, wtri);
-            cl_slots = 0;
-            for (int m = 0; m < cs; ++m) { const int n = cmap.slots_needed(m); if (n > cl_slots) cl_slots = n; }
+        for (const int cs_min = h.opt_cluster >= 2 ? cs : (cs + 1) / 2; cs >= 2 && cs >= cs_min && cluster == 1; --cs) {
+            p.cmap.plan(cs, D, wpp_c, wtri);
+            p.cl_slots = 0;
+            for (int m = 0; m < cs; ++m) { const int n = p.cmap.slots_needed(m); if (n > p.cl_slots) p.cl_slots = n; }
             for (int xl = ((size_t)E * N * 8 <= 32 * 1024) ? 1 : 0; xl >= 0 && cluster == 1; --xl) {
-                const Layout L = make_layout(N, D, A, E, P, DP, wpp_c, CM, CH, a.H * A, xl != 0, true, cl_slots);
-                if ((size_t)L.lds_total * 8 <= lds_cap) { G = P; lds_bytes = (size_t)L.lds_total * 8; a.x_in_lds = xl; cluster = cs; }
+                const Layout L = make_layout(N, D, A, E, P, DP, wpp_c, CM, CH, H * A, xl != 0, true, p.cl_slots);
+                if ((size_t)L.lds_total * 8 <= lds_cap) { G = P; lds_bytes = (size_t)L.lds_total * 8; p.x_in_lds = xl; cluster = cs; }
             }
         }
         // members of 8 wavefronts (no register spills: 145 VGPRs) from 8 members on; few, wide members otherwise (measured: B = 64,
         // 4 members: 0.267 / 0.270 ms with 1024 / 512 threads; B = 128, 2 members: 0.323 / 0.354; 16 members: 0.240 / 0.216)
-        if (cluster > 1 && h->opt_threads == 0) nt = cluster >= 8 ? 512 : 1024;
+        if (cluster > 1 && h.opt_threads == 0) nt = cluster >= 8 ? 512 : 1024;
         if (cluster == 1) cl_chunks = false;
     }
     if (!gs && cluster == 1) {
@@ -336,20 +331,93 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         // items matter; rows past the data are zero records.  Option "rows_per_chunk" overrides (tests, A/B).
         if (DP % 4 == 0 && DP >= 8) {
             CH = (N >= 1024) ? 256 : 64;
-            if (h->opt_rows_per_chunk > 0) CH = h->opt_rows_per_chunk <= 64 ? 64 : (h->opt_rows_per_chunk <= 128 ? 128 : 256);
+            if (h.opt_rows_per_chunk > 0) CH = h.opt_rows_per_chunk <= 64 ? 64 : (h.opt_rows_per_chunk <= 128 ? 128 : 256);
         } else {
             CH = (N >= 64) ? 64 : ((N + 3) & ~3);
         }
         RC = (N + CH - 1) / CH;
         G = 1;
-        StreamLayout SL = make_stream_layout(N, D, A, E, DP, CH, a.H * A);
+        StreamLayout SL = make_stream_layout(N, D, A, E, DP, CH, H * A);
         lds_bytes = (size_t)SL.total * 8;
-        if (lds_bytes > (size_t)h->lds_limit) { h->err = "rollout: N too large for the LDS column-factor array"; return GPMPC_ERR_LIMIT; }
+        if (lds_bytes > (size_t)h.lds_limit) { p.err = "rollout: N too large for the LDS column-factor array"; return GPMPC_ERR_LIMIT; }
         nt = 1024;
     }
-    a.G = G; a.CH = CH; a.RC = RC;
-    a.cols2 = (cols2 && !gs) ? 1 : 0;
-    if (a.act_inline_n > 0 && (gs || tiled)) {
+    p.cols2 = (cols2 && !gs) ? 1 : 0;
+    const int NCf = p.cols2 ? NCu : N;
+    const unsigned wppv = (unsigned)((RC * NCf + 63) / 64);
+    p.magic_N = magic_div((unsigned)NCf);
+    p.magic_wpp = magic_div(wppv);
+    p.magic_pt = magic_div((unsigned)N);
+    if ((unsigned long long)RC * NCf * NCf >= 0x100000000ULL || (unsigned long long)G * wppv * wppv >= 0x100000000ULL ||
+        (!gs && (unsigned long long)(D + 2 * P) * N * N >= 0x100000000ULL)) {      // magic_pt: the fused-horizon kernel only
+        p.err = "rollout: index range too large for the multiply-high division"; return GPMPC_ERR_LIMIT;
+    }
+    if (!gs && (unsigned long long)G * wppv >= 65000ULL) {     // 16-bit entries of the step's work-item list
+        p.err = "rollout: too many work-item slots for the 16-bit item list"; return GPMPC_ERR_LIMIT;
+    }
+    p.nt = nt; p.path = gs ? 1 : (tiled ? 2 : 0);
+    p.G = G; p.CH = CH; p.RC = RC; p.lds_bytes = lds_bytes;
+    p.cluster = cluster;
+    if (cluster > 1) p.xch_n = G * (int)wppv + G + D * (D + 1) + 32;       // item slots | separable pairs | mean sums | the members' XCD ids
+    p.fused_tiles = tiled && req.fused_tiles;
+    p.costs_to_caller = req.costs_to_caller;
+    return GPMPC_OK;
+}
+
+// The cooperative form's exchange buffers and this launch's tags.
+static int exchange_buffers(Handle* h, RolloutArgs& a, const RolloutPlan& p, hipStream_t s) {
+    const size_t words = (size_t)8 * ((a.B + 7) / 8) * 4 * p.xch_n;
+    // tags never repeat while the HANDLE lives (8192 per launch), short of the 32-bit wrap; the buffer is zeroed when it is
+    // (re)allocated and at the wrap
+    // The epoch survives a re-allocation: the new buffer may sit where the old one did, and lines of the old one -- with the
+    // old launches' tags -- can still be in some XCD's L2 (a re-allocated buffer whose tags restarted at 1 let a member accept
+    // such a line: the members' states then differ, so do their item lists, and somebody waits for a value nobody publishes:
+    // seen as a bounded-wait timeout in round 6).  Only the 32-bit wrap restarts it, 2^19 launches later.
+    const bool fresh = !h->xch.p || words > h->xch.cap;
+    int rc = grow(h, h->xch, words);
+    if (rc) return rc;
+    const bool wrap = h->xch_epoch >= (1u << 19) - 1;
+    if (fresh || wrap) { rc = zero_exchange(h, reinterpret_cast<unsigned long long*>(h->xch.p), h->xch.cap, s); if (rc) return rc; }
+    if (words > h->xch_uc_cap) {
+        if (h->xch_uc) GPMPC_HIP_CHECK(h, hipFree(h->xch_uc));
+        h->xch_uc = nullptr; h->xch_uc_cap = 0;
+        void* q = nullptr;
+        if (hipExtMallocWithFlags(&q, words * sizeof(unsigned long long), hipDeviceMallocUncached) != hipSuccess) {
+            (void)hipGetLastError();
+            GPMPC_HIP_CHECK(h, hipExtMallocWithFlags(&q, words * sizeof(unsigned long long), hipDeviceMallocFinegrained));
+        }
+        h->xch_uc = reinterpret_cast<unsigned long long*>(q);
+        h->xch_uc_cap = words;
+        rc = zero_exchange(h, h->xch_uc, words, s);
+        if (rc) return rc;
+    } else if (wrap) {
+        rc = zero_exchange(h, h->xch_uc, h->xch_uc_cap, s);
+        if (rc) return rc;
+    }
+    if (wrap) h->xch_epoch = 1;
+    a.xch_tag0 = h->xch_epoch * 8192u;
+    h->xch_epoch += 1;
+    a.xch = reinterpret_cast<unsigned long long*>(h->xch.p);
+    a.xch_uc = h->xch_uc;
+    return GPMPC_OK;
+}
+
+int launch_rollout(Handle* h, RolloutArgs& a, const RolloutPlan& p, hipStream_t s) {
+    const bool tiled = p.path == 2;
+    a.xrange = h->xrange.p; a.mono_exp = h->mono_exp; a.mono_w = h->mono_w.p;
+    for (int k = 0; k < 16; ++k) a.mono_cum[k] = h->mono_cum[k];
+    a.sep_kmax = p.sep_kmax; a.CM = p.CM;
+    a.force_path = h->opt_force_path; a.force_sep = h->opt_force_sep;
+    a.x_in_lds = p.x_in_lds; a.cols2 = p.cols2;
+    a.G = p.G; a.CH = p.CH; a.RC = p.RC;
+    a.magic_N = p.magic_N; a.magic_wpp = p.magic_wpp; a.magic_pt = p.magic_pt;
+    a.cluster = p.cluster; a.cmap = p.cmap; a.cl_slots = p.cl_slots; a.cl_dbg = h->opt_cl_dbg;
+    a.xch = nullptr; a.xch_uc = nullptr; a.xch_n = p.xch_n; a.xch_tag0 = 0;
+    // the batch-major state of a (possibly re-used) argument block is set on EVERY call, never inherited from an earlier one
+    a.tiled = tiled ? 1 : 0;
+    if (!p.fused_tiles) a.grad_mom = nullptr;              // only the batch-major forward can form the gradient's tile moments
+    if (!tiled) { a.t_begin = 0; a.t_end = 0; a.slow = nullptr; a.tile_part = nullptr; a.ntiles = 0; }
+    if (a.act_inline_n > 0 && p.path != 0) {
         // only the fused-horizon kernel reads the sequence from its argument block: the other paths get it as its own launch
         InlineActs u;
         for (int i = 0; i < kInlineActs; ++i) u.v[i] = a.act_inline[i];
@@ -357,97 +425,28 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         GPMPC_HIP_CHECK(h, hipGetLastError());
         a.act_inline_n = 0;
     }
-    const int NCf = a.cols2 ? NCu : N;
-    {
-        // exact division by multiply-high: for d >= 2, umulhi(x, ceil(2^32 / d)) == x / d whenever x * d < 2^32
-        // (magic 0 encodes d == 1: no division)
-        const unsigned wppv = (unsigned)((RC * NCf + 63) / 64);
-        auto magic = [](unsigned d) -> unsigned { return d <= 1 ? 0u : (unsigned)((0x100000000ULL + d - 1) / d); };
-        a.magic_N = magic((unsigned)NCf);
-        a.magic_wpp = magic(wppv);
-        a.magic_pt = magic((unsigned)N);
-        if ((unsigned long long)RC * NCf * NCf >= 0x100000000ULL || (unsigned long long)G * wppv * wppv >= 0x100000000ULL ||
-            (!gs && (unsigned long long)(D + 2 * P) * N * N >= 0x100000000ULL)) {      // magic_pt: the fused-horizon kernel only
-            h->err = "rollout: index range too large for the multiply-high division"; return GPMPC_ERR_LIMIT;
-        }
-        if (!gs && (unsigned long long)G * wppv >= 65000ULL) {     // 16-bit entries of the step's work-item list
-            h->err = "rollout: too many work-item slots for the 16-bit item list"; return GPMPC_ERR_LIMIT;
-        }
-    }
-
     // the propagation always stores the trajectory (the cost kernel reads it back): own buffers if
     // the caller did not ask for them
-    double* user_cm = a.cm_out;
-    double* user_cv = a.cv_out;
-    double* user_J = a.J_out;
-    {
-        const size_t nmu = (size_t)a.B * (a.H + 1) * D, nS = nmu * D;
-        if (!a.mu_out || !a.Sig_out) {
-            int rc = grow(h, h->traj, nmu + nS);
-            if (rc) return rc;
-            if (!a.mu_out) a.mu_out = h->traj.p;
-            if (!a.Sig_out) a.Sig_out = h->traj.p + nmu;
-        }
+    if (!a.mu_out || !a.Sig_out) {
+        const size_t nmu = (size_t)a.B * (a.H + 1) * a.D, nS = nmu * a.D;
+        int rc = grow(h, h->traj, nmu + nS);
+        if (rc) return rc;
+        if (!a.mu_out) a.mu_out = h->traj.p;
+        if (!a.Sig_out) a.Sig_out = h->traj.p + nmu;
     }
-    int rc = GPMPC_OK;
+    int rc = p.cluster > 1 ? exchange_buffers(h, a, p, s) : GPMPC_OK;
+    if (rc) return rc;
     auto launch_kernel = [&]() {
-        switch (DP) {
-            case 2:  return launch_rollout_dp2(h, a, nt, gs, lds_bytes, s);
-            case 3:  return launch_rollout_dp3(h, a, nt, gs, lds_bytes, s);
-            case 4:  return launch_rollout_dp4(h, a, nt, gs, lds_bytes, s);
-            case 6:  return launch_rollout_dp6(h, a, nt, gs, lds_bytes, s);
-            case 8:  return launch_rollout_dp8(h, a, nt, gs, lds_bytes, s);
-            default: return launch_rollout_dp16(h, a, nt, gs, lds_bytes, s);
+        const bool gs = p.path == 1;
+        switch (p.DP) {
+            case 2:  return launch_rollout_dp2(h, a, p.nt, gs, p.lds_bytes, s);
+            case 3:  return launch_rollout_dp3(h, a, p.nt, gs, p.lds_bytes, s);
+            case 4:  return launch_rollout_dp4(h, a, p.nt, gs, p.lds_bytes, s);
+            case 6:  return launch_rollout_dp6(h, a, p.nt, gs, p.lds_bytes, s);
+            case 8:  return launch_rollout_dp8(h, a, p.nt, gs, p.lds_bytes, s);
+            default: return launch_rollout_dp16(h, a, p.nt, gs, p.lds_bytes, s);
         }
     };
-    a.cl_dbg = h->opt_cl_dbg;
-    a.cl_slots = cl_slots;
-    a.xch_uc = nullptr;
-    a.cluster = cluster; a.xch = nullptr; a.xch_n = 0; a.xch_tag0 = 0;
-    h->last_cluster = cluster;
-    if (cluster > 1) {
-        const unsigned wppv = (unsigned)((RC * NCu + 63) / 64);
-        a.xch_n = G * (int)wppv + G + D * (D + 1) + 32;       // item slots | separable pairs | mean sums | the members' XCD ids
-        const size_t words = (size_t)8 * groups8 * 4 * a.xch_n;
-        // tags never repeat while the HANDLE lives (8192 per launch), short of the 32-bit wrap; the buffer is zeroed when it is
-        // (re)allocated and at the wrap
-        // The epoch survives a re-allocation: the new buffer may sit where the old one did, and lines of the old one -- with the
-        // old launches' tags -- can still be in some XCD's L2 (a re-allocated buffer whose tags restarted at 1 let a member accept
-        // such a line: the members' states then differ, so do their item lists, and somebody waits for a value nobody publishes:
-        // seen as a bounded-wait timeout in round 6).  Only the 32-bit wrap restarts it, 2^19 launches later.
-        const bool fresh = !h->xch.p || words > h->xch.cap;
-        int rcx = grow(h, h->xch, words);
-        if (rcx) return rcx;
-        const bool wrap = h->xch_epoch >= (1u << 19) - 1;
-        if (fresh || wrap) { rcx = zero_exchange(h, reinterpret_cast<unsigned long long*>(h->xch.p), h->xch.cap, s); if (rcx) return rcx; }
-        if (words > h->xch_uc_cap) {
-            if (h->xch_uc) GPMPC_HIP_CHECK(h, hipFree(h->xch_uc));
-            h->xch_uc = nullptr; h->xch_uc_cap = 0;
-            void* q = nullptr;
-            if (hipExtMallocWithFlags(&q, words * sizeof(unsigned long long), hipDeviceMallocUncached) != hipSuccess) {
-                (void)hipGetLastError();
-                GPMPC_HIP_CHECK(h, hipExtMallocWithFlags(&q, words * sizeof(unsigned long long), hipDeviceMallocFinegrained));
-            }
-            h->xch_uc = reinterpret_cast<unsigned long long*>(q);
-            h->xch_uc_cap = words;
-            rcx = zero_exchange(h, h->xch_uc, words, s);
-            if (rcx) return rcx;
-        } else if (wrap) {
-            rcx = zero_exchange(h, h->xch_uc, h->xch_uc_cap, s);
-            if (rcx) return rcx;
-        }
-        if (wrap) h->xch_epoch = 1;
-        a.xch_tag0 = h->xch_epoch * 8192u;
-        h->xch_epoch += 1;
-        a.xch = reinterpret_cast<unsigned long long*>(h->xch.p);
-        a.xch_uc = h->xch_uc;
-    }
-    h->last_rollout_path = gs ? 1 : (tiled ? 2 : 0);
-    // the batch-major state of a (possibly re-used) argument block is set on EVERY call, never inherited from an earlier one
-    a.tiled = tiled ? 1 : 0;
-    if (!tiled) a.grad_mom = nullptr;                      // only the batch-major forward can form the gradient's tile moments
-    h->last_fused_tiles = (tiled && a.grad_mom) ? 1 : 0;
-    if (!tiled) { a.t_begin = 0; a.t_end = 0; a.slow = nullptr; a.tile_part = nullptr; a.ntiles = 0; }
     if (tiled) {
         // per horizon step: parameters + batch-major tiles of the diagonal pairs, then the per-candidate rest of the step
         rc = tile_workspace(h, a);
@@ -461,12 +460,23 @@ int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
         rc = launch_kernel();
     }
     if (rc) return rc;
-    if ((user_cm || user_cv || user_J) && !a.defer_cost) {
-        hipLaunchKernelGGL(traj_cost_kernel, dim3(a.B), dim3(64), 0, s, a.mu_out, a.Sig_out, a.actions, a.cost, D, A, a.H,
-                           a.kappa, a.clip, a.use_constraints, user_cm, user_cv, user_J);
-        GPMPC_HIP_CHECK(h, hipGetLastError());
+    if ((a.cm_out || a.cv_out || a.J_out) && !p.costs_to_caller) {
+        rc = launch_traj_cost(h, a, a.cm_out, a.cv_out, a.J_out, s);
+        if (rc) return rc;
     }
+    h->last_rollout_path = p.path;
+    h->last_cluster = p.cluster;
     return GPMPC_OK;
+}
+
+int launch_rollout(Handle* h, RolloutArgs& a, hipStream_t s) {
+    int rc = ensure_rollout_tables(h, a.N, a.D);
+    if (rc) return rc;
+    RolloutPlan p;
+    // a slice of a population (RolloutArgs::B_plan) is planned like the population
+    rc = plan_rollout(*h, a.N, a.D, a.A, a.E, a.H, a.B_plan > a.B ? a.B_plan : a.B, RolloutRequest{false, false}, p);
+    if (rc) { h->err = p.err; return rc; }
+    return launch_rollout(h, a, p, s);
 }
 
 }  // namespace gpmpc_hip

@@ -23,8 +23,8 @@ static int launch_variant(Handle* h, RolloutArgs& a, bool global_scratch, size_t
     // The compile-time-D instantiation folds the index arithmetic.  For D >= 4 it spills (8 / 22 / 247 / 1000 VGPRs at
     // D = 4 / 6 / 8 / 16 against none with the runtime D) but only in the small algebra outside the pairwise loop, and it
     // still measured faster or equal at every D (tools/gpu_exact_ab.py: 19.1 vs 19.8 ms at config 4, 5.1 vs 6.0 ms at
-    // D = 6, 14.2 vs 15.6 ms at D = 8, equal at D = 16), so it is used whenever D == DP; option "exact_dim" = 2 forbids it.
-    const bool exact = (a.D == DP) && a.exact_dim != 2;
+    // D = 6, 14.2 vs 15.6 ms at D = 8, equal at D = 16), so it is used whenever D == DP.
+    const bool exact = a.D == DP;
     if constexpr (DP <= 4 && NT == 1024) {
         if (a.tiled) {
             // one horizon step of the per-candidate part of the batch-major path (diagonal pairs: pair_tile_kernel.h)

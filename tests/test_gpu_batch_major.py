@@ -89,7 +89,9 @@ def test_batch_major_path_against_oracle_and_fused_kernel(engine, N, D, A, H, B,
     assert np.max(np.abs(t_out["Sig"] - t_out["Sig"].transpose(0, 1, 3, 2))) == 0.0
 
 
-def test_batch_major_path_is_reproducible_and_independent_of_the_batch(engine):
+def test_batch_major_path_is_reproducible_and_independent_of_the_batch_and_its_split(engine):
+    """The same candidates give the same bits in any batch and under any split of the batch over the tile kernel's workgroups
+    (the split follows from the batch size: tile_chunk in pair_tile.hip)."""
     w = synth.make_workload(300, 4, 2, 3, 40, seed=5, s0=1e-5)
     engine.prepare(w.X, w.Y, w.lengthscales, w.outputscales, w.noises)
     engine.set_cost(w.target, w.W, w.W_T, w.kappa)
@@ -100,8 +102,13 @@ def test_batch_major_path_is_reproducible_and_independent_of_the_batch(engine):
     sub, _ = _rollout(engine, w, 1)
     assert np.array_equal(full["Sig"][3:20], sub["Sig"]) and np.array_equal(full["mu"][3:20], sub["mu"])
     assert np.array_equal(full["J"][3:20], sub["J"])
-    other_chunk, _ = _rollout(engine, w, 1, tile_chunk=6)           # another split of the candidates over workgroups
-    assert np.array_equal(other_chunk["Sig"], sub["Sig"])
+    # another split of the candidates over workgroups: 24 copies of the slice, 408 candidates, take chunks of 20 (16 up to
+    # B = 40), so the copies straddle the workgroups' boundaries
+    w.actions = np.tile(w.actions, (24, 1, 1))
+    other_chunk, _ = _rollout(engine, w, 1)
+    assert np.array_equal(other_chunk["Sig"], np.tile(sub["Sig"], (24, 1, 1, 1)))
+    assert np.array_equal(other_chunk["mu"], np.tile(sub["mu"], (24, 1, 1)))
+    assert np.array_equal(other_chunk["J"], np.tile(sub["J"], 24))
 
 
 def test_mixed_batch_hands_some_candidates_to_the_element_wise_kernel(engine):

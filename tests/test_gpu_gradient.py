@@ -151,10 +151,11 @@ def test_large_input_variance_gradient(engine):
 
 
 def test_removed_ab_options_are_rejected(engine):
-    """The moment pass's two-columns-per-lane form and the run-time-D switch lost their A/Bs in round 3 and are no longer built:
-    their option names are unknown to the boundary (GPMPC_ERR_ARG), not silently accepted."""
+    """The moment pass's two-columns-per-lane form and the run-time-D switch lost their A/Bs in round 3 and are no longer built,
+    and the measurement-only switches of the batch-major path and the gradient's launches are retired: their option names are
+    unknown to the boundary (GPMPC_ERR_ARG), not silently accepted."""
     import gp_mpc_amd
-    for name in ("grad_cols_per_lane", "exact_dim"):
+    for name in ("grad_cols_per_lane", "exact_dim", "tile_overlap", "grad_merge", "grad_fuse", "tile_chunk"):
         with pytest.raises(gp_mpc_amd.GpmpcError):
             engine.set_option(name, 2)
 

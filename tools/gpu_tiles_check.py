@@ -88,15 +88,4 @@ if "time" in modes or "c4" in modes:
         dj = rel(res[1][1], res[2][1])
         print(f"{name} N={N} D={D} H={H} B={B}: fused {res[2][0]:.2f} ms (path {res[2][2]}), tiled {res[1][0]:.2f} ms (path {res[1][2]}) "
               f"= {B / res[1][0] * 1e3:.0f} rollouts/s; |dJ| {dj:.1e}", flush=True)
-    for cch in (() if "c4" in modes else (32, 64, 96, 128)):
-        w = synth.named("c4", B=2048)
-        eng.prepare(w.X, w.Y, w.lengthscales, w.outputscales, w.noises)
-        eng.set_cost(w.target, w.W, w.W_T, w.kappa)
-        eng.set_option("pair_tiles", 1)
-        eng.set_option("tile_chunk", cch)
-        eng.rollout_timed(w.actions, w.mu0, w.S0, 1)
-        ms, J = eng.rollout_timed(w.actions, w.mu0, w.S0, 3)
-        print(f"c4 tiled, tile_chunk={cch}: {ms:.2f} ms", flush=True)
-        eng.set_option("tile_chunk", 0)
-        eng.set_option("pair_tiles", 0)
 eng.close()

@@ -370,6 +370,59 @@ struct GradPlan {
     RolloutPlan fwd;
 };
 
+// ---------------------------------------------------------------------------------------
+// Launch forms of a full factorisation (prepare.hip: plan_prepare), from N, the handle's options and device limits alone.
+// Crossover of the single launch (prepare_small.hip) with the panel chain, measured (round 3, tools/gpu_prepare_bench.py; the LDS
+// arrays were sized by N for the test): N = 200: 0.217 vs 0.240 ms, 256: 0.344 vs 0.299, 300: 0.387 vs 0.337, 400: 0.84 vs 0.49,
+// 500: 1.15 vs 0.60 -- one CU's matrix cores do the N^3 / 3 of the panel updates, so the single launch loses once the chain's
+// launches fill more than a CU.
+constexpr int kSmallPathMaxN = 240;
+// One workgroup per GP is the right shape for the factorisation (a chain of 200 dependent pivots) but not for the N^3 products
+// after it: on one CU they are matrix-core-bound at ~50 k cycles each for N = 200.  From this size on only the factorisation stays
+// in the single launch (option "fused_prepare" = 2 forces everything into it, 3 never).
+constexpr int kSmallCholeskyMinN = 96;
+// 32-wide panel chain: L^-1 in one launch after the factorisation up to this size (measured: 0.286 -> 0.254 ms at N = 257,
+// 0.315 -> 0.297 at 300, 0.404 vs 0.420 at 400, slower from 500 on) -- or, with option "prepare_invcols" = 2, up to 544 points
+// (17 row blocks of the block column in LDS)
+constexpr int kInvColsMaxN = 352;
+constexpr int kInvColsWideMaxN = 544;
+// Y^T Y by the LDS-tiled kernel (64 x 64 tiles) from this size on, the 32 x 32 one below it
+constexpr int kSyrkTiledMinN = 512;
+// All GPs per Gram tile, squared differences shared (gram_lower_kernel), once its one-workgroup-per-tile grid fills the chip
+// (measured, profiles/r06_gram_ab.txt: N = 4096, D = 16: 985 -> 264 us = 4.1 TB/s of stores; N = 1000, D = 4 (136 tiles):
+// 15.0 -> 17.4 us, hence a rule on the tile count): from this many tiles per CU on
+constexpr int kGramSharedTilesPerCu = 2;
+
+enum class PreparePath {
+    small_whole,               // everything in one launch (prepare_small.hip)
+    small_cholesky,            // the factorisation and L^-1 by prepare_small.hip, then the tail of prepare.hip
+    panel32,                   // the 32-wide panel chain
+    outer,                     // outer panels of 128 columns (N >= option "outer_min_n")
+};
+enum class GramForm { full, lower, shared_lower };                 // per-GP full matrix, per-GP lower triangle, all GPs per tile
+enum class Inv32Form { rows, cols, side };      // L^-1 of the 32-wide chain: a row block inline per step, one column-block
+                                                // launch after the factorisation, or row batches on the side stream
+enum class OuterInvForm { rows128, doubling, doubling_ykk };       // 128-row blocks; recursive doubling (after a separate Y_KK step)
+enum class SyrkInvForm { w32, tiled, t128 };                       // Y^T Y: 32 x 32, 64 x 64 or 128 x 128 tiles
+struct PreparePlan {
+    PreparePath path;
+    GramForm gram;
+    // 32-wide chain (panel32, and the inner steps of outer panels without block128)
+    bool round2;               // round-2 panel kernels (option "outer_block" = 0: the round-1 ones)
+    bool fuse_next;            // trailing update fused with the next diagonal block's factorisation (panel32)
+    Inv32Form inv32;           // (panel32)
+    int inv_batch;             // row blocks per side-stream launch
+    // outer panels
+    bool tile128;              // 128 x 128 tiles for the tiled products (also decides the beta form, see beta_partial)
+    bool block128;             // a whole outer panel in two launches
+    bool inner_left;           // left-looking 32-column steps inside an outer panel (else right-looking)
+    int outer2;                // binary outer levels of the trailing update, up to 128 * 2^outer2 columns
+    OuterInvForm outer_inv;
+    // tail
+    bool beta_partial;         // beta by column-chunk partials + a reduction
+    SyrkInvForm syrk;
+};
+
 // rollout.hip
 int ensure_rollout_tables(Handle* h, int N, int D);      // what the plan reads: monomial tables, the batch-major path's bands
 int plan_rollout(const Handle& h, int N, int D, int A, int E, int H, int Bp, const RolloutRequest& req, RolloutPlan& p);
@@ -401,9 +454,10 @@ int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStr
                              const RolloutSeeds* seeds = nullptr);
 int launch_argmin_to(Handle* h, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
                      hipStream_t s);
-// prepare.hip
+// prepare.hip (allow_reuse = false: a full factorisation even where the cached factors could be reused or border-updated)
+void plan_prepare(const Handle& h, int N, PreparePlan& p);
 int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, const double* os,
-                const double* noise, int N, int D, int E, hipStream_t s);
+                const double* noise, int N, int D, int E, hipStream_t s, bool allow_reuse = true);
 int run_set_factors(Handle* h, const double* X, const double* iK, const double* beta,
                     const double* ls, const double* os, int N, int D, int E, hipStream_t s);
 int ensure_model_buffers(Handle* h, int N, int D, int E, bool need_factor_ws);
@@ -427,8 +481,8 @@ int run_cem_local(Handle* h, RolloutArgs& a, int B_total, int b0, int it, int n_
                   const double* first_host, int mapper, const double* max_change_host, const double* a_prev_host,
                   const double* noise_dev, const double* state_dev, double* elites_out_dev, hipStream_t s);
 int run_cem_merge(Handle* h, const double* elites_dev, int lists, int n_elite, int n, int it, double* state_dev, hipStream_t s);
-// prepare_small.hip: 1 = handled (N <= 256), 0 = not applicable, < 0 = error
-int run_prepare_small(Handle* h, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
-                      int N, int D, int E, hipStream_t s);
+// prepare_small.hip: the single-launch paths of a plan (PreparePath::small_whole / small_cholesky)
+int launch_prepare_small(Handle* h, const PreparePlan& pp, const double* X, const double* Y, const double* ls, const double* os,
+                         const double* noise, int N, int D, int E, hipStream_t s);
 
 }  // namespace gpmpc_hip

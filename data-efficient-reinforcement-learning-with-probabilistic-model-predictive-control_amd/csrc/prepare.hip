@@ -1142,7 +1142,6 @@ static int pack_and_record(Handle* h, const double* X, const double* Y, const do
     hipLaunchKernelGGL(pack_record_kernel, dim3(nb), dim3(256), 0, s, X, Y, ls, os, noise, N, D, E, h->Xt.p, h->ils2.p, h->var.p,
                        h->logvar.p, h->xrange.p, h->Xc.p, h->Yc.p, h->hyp.p);
     GPMPC_HIP_CHECK(h, hipGetLastError());
-    h->have_state = true;
     return GPMPC_OK;
 }
 
@@ -1349,92 +1348,73 @@ static int try_incremental(Handle* h, const double* X, const double* Y, const do
     return 1;
 }
 
-int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, const double* os,
-                const double* noise, int N, int D, int E, hipStream_t s) {
-    h->last_prepare_mode = 0;
-    int rc = try_incremental(h, X, Y, ls, os, noise, N, D, E, s);
-    if (rc != 0) return rc < 0 ? rc : GPMPC_OK;
-    rc = ensure_model_buffers(h, N, D, E, true);
-    if (rc) return rc;
-    h->ready = false;
-    h->have_state = false;
-    // small memories: one launch, one workgroup per GP (prepare_small.hip) -- everything, or (rc == 2) the factorisation only
-    rc = run_prepare_small(h, X, Y, ls, os, noise, N, D, E, s);
-    if (rc < 0) return rc;
-    if (rc == 1) {
-        if ((rc = check_info(h, D, s))) return rc;
-        h->have_state = true;                    // the kernel recorded (X, Y, hyper-parameters)
-        h->inc_updates = 0;
-        h->N = N; h->D = D; h->E = E; h->ready = true;
-        return GPMPC_OK;
-    }
-    const bool factored = (rc == 2);
-    if (!factored) {
-        if ((rc = pack_and_record(h, X, Y, ls, os, noise, N, D, E, s))) return rc;
-        h->have_state = false;                   // valid only once the factorisation has succeeded
-        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->linv.p, 0, (size_t)D * N * N * sizeof(double), s));
-    }
-    if (!factored) GPMPC_HIP_CHECK(h, hipMemsetAsync(h->Tm.p, 0, (size_t)D * (N + kTPadRows) * N * sizeof(double), s));
-    if (!factored) {
+// Every kernel-form choice of a full factorisation: no HIP call, nothing written to the handle
+void plan_prepare(const Handle& h, int N, PreparePlan& p) {
+    p = PreparePlan{};
+    const bool outer = N >= h.opt_outer_min_n && h.opt_outer_block != 0;
+    // the 128 x 128 tiled kernels address a GP's matrix with 32-bit byte offsets (buffer loads): N^2 * 8 < 4 GiB, N <= 23170;
+    // beyond that the 64 x 64 kernels with 64-bit addresses run
+    p.tile128 = h.opt_tile128 != 0 && (size_t)N * N * sizeof(double) < 0xFFFFFFFFull;
+    // (option "outer_min_n" is at least 256: the single launch never meets an outer-panel form)
+    if (N <= kSmallPathMaxN && h.opt_fused_prepare != 0)
+        p.path = (h.opt_fused_prepare == 3 || (h.opt_fused_prepare != 2 && N >= kSmallCholeskyMinN)) ? PreparePath::small_cholesky
+                                                                                                      : PreparePath::small_whole;
+    else
+        p.path = outer ? PreparePath::outer : PreparePath::panel32;
+    // "gram_shared" 0: the per-GP kernel always, 2: the shared one whenever the outer panels run (A/B)
+    const int nt = (N + 63) / 64;
+    const bool shared = h.opt_gram_shared == 2 || (h.opt_gram_shared == 1 && nt * (nt + 1) / 2 >= kGramSharedTilesPerCu * h.num_cu);
+    p.gram = !outer ? GramForm::full : shared ? GramForm::shared_lower : GramForm::lower;
+    p.round2 = h.opt_outer_block != 0;
+    p.fuse_next = p.round2 && !outer && h.opt_prepare_fuse != 0;
+    if (p.path == PreparePath::panel32 && p.round2 && h.opt_prepare_invcols != 0 && N > NB &&
+        N <= (h.opt_prepare_invcols == 2 ? kInvColsWideMaxN : kInvColsMaxN))
+        p.inv32 = Inv32Form::cols;
+    else if (p.path == PreparePath::panel32 && h.opt_prepare_overlap != 0 && N > NB)
+        p.inv32 = Inv32Form::side;
+    else
+        p.inv32 = Inv32Form::rows;
+    p.inv_batch = !p.round2 ? 1 : h.opt_prepare_inv_batch < 1 ? 1 : (h.opt_prepare_inv_batch > kInvBatchMax ? kInvBatchMax : h.opt_prepare_inv_batch);
+    p.block128 = p.tile128 && h.opt_block128 != 0;
+    p.inner_left = h.opt_inner_left != 0;
+    p.outer2 = h.opt_outer2 < 0 ? 0 : (h.opt_outer2 > 4 ? 4 : h.opt_outer2);
+    p.outer_inv = !p.tile128 ? OuterInvForm::rows128 : p.block128 ? OuterInvForm::doubling : OuterInvForm::doubling_ykk;
+    // the 128-tile forms of the tail follow N and tile128, not the path: beta's also runs with the 32-wide chain (outer_block = 0)
+    p.beta_partial = N >= h.opt_outer_min_n && p.tile128;
+    p.syrk = outer && p.tile128 ? SyrkInvForm::t128 : (N >= kSyrkTiledMinN && p.round2) ? SyrkInvForm::tiled : SyrkInvForm::w32;
+}
+
+// K + noise I of all GPs: the full matrices, or the lower triangles the outer panels read
+static int launch_gram(Handle* h, const PreparePlan& p, const double* noise, int N, int D, int E, hipStream_t s) {
+    if (p.gram == GramForm::shared_lower) {
+        const int nt = (N + 63) / 64;
+        const dim3 gl(nt * (nt + 1) / 2);
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, gl, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, D, h->gram.p); };
+        if (E <= 4) go(gram_lower_kernel<4>);
+        else if (E <= 8) go(gram_lower_kernel<8>);
+        else if (E <= 12) go(gram_lower_kernel<12>);
+        else if (E <= 16) go(gram_lower_kernel<16>);
+        else if (E <= 20) go(gram_lower_kernel<20>);
+        else go(gram_lower_kernel<24>);
+    } else {
         const dim3 grid((N + 63) / 64, (N + 63) / 64, D);
-        const int lower = (N >= h->opt_outer_min_n && h->opt_outer_block != 0) ? 1 : 0;
-        const int nt_l = (N + 63) / 64;
-        // all GPs per tile, squared differences shared (gram_lower_kernel), once its one-workgroup-per-tile grid fills the chip
-        // (measured, profiles/r06_gram_ab.txt: N = 4096, D = 16: 985 -> 264 us = 4.1 TB/s of stores; N = 1000, D = 4 (136 tiles):
-        // 15.0 -> 17.4 us, hence the tile-count rule); "gram_shared" 0: the per-GP kernel always, 2: the shared one whenever lower (A/B)
-        if (lower && (h->opt_gram_shared == 2 || (h->opt_gram_shared == 1 && nt_l * (nt_l + 1) / 2 >= 2 * h->num_cu))) {
-            const int nt = nt_l;
-            const dim3 gl(nt * (nt + 1) / 2);
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, gl, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, D, h->gram.p); };
-            if (E <= 4) go(gram_lower_kernel<4>);
-            else if (E <= 8) go(gram_lower_kernel<8>);
-            else if (E <= 12) go(gram_lower_kernel<12>);
-            else if (E <= 16) go(gram_lower_kernel<16>);
-            else if (E <= 20) go(gram_lower_kernel<20>);
-            else go(gram_lower_kernel<24>);
-        }
-        else if (E <= 4) hipLaunchKernelGGL(gram_kernel<4>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, h->gram.p, lower);
+        const int lower = p.gram == GramForm::lower ? 1 : 0;
+        if (E <= 4) hipLaunchKernelGGL(gram_kernel<4>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, h->gram.p, lower);
         else if (E <= 8) hipLaunchKernelGGL(gram_kernel<8>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, h->gram.p, lower);
         else if (E <= 16) hipLaunchKernelGGL(gram_kernel<16>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, h->gram.p, lower);
         else hipLaunchKernelGGL(gram_kernel<24>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, noise, N, E, h->gram.p, lower);
-        GPMPC_HIP_CHECK(h, hipGetLastError());
     }
-    // Outer blocking (large N): the rank-32 trailing update touches the whole trailing matrix per panel -- 32 multiply-adds
-    // per 16 bytes read and written, HBM-bound at N = 4096.  With outer panels of 128 columns the 32-wide steps only update
-    // the strip inside the outer panel and one LDS-tiled rank-128 product per outer panel does the rest.
-    const int OW = (N >= h->opt_outer_min_n && h->opt_outer_block != 0) ? 128 : 0;
-    // the 128 x 128 tiled kernels address a GP's matrix with 32-bit byte offsets (buffer loads): N^2 * 8 < 4 GiB, N <= 23170;
-    // beyond that the 64 x 64 kernels with 64-bit addresses run
-    const bool tile128 = h->opt_tile128 != 0 && (size_t)N * N * sizeof(double) < 0xFFFFFFFFull;
-    // trailing update after the outer panel that ends at column cend (128 x 128 tiles, binary outer levels)
-    auto outer_update = [&](int cend) -> int {
-        // Binary outer levels: after m = cend / 128 outer panels, with 2^t the largest power of two dividing m
-        // (t <= tmax), the last 2^t panels update the next 2^t tile columns in one product (k = 128 * 2^t) -- or,
-        // at t = tmax, everything to the right.  Every element of the trailing matrix is then read and written
-        // once per 128 * 2^tmax columns instead of once per 128 (the update is bound by that traffic).
-        const int nto = (N - cend + T2 - 1) / T2;
-        const int tmax = h->opt_outer2 < 0 ? 0 : (h->opt_outer2 > 4 ? 4 : h->opt_outer2);
-        const int m = cend / OW;
-        int t = 0;
-        while (t < tmax && (m & ((2 << t) - 1)) == 0) ++t;
-        int nct = (t == tmax) ? nto : (1 << t);
-        if (nct > nto) nct = nto;
-        const int ntile = nct * nto - nct * (nct - 1) / 2;
-        const int wk = OW << t;
-        hipLaunchKernelGGL(syrk_outer_t128_kernel, dim3(ntile * D), dim3(512), 0, s, h->gram.p, N, D, ntile,
-                           cend - wk, wk, nto);
-        GPMPC_HIP_CHECK(h, hipGetLastError());
-        return GPMPC_OK;
-    };
-    // 32-wide panel path (256 < N < outer_min_n): row block k of Y = L^-1 needs rows <= k of L and the earlier rows of Y only --
-    // not the panel solve and trailing update of step k -- so the inverse's chain of launches runs on a side stream BESIDE the
-    // factorisation's (one event per step; every kernel here fills a few CUs).  N = 500: the factorisation chain is 16 x
-    // (8.9 + 4.7 + 5.0) us, the inverse chain 15 x 14.3 us (profiles/r04_c3_kernel_trace_stats.txt); in sequence 0.59 ms.
-    // ... or, up to 544 points (17 row blocks of the block column in LDS), the whole inverse as ONE launch after the factorisation
-    const bool inv_cols = !OW && !factored && h->opt_outer_block != 0 && h->opt_prepare_invcols != 0 && N > NB &&
-                          N <= (h->opt_prepare_invcols == 2 ? 544 : 352);       // measured: 0.286 -> 0.254 ms at N = 257, 0.315 -> 0.297 at 300, 0.404 vs 0.420 at 400, slower from 500 on
-    const bool overlap_inv = !OW && !factored && !inv_cols && h->opt_prepare_overlap != 0 && N > NB;
-    if (overlap_inv && !h->side_stream) {
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    return GPMPC_OK;
+}
+
+// 32-wide panel chain and L^-1 by one of its three forms.  Row block k of Y = L^-1 needs rows <= k of L and the earlier rows of
+// Y only -- not the panel solve and trailing update of step k -- so with Inv32Form::side the inverse's chain of launches runs on
+// a side stream BESIDE the factorisation's (one event per step; every kernel here fills a few CUs).  N = 500: the factorisation
+// chain is 16 x (8.9 + 4.7 + 5.0) us, the inverse chain 15 x 14.3 us (profiles/r04_c3_kernel_trace_stats.txt); in sequence 0.59 ms.
+static int factor_panel32(Handle* h, const PreparePlan& p, int N, int D, hipStream_t s) {
+    const bool side = p.inv32 == Inv32Form::side;
+    if (side && !h->side_stream) {
         GPMPC_HIP_CHECK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
         GPMPC_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_params, hipEventDisableTiming));
         GPMPC_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_points, hipEventDisableTiming));
@@ -1442,129 +1422,119 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
     int inv_rows_done = 1;                                // row blocks [1, inv_rows_done) of L^-1 are launched (block 0 is its diagonal block)
     for (int k0 = 0; k0 < N; k0 += NB) {
         const int nb = (N - k0 < NB) ? (N - k0) : NB;
-        const bool blk128 = OW && tile128 && h->opt_block128 != 0;
-        if (!factored && blk128) {
-            // whole outer panel: block factorisation (+ its inverse) and the solve of the rows below, two launches
-            if (k0 % OW == 0) {
-                const void* kern = reinterpret_cast<const void*>(potrf_block128_kernel);
-                if ((rc = allow_full_lds(h, kern))) return rc;
-                const size_t lds = (size_t)(T2 * kPS + NB * 33 + 4 * NB + NB) * sizeof(double);
-                hipLaunchKernelGGL(potrf_block128_kernel, dim3(D), dim3(1024), lds, s, h->gram.p, h->linv.p, N, k0, h->info);
-                const int cend = k0 + OW;
-                if (cend < N) {
-                    const int nrow = (N - cend + T2 - 1) / T2;
-                    hipLaunchKernelGGL(trsm_outer_t128_kernel, dim3(nrow * D), dim3(512), 0, s, h->gram.p, h->linv.p, N, D,
-                                       nrow, k0, OW);
-                    if ((rc = outer_update(cend))) return rc;
-                }
-            }
-        } else if (!factored) {
-            const bool fast = h->opt_outer_block != 0;           // round-2 panel kernels (option "outer_block" = 0: the round-1 ones)
-            // inside an outer panel the 32-column panels are factorised left-looking (option "inner_left" = 0: right-looking
-            // with a rank-32 update of the rest of the outer panel per step)
-            const bool ll = OW && h->opt_inner_left != 0;
-            const int left = ll ? k0 % OW : 0;
-            // 32-wide path: from the second panel on the diagonal block was factorised by the previous panel's fused trailing update
-            const bool fuse_next = fast && !OW && h->opt_prepare_fuse != 0;
-            if (fuse_next && k0 > 0) { /* done by syrk_trailing_potrf_kernel of the panel before */ }
-            else if (fast) hipLaunchKernelGGL(potrf_diag_fast_kernel, dim3(D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info, left);
-            else hipLaunchKernelGGL(potrf_diag_kernel, dim3(D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info);
-            if (overlap_inv && k0 > 0) {
-                // rows <= k of L and Y_kk are final: row block k of the inverse can start now, beside this step's solve and update --
-                // in batches of `prepare_inv_batch` row blocks per launch (1: a launch per row block, the round-4 form)
-                const int kp = k0 / NB, last = (N + NB - 1) / NB - 1;
-                int batch = h->opt_prepare_inv_batch < 1 ? 1 : (h->opt_prepare_inv_batch > kInvBatchMax ? kInvBatchMax : h->opt_prepare_inv_batch);
-                if (!fast) batch = 1;
-                if (batch == 1) {
-                    GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_params, s));
-                    GPMPC_HIP_CHECK(h, hipStreamWaitEvent(h->side_stream, h->ev_params, 0));
-                    hipLaunchKernelGGL(trinv_row_kernel, dim3((k0 + 31) / 32, D), dim3(256), 0, h->side_stream, h->gram.p, h->linv.p, N, k0, nb, 0, 0, 0);
-                } else if (kp - inv_rows_done + 1 >= batch || kp == last) {
-                    GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_params, s));
-                    GPMPC_HIP_CHECK(h, hipStreamWaitEvent(h->side_stream, h->ev_params, 0));
-                    hipLaunchKernelGGL(trinv_rows_batch_kernel, dim3(kp, D), dim3(256), 0, h->side_stream, h->gram.p, h->linv.p, N, inv_rows_done, kp + 1);
-                    inv_rows_done = kp + 1;
-                }
-            }
-            const int M = N - k0 - nb;
-            if (M > 0) {
-                if (fast && left > 0) hipLaunchKernelGGL(trsm_panel_ll_kernel, dim3((M + 63) / 64, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb, left);
-                else if (fast) hipLaunchKernelGGL(trsm_panel_mfma_kernel, dim3((M + 63) / 64, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb);
-                else hipLaunchKernelGGL(trsm_panel_kernel, dim3((M + 255) / 256, D), dim3(256), 0, s, h->gram.p, N, k0, nb);
-                int cend = N;
-                if (OW) { cend = (k0 / OW + 1) * OW; if (cend > N) cend = N; }
-                const int nt = (M + 31) / 32;
-                const int ntx = (cend - (k0 + nb) + 31) / 32;
-                if (ntx > 0 && !ll) {
-                    if (fuse_next) hipLaunchKernelGGL(syrk_trailing_potrf_kernel, dim3(nt, nt, D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info);
-                    else hipLaunchKernelGGL(syrk_trailing_kernel, dim3(ntx < nt ? ntx : nt, nt, D), dim3(256), 0, s, h->gram.p, N, k0, nb, cend);
-                }
-                if (OW && k0 + nb == cend && cend < N) {             // outer panel [cend - OW, cend) complete: rank-OW update of the rest
-                    if (tile128) {
-                        if ((rc = outer_update(cend))) return rc;
-                    } else {
-                        const int nto = (N - cend + TS - 1) / TS;
-                        hipLaunchKernelGGL(syrk_outer_kernel, dim3(nto, nto, D), dim3(256), 0, s, h->gram.p, N, cend - OW, OW);
-                    }
-                }
+        if (p.fuse_next && k0 > 0) { /* factorised by syrk_trailing_potrf_kernel of the panel before */ }
+        else if (p.round2) hipLaunchKernelGGL(potrf_diag_fast_kernel, dim3(D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info, 0);
+        else hipLaunchKernelGGL(potrf_diag_kernel, dim3(D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info);
+        if (side && k0 > 0) {
+            // rows <= k of L and Y_kk are final: row block k of the inverse can start now, beside this step's solve and update --
+            // in batches of `inv_batch` row blocks per launch (1: a launch per row block, the round-4 form)
+            const int kp = k0 / NB, last = (N + NB - 1) / NB - 1;
+            if (p.inv_batch == 1) {
+                GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_params, s));
+                GPMPC_HIP_CHECK(h, hipStreamWaitEvent(h->side_stream, h->ev_params, 0));
+                hipLaunchKernelGGL(trinv_row_kernel, dim3((k0 + 31) / 32, D), dim3(256), 0, h->side_stream, h->gram.p, h->linv.p, N, k0, nb, 0, 0, 0);
+            } else if (kp - inv_rows_done + 1 >= p.inv_batch || kp == last) {
+                GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_params, s));
+                GPMPC_HIP_CHECK(h, hipStreamWaitEvent(h->side_stream, h->ev_params, 0));
+                hipLaunchKernelGGL(trinv_rows_batch_kernel, dim3(kp, D), dim3(256), 0, h->side_stream, h->gram.p, h->linv.p, N, inv_rows_done, kp + 1);
+                inv_rows_done = kp + 1;
             }
         }
-        if (k0 > 0 && !OW && !factored && !overlap_inv && !inv_cols) {
+        const int M = N - k0 - nb;
+        if (M > 0) {
+            const int nt = (M + 31) / 32;
+            if (p.round2) hipLaunchKernelGGL(trsm_panel_mfma_kernel, dim3((M + 63) / 64, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb);
+            else hipLaunchKernelGGL(trsm_panel_kernel, dim3((M + 255) / 256, D), dim3(256), 0, s, h->gram.p, N, k0, nb);
+            if (p.fuse_next) hipLaunchKernelGGL(syrk_trailing_potrf_kernel, dim3(nt, nt, D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info);
+            else hipLaunchKernelGGL(syrk_trailing_kernel, dim3(nt, nt, D), dim3(256), 0, s, h->gram.p, N, k0, nb, N);
+        }
+        if (p.inv32 == Inv32Form::rows && k0 > 0)
             hipLaunchKernelGGL(trinv_row_kernel, dim3((k0 + 31) / 32, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb, 0, 0, 0);
-        }
     }
-    if (inv_cols) {
+    if (p.inv32 == Inv32Form::cols) {
         const void* kern = reinterpret_cast<const void*>(trinv_colblock_kernel);
-        if ((rc = allow_full_lds(h, kern))) return rc;
+        int rc = allow_full_lds(h, kern);
+        if (rc) return rc;
         const int nblk = (N + NB - 1) / NB;
         const size_t lds = (size_t)(2 * 32 * 33 + (size_t)nblk * 32 * 32) * sizeof(double);
         hipLaunchKernelGGL(trinv_colblock_kernel, dim3(nblk, D), dim3(256), lds, s, h->gram.p, h->linv.p, N);
     }
-    if (overlap_inv) {                                    // join: what follows reads all of Y
+    if (side) {                                           // join: what follows reads all of Y
         GPMPC_HIP_CHECK(h, hipEventRecord(h->ev_points, h->side_stream));
         GPMPC_HIP_CHECK(h, hipStreamWaitEvent(s, h->ev_points, 0));
     }
-    if (OW && tile128) {
-        // Y = L^-1 by recursive doubling.  All diagonal 128-blocks Y_KK at once (the 32-row recursion restricted to the columns
-        // of the block: 3 launches), then for b = 128, 256, ...: every pair of adjacent b-blocks [[Y11, 0], [Y21, Y22]] gets
-        // Y21 = -Y22 (L21 Y11) from two batched tiled products (scratch W = L21 Y11: the iK buffer, written later).  5 levels
-        // at N = 4096, every launch >= 256 workgroups, instead of 31 dependent steps whose first ones fill a few CUs.
-        const size_t NN = (size_t)N * N;
-        const int nblk = (N + OW - 1) / OW;
-        for (int koff = NB; koff < OW && h->opt_block128 == 0; koff += NB)      // (potrf_block128_kernel leaves Y_KK behind)
-            hipLaunchKernelGGL(trinv_row_kernel, dim3((koff + 31) / 32, D, nblk), dim3(256), 0, s, h->gram.p, h->linv.p, N, 0, 0, 0, OW, koff);
-        for (int b = OW; b < N; b *= 2) {
-            const int nq = (N - b + 2 * b - 1) / (2 * b);              // pairs q with (2q + 1) b < N
-            const int lastrows = N - (2 * (nq - 1) + 1) * b;
-            GemmBatch g;
-            g.lda = g.ldb = g.ldc = N;
-            g.sa = g.sb = g.sc = NN;
-            g.qa = g.qb = g.qc = (size_t)2 * b * ((size_t)N + 1);
-            g.nq = nq; g.nbatch = nq * D;
-            g.M = b; g.M_last = lastrows < b ? lastrows : b;
-            g.NC = b; g.Kd = b;
-            g.tiles_x = (b + T2 - 1) / T2;
-            g.tiles = g.tiles_x * ((b + T2 - 1) / T2);
-            const size_t off21 = (size_t)b * N;                        // block (1, 0) of a pair relative to its block (0, 0)
-            const size_t off22 = (size_t)b * N + b;
-            const dim3 grid(g.tiles * g.nbatch);
-            // W = L21 Y11
-            g.A = h->gram.p + off21; g.B = h->linv.p; g.C = h->iK.p + off21;
-            g.a_rem = NN - off21;
-            g.alpha = 1.0; g.kskip = 1; g.ktri = 0; g.kd_is_m = 0;
-            hipLaunchKernelGGL(gemm_nn_t128_kernel, grid, dim3(512), 0, s, g);
-            // Y21 = -Y22 W
-            g.A = h->linv.p + off22; g.B = h->iK.p + off21; g.C = h->linv.p + off21;
-            g.a_rem = NN - off22;
-            g.alpha = -1.0; g.kskip = 0; g.ktri = 1; g.kd_is_m = 1;
-            hipLaunchKernelGGL(gemm_nn_t128_kernel, grid, dim3(512), 0, s, g);
+    return GPMPC_OK;
+}
+
+constexpr int kOW = 128;                                  // outer panel width
+
+// Trailing update after the outer panel that ends at column cend (128 x 128 tiles).  Binary outer levels: after m = cend / 128
+// outer panels, with 2^t the largest power of two dividing m (t <= outer2), the last 2^t panels update the next 2^t tile
+// columns in one product (k = 128 * 2^t) -- or, at t = outer2, everything to the right.  Every element of the trailing matrix
+// is then read and written once per 128 * 2^outer2 columns instead of once per 128 (the update is bound by that traffic).
+static int outer_update(Handle* h, const PreparePlan& p, int N, int D, int cend, hipStream_t s) {
+    const int nto = (N - cend + T2 - 1) / T2;
+    const int m = cend / kOW;
+    int t = 0;
+    while (t < p.outer2 && (m & ((2 << t) - 1)) == 0) ++t;
+    int nct = (t == p.outer2) ? nto : (1 << t);
+    if (nct > nto) nct = nto;
+    const int ntile = nct * nto - nct * (nct - 1) / 2;
+    const int wk = kOW << t;
+    hipLaunchKernelGGL(syrk_outer_t128_kernel, dim3(ntile * D), dim3(512), 0, s, h->gram.p, N, D, ntile, cend - wk, wk, nto);
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    return GPMPC_OK;
+}
+
+// Outer panels (large N): the rank-32 trailing update touches the whole trailing matrix per panel -- 32 multiply-adds per 16
+// bytes read and written, HBM-bound at N = 4096.  With outer panels of 128 columns the 32-wide steps only update the strip
+// inside the outer panel and one LDS-tiled rank-128 product per outer panel does the rest.  Then L^-1 by 128-column blocks.
+static int factor_outer(Handle* h, const PreparePlan& p, int N, int D, hipStream_t s) {
+    int rc;
+    for (int K0 = 0; K0 < N; K0 += kOW) {
+        const int cend = (K0 + kOW < N) ? K0 + kOW : N;
+        if (p.block128) {
+            // whole outer panel: block factorisation (+ its inverse) and the solve of the rows below, two launches
+            const void* kern = reinterpret_cast<const void*>(potrf_block128_kernel);
+            if ((rc = allow_full_lds(h, kern))) return rc;
+            const size_t lds = (size_t)(T2 * kPS + NB * 33 + 4 * NB + NB) * sizeof(double);
+            hipLaunchKernelGGL(potrf_block128_kernel, dim3(D), dim3(1024), lds, s, h->gram.p, h->linv.p, N, K0, h->info);
+            if (cend < N) {
+                const int nrow = (N - cend + T2 - 1) / T2;
+                hipLaunchKernelGGL(trsm_outer_t128_kernel, dim3(nrow * D), dim3(512), 0, s, h->gram.p, h->linv.p, N, D, nrow, K0, kOW);
+                if ((rc = outer_update(h, p, N, D, cend, s))) return rc;
+            }
+            continue;
         }
-    } else if (OW) {
+        // 32-column panels inside the outer panel, left-looking (option "inner_left" = 0: right-looking with a rank-32 update of
+        // the rest of the outer panel per step)
+        for (int k0 = K0; k0 < cend; k0 += NB) {
+            const int nb = (N - k0 < NB) ? (N - k0) : NB;
+            const int left = p.inner_left ? k0 - K0 : 0;
+            hipLaunchKernelGGL(potrf_diag_fast_kernel, dim3(D), dim3(NB * NB), 0, s, h->gram.p, h->linv.p, N, k0, nb, h->info, left);
+            const int M = N - k0 - nb;
+            if (M == 0) break;
+            if (left > 0) hipLaunchKernelGGL(trsm_panel_ll_kernel, dim3((M + 63) / 64, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb, left);
+            else hipLaunchKernelGGL(trsm_panel_mfma_kernel, dim3((M + 63) / 64, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb);
+            const int nt = (M + 31) / 32, ntx = (cend - (k0 + nb) + 31) / 32;
+            if (ntx > 0 && !p.inner_left)
+                hipLaunchKernelGGL(syrk_trailing_kernel, dim3(ntx < nt ? ntx : nt, nt, D), dim3(256), 0, s, h->gram.p, N, k0, nb, cend);
+        }
+        if (cend < N) {                                   // outer panel [K0, cend) complete: rank-128 update of the rest
+            if (p.tile128) {
+                if ((rc = outer_update(h, p, N, D, cend, s))) return rc;
+            } else {
+                const int nto = (N - cend + TS - 1) / TS;
+                hipLaunchKernelGGL(syrk_outer_kernel, dim3(nto, nto, D), dim3(256), 0, s, h->gram.p, N, K0, kOW);
+            }
+        }
+    }
+    const size_t NN = (size_t)N * N;
+    if (p.outer_inv == OuterInvForm::rows128) {
         // Y = L^-1 by 128-row blocks: inside a block the 32-row recursion (columns of the block only) gives Y_KK; the part left
         // of the block is two tiled products, W = L[K, c:K] Y[c:K, c] (scratch: the iK buffer, written later) and Y[K, c] = -Y_KK W
-        const size_t NN = (size_t)N * N;
-        for (int K0 = 0; K0 < N; K0 += OW) {
-            const int mb = (N - K0 < OW) ? (N - K0) : OW;
+        for (int K0 = 0; K0 < N; K0 += kOW) {
+            const int mb = (N - K0 < kOW) ? (N - K0) : kOW;
             for (int k0 = K0 + NB; k0 < K0 + mb; k0 += NB) {
                 const int nb = (N - k0 < NB) ? (N - k0) : NB;
                 hipLaunchKernelGGL(trinv_row_kernel, dim3((k0 - K0 + 31) / 32, D), dim3(256), 0, s, h->gram.p, h->linv.p, N, k0, nb, K0, 0, 0);
@@ -1577,11 +1547,51 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
                                    h->iK.p + (size_t)K0 * N, N, NN, h->linv.p + (size_t)K0 * N, N, NN, mb, K0, mb, -1.0, 0, 1);
             }
         }
+        return GPMPC_OK;
     }
+    // Y = L^-1 by recursive doubling.  All diagonal 128-blocks Y_KK at once (the 32-row recursion restricted to the columns of
+    // the block: 3 launches; potrf_block128_kernel leaves them behind), then for b = 128, 256, ...: every pair of adjacent
+    // b-blocks [[Y11, 0], [Y21, Y22]] gets Y21 = -Y22 (L21 Y11) from two batched tiled products (scratch W = L21 Y11: the iK
+    // buffer, written later).  5 levels at N = 4096, every launch >= 256 workgroups, instead of 31 dependent steps whose first
+    // ones fill a few CUs.
+    const int nblk = (N + kOW - 1) / kOW;
+    for (int koff = NB; koff < kOW && p.outer_inv == OuterInvForm::doubling_ykk; koff += NB)
+        hipLaunchKernelGGL(trinv_row_kernel, dim3((koff + 31) / 32, D, nblk), dim3(256), 0, s, h->gram.p, h->linv.p, N, 0, 0, 0, kOW, koff);
+    for (int b = kOW; b < N; b *= 2) {
+        const int nq = (N - b + 2 * b - 1) / (2 * b);              // pairs q with (2q + 1) b < N
+        const int lastrows = N - (2 * (nq - 1) + 1) * b;
+        GemmBatch g;
+        g.lda = g.ldb = g.ldc = N;
+        g.sa = g.sb = g.sc = NN;
+        g.qa = g.qb = g.qc = (size_t)2 * b * ((size_t)N + 1);
+        g.nq = nq; g.nbatch = nq * D;
+        g.M = b; g.M_last = lastrows < b ? lastrows : b;
+        g.NC = b; g.Kd = b;
+        g.tiles_x = (b + T2 - 1) / T2;
+        g.tiles = g.tiles_x * ((b + T2 - 1) / T2);
+        const size_t off21 = (size_t)b * N;                        // block (1, 0) of a pair relative to its block (0, 0)
+        const size_t off22 = (size_t)b * N + b;
+        const dim3 grid(g.tiles * g.nbatch);
+        // W = L21 Y11
+        g.A = h->gram.p + off21; g.B = h->linv.p; g.C = h->iK.p + off21;
+        g.a_rem = NN - off21;
+        g.alpha = 1.0; g.kskip = 1; g.ktri = 0; g.kd_is_m = 0;
+        hipLaunchKernelGGL(gemm_nn_t128_kernel, grid, dim3(512), 0, s, g);
+        // Y21 = -Y22 W
+        g.A = h->linv.p + off22; g.B = h->iK.p + off21; g.C = h->linv.p + off21;
+        g.a_rem = NN - off22;
+        g.alpha = -1.0; g.kskip = 0; g.ktri = 1; g.kd_is_m = 1;
+        hipLaunchKernelGGL(gemm_nn_t128_kernel, grid, dim3(512), 0, s, g);
+    }
+    return GPMPC_OK;
+}
+
+// Every path but the single launch: z = Y y, beta = Y^T z, iK = Y^T Y and T from Y = L^-1
+static int launch_tail(Handle* h, const PreparePlan& p, const double* Y, int N, int D, hipStream_t s) {
     GPMPC_HIP_CHECK(h, hipGetLastError());
     hipLaunchKernelGGL(targets_by_gp_kernel, dim3((N * D + 255) / 256), dim3(256), 0, s, Y, N, D, h->vv.p);      // vv: border-update scratch, free here
     hipLaunchKernelGGL(zvec_kernel, dim3((N + 3) / 4, D), dim3(256), 0, s, h->linv.p, h->vv.p, N, h->zvec.p);
-    if (N >= h->opt_outer_min_n && tile128) {
+    if (p.beta_partial) {
         // partials in the iK buffer (written by the product that follows)
         const int nch = (N + 255) / 256;
         hipLaunchKernelGGL(beta_partial_kernel, dim3((N + 63) / 64, nch, D), dim3(256), 0, s, h->linv.p, h->zvec.p, N, h->iK.p);
@@ -1589,11 +1599,11 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
     } else {
         hipLaunchKernelGGL(beta_kernel, dim3((N + 63) / 64, D), dim3(256), 0, s, h->linv.p, h->zvec.p, N, h->beta.p);
     }
-    if (N >= h->opt_outer_min_n && h->opt_outer_block != 0 && tile128) {
+    if (p.syrk == SyrkInvForm::t128) {
         const int nt = (N + T2 - 1) / T2, ntile = nt * (nt + 1) / 2;
         hipLaunchKernelGGL(syrk_inverse_t128_kernel, dim3(ntile * D), dim3(512), 0, s, h->linv.p, h->beta.p, N, D, ntile,
                            h->iK.p, h->Tm.p);
-    } else if (N >= 512 && h->opt_outer_block != 0) {
+    } else if (p.syrk == SyrkInvForm::tiled) {
         const int nt = (N + TS - 1) / TS;
         hipLaunchKernelGGL(syrk_inverse_tiled_kernel, dim3(nt, nt, D), dim3(256), 0, s, h->linv.p, h->beta.p, N, h->iK.p, h->Tm.p);
     } else {
@@ -1601,19 +1611,46 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
         hipLaunchKernelGGL(syrk_inverse_kernel, dim3(nt, nt, D), dim3(256), 0, s, h->linv.p, h->beta.p, N, h->iK.p, h->Tm.p);
     }
     GPMPC_HIP_CHECK(h, hipGetLastError());
-    if ((rc = check_info(h, D, s))) return rc;
-    h->have_state = true;                         // (X, Y, hyper-parameters) were recorded by the first launch
+    return GPMPC_OK;
+}
+
+// the cached factors are complete, and (X, Y, hyper-parameters) were recorded with them
+static void commit_state(Handle* h, int N, int D, int E) {
+    h->have_state = true;
     h->inc_updates = 0;
     h->N = N; h->D = D; h->E = E; h->ready = true;
+}
+
+int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, const double* os,
+                const double* noise, int N, int D, int E, hipStream_t s, bool allow_reuse) {
+    h->last_prepare_mode = 0;
+    int rc = allow_reuse ? try_incremental(h, X, Y, ls, os, noise, N, D, E, s) : 0;
+    if (rc != 0) return rc < 0 ? rc : GPMPC_OK;
+    if ((rc = ensure_model_buffers(h, N, D, E, true))) return rc;
+    h->ready = false;
+    h->have_state = false;
+    PreparePlan p;
+    plan_prepare(*h, N, p);
+    if (p.path == PreparePath::small_whole || p.path == PreparePath::small_cholesky) {
+        rc = launch_prepare_small(h, p, X, Y, ls, os, noise, N, D, E, s);         // its kernel records the state and zeroes T
+    } else {
+        if ((rc = pack_and_record(h, X, Y, ls, os, noise, N, D, E, s))) return rc;
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->linv.p, 0, (size_t)D * N * N * sizeof(double), s));
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->Tm.p, 0, (size_t)D * (N + kTPadRows) * N * sizeof(double), s));
+        if ((rc = launch_gram(h, p, noise, N, D, E, s))) return rc;
+        rc = p.path == PreparePath::outer ? factor_outer(h, p, N, D, s) : factor_panel32(h, p, N, D, s);
+    }
+    if (rc) return rc;
+    if (p.path != PreparePath::small_whole && (rc = launch_tail(h, p, Y, N, D, s))) return rc;
+    if ((rc = check_info(h, D, s))) return rc;
+    commit_state(h, N, D, E);
     return GPMPC_OK;
 }
 
 int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
             int N, int D, int E, double* out_host, hipStream_t s) {
-    const int keep = h->opt_incremental;
-    h->opt_incremental = 0;                       // always a fresh factorisation: the hyper-parameters are the variables
-    int rc = run_prepare(h, X, Y, ls, os, noise, N, D, E, s);
-    h->opt_incremental = keep;
+    // always a fresh factorisation: the hyper-parameters are the variables
+    int rc = run_prepare(h, X, Y, ls, os, noise, N, D, E, s, false);
     if (rc) return rc;
     const int nt = (N + 63) / 64;
     const int EP = E <= 4 ? 4 : (E <= 8 ? 8 : (E <= 16 ? 16 : 24));

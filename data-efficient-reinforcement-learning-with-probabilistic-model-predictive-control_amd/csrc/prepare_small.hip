@@ -32,7 +32,7 @@ struct SmallPrepArgs {
     double *K, *Yinv, *z, *beta, *iK, *T;
     int* info;
     int cholesky_only;       // 1: stop after the factorisation (L, inverted diagonal blocks); the N^3 products that follow
-                             // (L^-1 by row blocks, beta, Y^T Y) then run as wide launches of prepare.hip's kernels
+                             // run as wide launches: L^-1 by trinv_cols_small_kernel, beta and Y^T Y by prepare.hip's tail
 };
 
 // LDS hand-off between lanes of ONE wavefront: LDS operations of a wave complete in issue order; the fences keep the
@@ -431,21 +431,13 @@ __global__ __launch_bounds__(256) void trinv_cols_small_kernel(const double* __r
     }
 }
 
-// Host side: returns 1 when the fused path handled the whole call (N <= 256), 2 when it did the factorisation, the
-// triangular inverse and the zero fill of T, and the caller has to run beta and Y^T Y (run_prepare's tail), 0 to fall
-// through, < 0 on error.
-int run_prepare_small(Handle* h, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
-                      int N, int D, int E, hipStream_t s) {
-    // Crossover with the panel chain, measured (round 3, tools/gpu_prepare_bench.py; the LDS arrays were sized by N for the test):
-    // N = 200: 0.217 vs 0.240 ms, 256: 0.344 vs 0.299, 300: 0.387 vs 0.337, 400: 0.84 vs 0.49, 500: 1.15 vs 0.60 -- one CU's
-    // matrix cores do the N^3 / 3 of the panel updates, so the single launch loses once the chain's launches fill more than a CU.
-    constexpr int kSmallPathMaxN = 240;
-    if (N > kSmallPathMaxN || N < 1 || h->opt_fused_prepare == 0) return 0;
+// Host side: PreparePath::small_whole runs everything in one launch; small_cholesky the factorisation, the triangular inverse
+// and the zero fill of T, after which run_prepare's tail (prepare.hip) runs beta and Y^T Y.
+int launch_prepare_small(Handle* h, const PreparePlan& pp, const double* X, const double* Y, const double* ls, const double* os,
+                         const double* noise, int N, int D, int E, hipStream_t s) {
+    static_assert(kSmallPathMaxN <= kSmallMaxN, "the LDS arrays of prepare_small_kernel hold kSmallMaxN points");
     SmallPrepArgs p;
-    // One workgroup per GP is the right shape for the factorisation (a chain of 200 dependent pivots) but not for the
-    // N^3 products after it: on one CU they are matrix-core-bound at ~50 k cycles each for N = 200.  From N = 96 up only
-    // the factorisation stays in the single launch (option "fused_prepare" = 2 forces everything into it, 3 never).
-    p.cholesky_only = (h->opt_fused_prepare == 3 || (h->opt_fused_prepare != 2 && N >= 96)) ? 1 : 0;
+    p.cholesky_only = pp.path == PreparePath::small_cholesky ? 1 : 0;
     p.X = X; p.Y = Y; p.ls = ls; p.os = os; p.noise = noise;
     p.N = N; p.D = D; p.E = E;
     p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.logvar = h->logvar.p; p.xrange = h->xrange.p;
@@ -465,7 +457,7 @@ int run_prepare_small(Handle* h, const double* X, const double* Y, const double*
     if (p.cholesky_only && N > kSB)
         hipLaunchKernelGGL(trinv_cols_small_kernel, dim3((N + kSB - 1) / kSB - 1, D), dim3(256), 0, s, h->gram.p, h->linv.p, N);
     GPMPC_HIP_CHECK(h, hipGetLastError());
-    return p.cholesky_only ? 2 : 1;
+    return GPMPC_OK;
 }
 
 }  // namespace gpmpc_hip

@@ -162,7 +162,7 @@ struct RolloutArgs {
     unsigned xch_tag0;           // tags of this launch: xch_tag0 + step + 1 (unique over the life of the buffer)
     unsigned long long* xch;
     unsigned long long* xch_uc;  // the same layout in uncached device memory (members on several XCDs; the placement prologue)
-    int cl_dbg;                  // timing experiments of the exchange (-DGPMPC_CL_DEBUG builds only)
+    int cl_dbg;                  // option cluster_debug: 4 the exchange's general form, 8 members spread over the XCDs (tests)
     // one sequence from the host (gpmpc_objective_grad_host): the actions ride in this block instead of an upload launch; the
     // fused-horizon kernel takes them from here and leaves a copy at `act_store` (= actions) for the gradient's kernels
     int act_inline_n;            // H * A (<= kInlineActs), or 0

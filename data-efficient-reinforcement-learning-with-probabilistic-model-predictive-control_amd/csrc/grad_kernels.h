@@ -84,18 +84,11 @@ __device__ inline void seeded_cost_weights(bool has_cm, double cmb, bool has_cv,
     if (has_cv) wv = has_J ? cvb + wv : cvb;
 }
 
-__host__ __device__ inline int tri_index(int d, int e, int DP) { return d * DP - (d * (d - 1)) / 2 + (e - d); }   // d <= e
-
 // Mean-part moments per output a (sums over the points, weights lb_ai):
 //   [0] 1 | [1, 1+D) nu_d | tri(D) nu_d1 nu_d2 (d1 <= d2) | D x tri(D) nu_k nu_d1 nu_d2 | NX nu_x | D x NX nu_k nu_x
 __host__ __device__ inline int tri_count(int D) { return D * (D + 1) / 2; }
 __host__ __device__ inline int mean_moment_count(int D, int NX) { return 1 + D + tri_count(D) + D * tri_count(D) + NX + D * NX; }
 __host__ __device__ inline int sym_index(int i, int j, int D) { return i <= j ? tri_index(i, j, D) : tri_index(j, i, D); }
-__device__ inline void decode_tri(int k, int D, int& d1, int& d2) {
-    d1 = 0;
-    while (k >= D - d1) { k -= D - d1; ++d1; }
-    d2 = d1 + k;
-}
 // factors of component `comp`: indices < D are state dims, D + x the extra input dims; -1 = no factor
 __device__ inline void decode_mean_moment(int comp, int D, int NX, int& i1, int& i2, int& i3) {
     const int T2 = tri_count(D);

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64 * sep_grad_waves(DP), DP <= 3 ? 3 : 2) void sep_
         s_m[e] = v;
     }
     for (int i = tid; i < D * E; i += NT) s_ils2[i] = p.ils2[i];
-    for (int i = tid; i < 64; i += NT) s_tab[i] = kExp2Tab[i];
+    stage_exp_tab(s_tab, tid, NT);
     for (int i = tid; i < 16 * NB; i += NT) {
         const bool in = i < p.mono_cum[p.kmax];
         s_cw[i] = in ? p.mono_w[i] : 0.0;
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(64 * sep_grad_waves(DP), DP <= 3 ? 3 : 2) void sep_
             const double* Z = s_Z + pq * DP * DP;
             const double* il = s_ils2 + co * E;
             const double lv = p.logvar[co];
-            mfma_d4 acc[NA][NB];
+            d4 acc[NA][NB];
             double accE[NE > 0 ? NE : 1][NB];
             if constexpr (sep_grad_version(DP) == 1) {
             const int K1 = K + 1;
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(64 * sep_grad_waves(DP), DP <= 3 ? 3 : 2) void sep_
 #pragma unroll
             for (int ia = 0; ia < NA; ++ia)
 #pragma unroll
-                for (int ib = 0; ib < NB; ++ib) acc[ia][ib] = mfma_d4{0.0, 0.0, 0.0, 0.0};
+                for (int ib = 0; ib < NB; ++ib) acc[ia][ib] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int e = 0; e < NE; ++e)
 #pragma unroll
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(64 * sep_grad_waves(DP), DP <= 3 ? 3 : 2) void sep_
 #pragma unroll
             for (int ia = 0; ia < NA; ++ia)
 #pragma unroll
-                for (int ib = 0; ib < NB; ++ib) acc[ia][ib] = mfma_d4{0.0, 0.0, 0.0, 0.0};
+                for (int ib = 0; ib < NB; ++ib) acc[ia][ib] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int e = 0; e < NE; ++e)
 #pragma unroll

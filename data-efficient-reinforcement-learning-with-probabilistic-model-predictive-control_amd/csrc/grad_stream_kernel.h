@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kGsThreads) void pair_moments_stream_kernel(const G
 
     for (int i = tid; i < D; i += NT) c_logvar[i] = p.logvar[i];
     for (int i = tid; i < D * E; i += NT) c_ils2[i] = p.ils2[i];
-    for (int i = tid; i < 64; i += NT) c_tab[i] = kExp2Tab[i];
+    stage_exp_tab(c_tab, tid, NT);
     for (int i = tid; i < 2 * E; i += NT) c_xr[i] = p.xrange[i];
     for (int i = tid; i < E; i += NT) {
         double v;

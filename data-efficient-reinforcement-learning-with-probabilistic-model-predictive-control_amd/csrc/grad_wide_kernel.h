@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_pair_moments_kernel(const W
 
     const double* mu = p.mu + ((size_t)c * (H + 1) + t) * D;
     const double* Sg = p.Sig + ((size_t)c * (H + 1) + t) * D * D;
-    for (int i = tid; i < 64; i += NT) s_exptab[i] = kExp2Tab[i];
+    stage_exp_tab(s_exptab, tid, NT);
     for (int i = tid; i <= 2 * kTableHalf; i += NT) s_etab[i - kTableHalf] = exp((double)(i - kTableHalf) * 0.0078125);
     for (int e = tid; e < E; e += NT) {
         double v;
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_pair_moments_kernel(const W
                 const double ecj = jin ? fast_exp(rowsum ? kprime(jc, 1) : k_c[jc], s_exptab) : 0.0;
                 const double colf = diag ? ecj : ecj * bcj;       // column factor of the sums (diagonal pair: beta_cj sits in the weight)
                 double csum0 = 0.0, csum1 = 0.0;
-                mfma_d4 vc = {0.0, 0.0, 0.0, 0.0};
+                d4 vc = {0.0, 0.0, 0.0, 0.0};
                 __syncthreads();                                   // previous sweep done with the stage
                 fill(0, s_stage);
                 __syncthreads();
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_pair_moments_kernel(const W
                             // two 16-row tiles per iteration: 8 independent evaluations of the exponential per lane
                             const double* a0p = st + (size_t)(16 * rt + col16) * RSW + 2 + grp;
                             const double* a1p = a0p + 16 * RSW;
-                            mfma_d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
+                            d4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                             for (int qd = 0; qd < 4; ++qd) {
                                 c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0p[4 * qd], hB[qd], c0, 0, 0, 0);
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_pair_moments_kernel(const W
             const double kcj = k_c[jc];
             const double bcj = jin ? beta_c[jc] : 0.0;
             double csum = 0.0;
-            mfma_d4 vc = {0.0, 0.0, 0.0, 0.0};
+            d4 vc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
             for (int rt = 0; rt < NT16; ++rt) {
                 // A operand of the c tile: u_row[dim 4 qd + grp], row = rt * 16 + col16
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(kWideThreads) void wide_pair_moments_kernel(const W
                     const int d = 4 * qd + grp;
                     aA[qd] = (d < D) ? (p.Xt[(size_t)d * N + irc] - s_m[d]) * il_r[d] : 0.0;
                 }
-                mfma_d4 cc = {0.0, 0.0, 0.0, 0.0};
+                d4 cc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) cc = __builtin_amdgcn_mfma_f64_16x16x4f64(aA[qd], hB[qd], cc, 0, 0, 0);
                 double ev[4];

@@ -22,7 +22,7 @@
 // are bitwise the same whatever P is, wherever it sits in the batch, whoever its neighbours are and however the points are
 // chunked.  P is processed in chunks so the workspace stays within kWsBudget whatever P is.
 #include "moments_common.h"
-#include "rollout_kernel.h"     // fast_exp, kExp2Tab
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void moments_pair_kernel(MomentsArgs p) {
     const int tile = blockIdx.x, rt = tile / nt, ct = tile - rt * nt;
     const int pr = blockIdx.y;
     int a, b;
-    pair_of(pr, p.D, a, b);
+    decode_tri(pr, p.D, a, b);
     const bool diag = a == b;
     if (diag && rt > ct) return;                                          // lower tiles of a diagonal pair: nothing
     const int pt0 = blockIdx.z * kPPW;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(64) void moments_finish_kernel(MomentsArgs p) {
     const int lane = threadIdx.x;
     const int pt = blockIdx.x / p.npairs, pr = blockIdx.x - pt * p.npairs;
     int a, b;
-    pair_of(pr, p.D, a, b);
+    decode_tri(pr, p.D, a, b);
     const bool diag = a == b;
     const int nt = p.nt, nw = nt * nt * kWaves;
     const double* part = p.part + ((size_t)pt * p.npairs + pr) * nw;
@@ -239,8 +239,7 @@ __global__ __launch_bounds__(64) void moments_finish_kernel(MomentsArgs p) {
         const int tile = k / kWaves, rt = tile / nt, ct = tile - rt * nt;
         if (!diag || rt <= ct) s += part[k];
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_xor_sum(s);
     if (lane != 0) return;
     const int D = p.D;
     const double ldR = p.setup[((size_t)pt * p.nprob + D + pr) * setup_stride(p.E) + (size_t)p.E * p.E];

@@ -33,7 +33,7 @@
 // is, wherever it sits and however the batch is chunked.  Points are chunked so the workspace stays within 32 MB (or one point's
 // need when that is more).
 #include "moments_common.h"
-#include "rollout_kernel.h"     // fast_exp, kExp2Tab
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
@@ -54,13 +54,6 @@ struct BackArgs {
 
 __host__ __device__ inline size_t psum_stride(int E) { return 1 + 2 * (size_t)E + 2 * (size_t)E * E; }
 __host__ __device__ inline size_t pp_stride(int E) { return (size_t)E * E + E + 1; }
-
-// upper-triangle entry index -> (e, f), e <= f, row by row
-__device__ inline void tri_of(int k, int E, int& e, int& f) {
-    e = 0;
-    while (k >= E - e) { k -= E - e; ++e; }
-    f = e + k;
-}
 
 // ----------------------------------------------------------------------------------------------------------------------------
 // O(N) pass: one workgroup per (point, output a).
@@ -115,8 +108,8 @@ __global__ __launch_bounds__(256) void mb_point_kernel(BackArgs q) {
     const int ent0 = nent <= 256 ? tid % nent : tid, slice = nent <= 256 ? tid / nent : 0;
     const bool own0 = slice < slices && ent0 < nent, own1 = nent > 256 && tid + 256 < nent;
     int e0 = 0, f0 = 0, e1 = 0, f1 = 0;
-    if (own0) tri_of(ent0, E, e0, f0);
-    if (own1) tri_of(tid + 256, E, e1, f1);
+    if (own0) decode_tri(ent0, E, e0, f0);
+    if (own1) decode_tri(tid + 256, E, e1, f1);
     double a2[2] = {0.0, 0.0}, a3[2] = {0.0, 0.0};
     __syncthreads();
     double s0 = 0.0, s1[EP];
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(256) void mb_point_kernel(BackArgs q) {
         double v2 = 0.0, v3 = 0.0;
         for (int sl = 0; sl < slices; ++sl) { v2 += s_acc[0][sl * nent + k]; v3 += s_acc[1][sl * nent + k]; }
         int e, f;
-        tri_of(k, E, e, f);
+        decode_tri(k, E, e, f);
         S2[e * E + f] = v2; S2[f * E + e] = v2;
         S3[e * E + f] = v3; S3[f * E + e] = v3;
     }
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(256) void mb_pair_kernel(BackArgs q) {
     const int nt = p.nt, N = p.N, E = p.E, D = p.D;
     const int rt = blockIdx.x, pr = blockIdx.y, pt = blockIdx.z;
     int a, b;
-    pair_of(pr, D, a, b);
+    decode_tri(pr, D, a, b);
     const bool diag = a == b;
     const int r0 = rt * kTile;
     const int lr = 16 * wv + 4 * (lane >> 4), lc = 4 * (lane & 15);
@@ -261,7 +254,7 @@ __global__ __launch_bounds__(256) void mb_pair_kernel(BackArgs q) {
         const int k = tid + 256 * s;
         ke[s] = kf[s] = 0;
         kind[s] = k < nent ? 0 : k < nent + E ? 1 : k < ntot ? 2 : -1;
-        if (kind[s] == 0) tri_of(k, E, ke[s], kf[s]);
+        if (kind[s] == 0) decode_tri(k, E, ke[s], kf[s]);
         else if (kind[s] == 1) ke[s] = k - nent;
     }
     double acc[2] = {0.0, 0.0};
@@ -486,7 +479,7 @@ __global__ __launch_bounds__(256) void mb_finish_kernel(BackArgs q) {
         const int nt = p.nt;
         for (int pr = 0; pr < p.npairs; ++pr) {
             int a, b;
-            pair_of(pr, D, a, b);
+            decode_tri(pr, D, a, b);
             const bool diag = a == b;
             const double gam = diag ? Sb[a * D + a] : Sb[a * D + b] + Sb[b * D + a];
             const double ldR = p.setup[((size_t)pt * p.nprob + D + pr) * setup_stride(E) + EE];

@@ -2,7 +2,7 @@
 // argument block, the pair numbering and the per-(point, problem) setup kernel (C_a^-1 | log det B_a, Q_ab | log det R_ab and,
 // for the backward, A_ab^-1).  See the moments.hip header for the notation.
 #pragma once
-#include "gpmpc_internal.h"
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
@@ -35,13 +35,6 @@ struct MomentsArgs {
 
 __host__ __device__ inline size_t setup_stride(int E) { return (size_t)E * E + 1; }
 
-// pair index -> (a, b), a <= b, in the order (0,0) (0,1) .. (0,D-1) (1,1) ..
-__device__ inline void pair_of(int pr, int D, int& a, int& b) {
-    a = 0;
-    while (pr >= D - a) { pr -= D - a; ++a; }
-    b = a + pr;
-}
-
 // ----------------------------------------------------------------------------------------------------------------------------
 // Setup: one wavefront per (point, problem).
 __global__ __launch_bounds__(64) void moments_setup_kernel(MomentsArgs p) {
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(64) void moments_setup_kernel(MomentsArgs p) {
     const double* Sg = p.Sig ? p.Sig + (size_t)pt * E * E : nullptr;
     const bool pairp = prob >= D;
     int a = prob, b = prob;
-    if (pairp) pair_of(prob - D, D, a, b);
+    if (pairp) decode_tri(prob - D, D, a, b);
     if (lane < E) s_d[lane] = pairp ? sqrt(p.ils2[a * E + lane] + p.ils2[b * E + lane]) : sqrt(p.ils2[a * E + lane]);
     __syncthreads();
     // A = D Sigma D + I  (B_a with D = 1/l_a; I + G with D = Lambda_ab^1/2)

@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kTileWaves * 64, 2) void pair_tile_moments_kernel(c
     const double lv = p.logvar[a];
     const int ngroups = (ncand + kTileGC - 1) / kTileGC;
     // compact records hold the D diagonal pairs only; the forward's step records all P pairs
-    const double* __restrict__ tpar = p.crec + p.off_pair + (p.compact ? a : pair_index(a, a, p.D)) * p.PRP;
+    const double* __restrict__ tpar = p.crec + p.off_pair + (p.compact ? a : tri_index(a, a, p.D)) * p.PRP;
     auto degrees = [&](int g, int (&K)[kTileGC]) {
 #pragma unroll
         for (int kk = 0; kk < kTileGC; ++kk) {
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(64) void tile_moments_reduce_kernel(const StepArgs 
     const int D = p.D, E = p.E, NX = E - D, P = D * (D + 1) / 2;
     const size_t git = p.fused_t >= 0 ? (size_t)it * p.H + p.fused_t : (size_t)p.item0 + it;      // FUSED: item = candidate, this step
     for (int a = 0; a < D; ++a) {
-        const int q = pair_index(a, a, D);
+        const int q = tri_index(a, a, D);
         const int K = (int)p.crec[(size_t)it * p.CS + p.off_pair + (p.compact ? a : q) * p.PRP + DP * DP + 1] & 63;
         if (lane == 0) done[git * P + q] = K > 0 ? 1 : 0;
         if (K == 0) continue;

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kTileWaves * 64, 4) void pair_tile_kernel(const Ste
     const double lv = p.logvar[a];
     const int ngroups = (ncand + kTileGC - 1) / kTileGC;
     // the (a, a) problem of the candidates' step records: Z (DP x DP) | 1 / sqrt(det R) | degree
-    const double* __restrict__ tpar = p.crec + p.off_pair + pair_index(a, a, D) * p.PRP;
+    const double* __restrict__ tpar = p.crec + p.off_pair + tri_index(a, a, D) * p.PRP;
     // Taylor degrees of the candidates of a group (0: direct exp), fetched one group ahead
     auto degrees = [&](int g, int (&K)[kTileGC]) {
 #pragma unroll

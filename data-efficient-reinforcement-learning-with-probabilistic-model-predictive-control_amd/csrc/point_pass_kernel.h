@@ -73,8 +73,6 @@ struct StepArgs {
     int fused_t;            // >= 0: the gradient's tile moments are formed inside the forward's step `fused_t` (items = candidates)
 };
 
-__host__ __device__ inline int pair_index(int a, int b, int D) { return a * D - (a * (a - 1)) / 2 + (b - a); }
-
 // ------------------------------------------------------------------------------------------
 // All the D x D algebra of step t, one thread per problem: phase P1 of rollout_kernel.
 //   mean problem a : A_a = Sigma + diag(l_a^2) -> A_a^-1, c_a = var_a / sqrt(det B_a)                 (gp_model.py:141-150)
@@ -664,7 +662,7 @@ __global__ __launch_bounds__(64) void step_combine_kernel(const StepArgs p) {
     for (int idx = lane; idx < D * D; idx += 64) {
         const int i = idx / D, j = idx - i * D;
         const int a = i < j ? i : j, b = i < j ? j : i;
-        const double S = s_Sp[pair_index(a, b, D)] - s_M[i] * s_M[j] + (i == j ? p.var[i] : 0.0);
+        const double S = s_Sp[tri_index(a, b, D)] - s_M[i] * s_M[j] + (i == j ? p.var[i] : 0.0);
         double cij = 0.0, cji = 0.0;
         for (int k = 0; k < D; ++k) {
             cij = fma(s_Sig[i * D + k], s_Vs[k * D + j], cij);

@@ -12,13 +12,11 @@
 // Every sum of a row runs in an order fixed by N alone (k steps, lanes, waves, column blocks): a point's bits do not depend on
 // M, on its place in the batch or on the other points.  No atomics.  M is processed in chunks of Mc rows so the workspace
 // (2 D nCB Mc doubles) stays within kWsBudget.  Without var_out the k loop is compiled out (the mean is a GEMV).
-#include "gpmpc_internal.h"
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 64;                  // query rows per workgroup
 constexpr int kBN = 256;                 // columns of iK per workgroup (64 per wave)

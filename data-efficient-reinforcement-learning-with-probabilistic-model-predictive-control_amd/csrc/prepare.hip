@@ -12,30 +12,10 @@
 // N^3 contractions are the only dense contractions of the hot path and run on the matrix
 // cores with v_mfma_f64_16x16x4_f64 (wave64: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15],
 // D[row=(l>>4)+4r][col=l&15]).
-#include "gpmpc_internal.h"
+#include "device_common.h"
 #include "prepare_tiled.h"
-#include "rollout_kernel.h"        // fast_exp / kExp2Tab
 
 namespace gpmpc_hip {
-
-// acc += sum over p in [pbeg, pend) of A(p) B(p) for one 16 x 16 tile with the operands straight from global memory:
-// the loads of U k-steps are issued before the first MFMA of the group, so a group costs one memory round trip, not U
-// (without it every v_mfma waited for its own two loads: the N^3 kernels ran at L2 latency, 8-21 TFLOP/s at N = 4096).
-template <int U, typename FA, typename FB>
-__device__ inline void mfma_kloop(d4& acc, int pbeg, int pend, int lk, FA loadA, FB loadB) {
-    for (int pp = pbeg; pp < pend; pp += 4 * U) {
-        double av[U], bv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int pk = pp + 4 * u + lk;
-            const bool in = pk < pend;
-            av[u] = in ? loadA(pk) : 0.0;
-            bv[u] = in ? loadB(pk) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-    }
-}
 
 // ------------------------------------------------------------------------------------------
 __global__ void pack_inputs_kernel(const double* __restrict__ X, const double* __restrict__ ls,
@@ -360,7 +340,7 @@ __global__ __launch_bounds__(NB * NB) void potrf_diag_fast_kernel(double* __rest
     if (c == 0) { colb[0][r] = a0; colb[0][NB + r] = a1; }
     if (tid == 0) {
         if (!(a0 > 0.0) && info[a] == 0) info[a] = k0 + 1;
-        sinv[0] = inv_sqrt_pos_p(a0);
+        sinv[0] = inv_sqrt_pos(a0);
     }
     if (tid >= nb && tid < NB) sinv[tid] = 0.0;
     __syncthreads();
@@ -378,7 +358,7 @@ __global__ __launch_bounds__(NB * NB) void potrf_diag_fast_kernel(double* __rest
                     cn[NB + r] = a1;
                     if (r == k + 1) {
                         if (!(a0 > 0.0) && info[a] == 0) info[a] = k0 + k + 2;
-                        sinv[k + 1] = inv_sqrt_pos_p(a0);
+                        sinv[k + 1] = inv_sqrt_pos(a0);
                     }
                 }
             }
@@ -597,7 +577,7 @@ __global__ __launch_bounds__(NB * NB) void syrk_trailing_potrf_kernel(double* __
     if (c == 0) { colb[0][r] = a0; colb[0][NB + r] = a1; }
     if (tid == 0) {
         if (!(a0 > 0.0) && info[a] == 0) info[a] = r0 + 1;
-        sinv[0] = inv_sqrt_pos_p(a0);
+        sinv[0] = inv_sqrt_pos(a0);
     }
     if (tid >= nb2 && tid < NB) sinv[tid] = 0.0;
     __syncthreads();
@@ -615,7 +595,7 @@ __global__ __launch_bounds__(NB * NB) void syrk_trailing_potrf_kernel(double* __
                     cn[NB + r] = a1;
                     if (r == k + 1) {
                         if (!(a0 > 0.0) && info[a] == 0) info[a] = r0 + k + 2;
-                        sinv[k + 1] = inv_sqrt_pos_p(a0);
+                        sinv[k + 1] = inv_sqrt_pos(a0);
                     }
                 }
             }
@@ -924,7 +904,7 @@ __global__ __launch_bounds__(256) void syrk_inverse_kernel(const double* __restr
     const int a = blockIdx.z;
     const double* Y = Yall + (size_t)a * N * N;
     double* iK = iKall + (size_t)a * N * N;
-    double* T = Tall + (size_t)a * (N + kTPadRows) * N;
+    double* T = Tall + (size_t)a * (N + kTPad) * N;
     const double* be = beta + (size_t)a * N;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = ti * 32 + (wave >> 1) * 16;
@@ -992,7 +972,7 @@ __global__ __launch_bounds__(256) void border_lvec_kernel(const double* __restri
     const double* r = linv + ((size_t)a * n + row) * n;
     double s = 0.0;
     for (int j = lane; j <= row; j += 64) s = fma(r[j], kv[(size_t)a * ldk + j], s);
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_xor_sum(s);
     if (lane == 0) lv[(size_t)a * ldk + row] = s;
 }
 
@@ -1066,13 +1046,13 @@ __global__ __launch_bounds__(256) void tm_kernel(const double* __restrict__ iK, 
     const int a = blockIdx.z;
     const int j = blockIdx.x * 64 + (threadIdx.x & 63);
     const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (i >= N + kTPadRows || j >= N) return;                // the launch covers the zero rows after T_a too (no memset)
+    if (i >= N + kTPad || j >= N) return;                // the launch covers the zero rows after T_a too (no memset)
     double t = 0.0;
     if (i <= j) {
         t = beta[(size_t)a * N + i] * beta[(size_t)a * N + j] - iK[((size_t)a * N + i) * N + j];
         if (i == j) t *= 0.5;
     }
-    T[((size_t)a * (N + kTPadRows) + i) * N + j] = t;        // upper triangle only
+    T[((size_t)a * (N + kTPad) + i) * N + j] = t;        // upper triangle only
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1090,7 +1070,7 @@ static inline bool fits(const Buf& b, size_t need) { return b.p && need <= b.cap
 int ensure_model_buffers(Handle* h, int N, int D, int E, bool need_factor_ws) {
     // allocate with head-room for 64 more points: appended points then reuse the buffers (and their contents)
     const size_t Nc = (size_t)N + 64;
-    const bool regrow = !fits(h->iK, (size_t)D * N * N) || !fits(h->Tm, (size_t)D * (N + kTPadRows) * N) ||
+    const bool regrow = !fits(h->iK, (size_t)D * N * N) || !fits(h->Tm, (size_t)D * (N + kTPad) * N) ||
                         !fits(h->beta, (size_t)D * N) || !fits(h->Xt, (size_t)E * N) ||
                         (need_factor_ws && (!fits(h->gram, (size_t)D * N * N) || !fits(h->linv, (size_t)D * N * N)));
     const size_t Ns = regrow ? Nc : (size_t)N;
@@ -1104,10 +1084,10 @@ int ensure_model_buffers(Handle* h, int N, int D, int E, bool need_factor_ws) {
     if ((rc = grow(h, h->beta, DN))) return rc;
     if ((rc = grow(h, h->zvec, DN))) return rc;
     if ((rc = grow(h, h->iK, NN))) return rc;
-    if ((rc = grow(h, h->Tm, (size_t)D * (Ns + kTPadRows) * Ns))) return rc;    // + zero rows per GP
+    if ((rc = grow(h, h->Tm, (size_t)D * (Ns + kTPad) * Ns))) return rc;    // + zero rows per GP
     if (need_factor_ws) {
         if ((rc = grow(h, h->gram, NN))) return rc;
-        if ((rc = grow(h, h->linv, (size_t)D * (Ns + kTPadRows) * Ns))) return rc;   // trades places with Tm in border updates
+        if ((rc = grow(h, h->linv, (size_t)D * (Ns + kTPad) * Ns))) return rc;   // trades places with Tm in border updates
     }
     if ((rc = grow(h, h->Xc, Ns * E))) return rc;
     if ((rc = grow(h, h->Yc, Ns * D))) return rc;
@@ -1152,7 +1132,7 @@ int run_set_factors(Handle* h, const double* X, const double* iK, const double* 
     if ((rc = pack(h, X, ls, os, N, D, E, s))) return rc;
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->iK.p, iK, (size_t)D * N * N * sizeof(double), hipMemcpyDeviceToDevice, s));
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->beta.p, beta, (size_t)D * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPadRows + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p, nullptr);
+    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p, nullptr);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     h->N = N; h->D = D; h->E = E; h->ready = true;
     h->have_state = false;                      // no (X, Y, hyper-parameters) record for these factors
@@ -1291,7 +1271,7 @@ static int try_incremental(Handle* h, const double* X, const double* Y, const do
     const int n0 = h->N, k = N - n0;
     if (k < 0 || k > 8 || h->inc_updates + k > h->opt_refresh_every) return 0;
     const size_t NN = (size_t)D * N * N, DN = (size_t)D * N;
-    const size_t TN = (size_t)D * (N + kTPadRows) * N;
+    const size_t TN = (size_t)D * (N + kTPad) * N;
     if (!fits(h->iK, NN) || !fits(h->gram, NN) || !fits(h->linv, TN) || !fits(h->beta, DN) || !fits(h->zvec, DN) ||
         !fits(h->Tm, TN) || !fits(h->Xt, (size_t)E * N) || !fits(h->Xc, (size_t)N * E) ||
         !fits(h->Yc, (size_t)N * D) || !fits(h->kv, DN) || !fits(h->vv, DN))
@@ -1328,7 +1308,7 @@ static int try_incremental(Handle* h, const double* X, const double* Y, const do
         t = h->linv; h->linv = h->Tm; h->Tm = t;
         t = h->beta; h->beta = h->zvec; h->zvec = t;
     }
-    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPadRows + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p,
+    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p,
                        h->mismatch);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     int verdict[kMaxD + 1];
@@ -1636,7 +1616,7 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
     } else {
         if ((rc = pack_and_record(h, X, Y, ls, os, noise, N, D, E, s))) return rc;
         GPMPC_HIP_CHECK(h, hipMemsetAsync(h->linv.p, 0, (size_t)D * N * N * sizeof(double), s));
-        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->Tm.p, 0, (size_t)D * (N + kTPadRows) * N * sizeof(double), s));
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->Tm.p, 0, (size_t)D * (N + kTPad) * N * sizeof(double), s));
         if ((rc = launch_gram(h, p, noise, N, D, E, s))) return rc;
         rc = p.path == PreparePath::outer ? factor_outer(h, p, N, D, s) : factor_panel32(h, p, N, D, s);
     }
@@ -1659,12 +1639,12 @@ int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const
     double* partial = h->mllws.p;
     double* out = partial + npart;
     const dim3 grid(nt, nt, D);
-    if (EP == 4) hipLaunchKernelGGL(mll_tile_kernel<4>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPadRows, partial);
-    else if (EP == 8) hipLaunchKernelGGL(mll_tile_kernel<8>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPadRows, partial);
-    else if (EP == 16) hipLaunchKernelGGL(mll_tile_kernel<16>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPadRows, partial);
-    else hipLaunchKernelGGL(mll_tile_kernel<24>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPadRows, partial);
+    if (EP == 4) hipLaunchKernelGGL(mll_tile_kernel<4>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPad, partial);
+    else if (EP == 8) hipLaunchKernelGGL(mll_tile_kernel<8>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPad, partial);
+    else if (EP == 16) hipLaunchKernelGGL(mll_tile_kernel<16>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPad, partial);
+    else hipLaunchKernelGGL(mll_tile_kernel<24>, grid, dim3(256), 0, s, h->Xt.p, h->ils2.p, h->var.p, h->Tm.p, N, E, kTPad, partial);
     hipLaunchKernelGGL(mll_finish_kernel, dim3(D), dim3(256), 0, s, partial, nt, EP, Y, h->beta.p, h->gram.p, h->Tm.p, h->ils2.p,
-                       h->var.p, N, D, E, kTPadRows, out);
+                       h->var.p, N, D, E, kTPad, out);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(out_host, out, nout * sizeof(double), hipMemcpyDeviceToHost, s));
     GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));

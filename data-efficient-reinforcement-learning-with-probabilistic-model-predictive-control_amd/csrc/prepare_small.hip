@@ -15,13 +15,11 @@
 //   * columns are never divided: every update multiplies by the two scaled factors, L is scaled on the way out;
 //   * the panel solve is a product with the inverted diagonal block on the matrix cores, not a substitution.
 // The N^3 parts (trailing update, L^-1 by row blocks, Y^T Y) are 16 x 16 fp64 MFMA tiles dealt to the 16 wavefronts.
-#include "gpmpc_internal.h"
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
-typedef double sd4 __attribute__((ext_vector_type(4)));
 constexpr int kSB = 32;            // panel width
-constexpr int kSTPad = 72;         // zero rows after every T_a (= kTPad of rollout_kernel.h)
 constexpr int kSmallMaxN = 256;
 
 struct SmallPrepArgs {
@@ -34,41 +32,6 @@ struct SmallPrepArgs {
     int cholesky_only;       // 1: stop after the factorisation (L, inverted diagonal blocks); the N^3 products that follow
                              // run as wide launches: L^-1 by trinv_cols_small_kernel, beta and Y^T Y by prepare.hip's tail
 };
-
-// LDS hand-off between lanes of ONE wavefront: LDS operations of a wave complete in issue order; the fences keep the
-// compiler from moving accesses across
-__device__ inline void wave_lds_sync_s() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 1 / sqrt(d), d > 0: fp32 seed (1 ulp) + two Newton steps y <- y (1.5 - 0.5 d y^2): relative error ~2^-85 before rounding
-__device__ inline double inv_sqrt_pos(double d) {
-    double y = (double)__builtin_amdgcn_rsqf((float)d);
-    const double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
-    return y;
-}
-
-// acc += sum over p in [pbeg, pend) of A(p) B(p) for one 16 x 16 tile, operands straight from global memory (L2): the
-// loads of U k-steps are issued before the first MFMA of the group, so a group costs one L2 round trip, not U.
-template <int U, typename FA, typename FB>
-__device__ inline void mfma_kloop(sd4& acc, int pbeg, int pend, int lk, FA loadA, FB loadB) {
-    for (int pp = pbeg; pp < pend; pp += 4 * U) {
-        double av[U], bv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int pk = pp + 4 * u + lk;
-            const bool in = pk < pend;
-            av[u] = in ? loadA(pk) : 0.0;
-            bv[u] = in ? loadB(pk) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-    }
-}
 
 __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs p) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -84,7 +47,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
     double* K = p.K + (size_t)a * N * N;
     double* Yv = p.Yinv + (size_t)a * N * N;
     double* iK = p.iK + (size_t)a * N * N;
-    double* T = p.T + (size_t)a * (N + kSTPad) * N;
+    double* T = p.T + (size_t)a * (N + kTPad) * N;
     double* be = p.beta + (size_t)a * N;
     double* zv = p.z + (size_t)a * N;
 #ifdef GPMPC_PROF_ON
@@ -164,7 +127,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
             const int nrt = (nr + 15) >> 4;
             for (int t = wave; t < nrt; t += 16) {
                 const int i0 = k0 + t * 16;
-                sd4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+                d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
                 double c0v[4], c1v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {                // the Gram values of this tile (lower triangle only is defined)
@@ -254,7 +217,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
             const int nrt = (M + 15) >> 4;
             for (int t = wave; t < 2 * nrt; t += 16) {
                 const int i0 = (t >> 1) * 16, j0 = (t & 1) * 16;
-                sd4 acc = {0.0, 0.0, 0.0, 0.0};
+                d4 acc = {0.0, 0.0, 0.0, 0.0};
                 const double* Ar = Lp + (size_t)(nb + i0 + li) * 33;
 #pragma unroll
                 for (int kk = 0; kk < kSB; kk += 4)
@@ -275,7 +238,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
     SMALL_STAMP();
     if (p.cholesky_only) {
         // T_a := 0 (its upper triangle is filled by the Y^T Y launch that follows): saves the memset launch
-        for (int idx = tid; idx < (N + kSTPad) * N; idx += 1024) T[idx] = 0.0;
+        for (int idx = tid; idx < (N + kTPad) * N; idx += 1024) T[idx] = 0.0;
         return;
     }
     // ---- P3: Y = L^-1 by row blocks: Y[k, c] = -Ykk (L[k, :k] Y[:k, c]) for c < k ------------------------------------------
@@ -285,7 +248,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
         // W = L[k, 0:k0] Y[0:k0, 0:k0] -> scratch in T_a (32 x k0, row stride k0)
         for (int t = wave; t < 2 * nct; t += 16) {
             const int i0 = (t & 1) * 16, c0 = (t >> 1) * 16;
-            sd4 acc = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
             const bool rowin = (i0 + li < nb);
             const double* Arow = K + (size_t)(k0 + (rowin ? i0 + li : 0)) * N;
             const double* Bcol = Yv + c0 + li;
@@ -299,7 +262,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
         // Y[k, c] = -Ykk W   (Ykk = the block's inverse of P2b; lower triangular)
         for (int t = wave; t < 2 * nct; t += 16) {
             const int i0 = (t & 1) * 16, c0 = (t >> 1) * 16;
-            sd4 acc = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
             const bool rowin = (i0 + li < nb);
             const double* Arow = Yv + (size_t)(k0 + (rowin ? i0 + li : 0)) * N + k0;
             const double* Bcol = T + c0 + li;
@@ -351,7 +314,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
 
     SMALL_STAMP();
     // ---- P5: iK = Y^T Y (gp_model.py:428), T = beta beta^T - iK (upper triangle, diagonal halved), zero elsewhere ----------
-    for (int idx = tid; idx < (N + kSTPad) * N; idx += 1024) T[idx] = 0.0;
+    for (int idx = tid; idx < (N + kTPad) * N; idx += 1024) T[idx] = 0.0;
     __syncthreads();
     {
         const int nt = (N + 15) >> 4;
@@ -362,7 +325,7 @@ __global__ __launch_bounds__(1024) void prepare_small_kernel(const SmallPrepArgs
             while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
             const int tj = t - ti * (ti + 1) / 2;
             const int i0 = ti * 16, j0 = tj * 16;              // j0 <= i0
-            sd4 acc = {0.0, 0.0, 0.0, 0.0};
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
             const int ci = (i0 + li < N) ? i0 + li : N - 1, cj = (j0 + li < N) ? j0 + li : N - 1;    // clamped: masked on store
             mfma_kloop<16>(acc, i0, N, lk,                                                             // Y[p][c] = 0 for p < c
                           [&](int pk) { return Yv[(size_t)pk * N + ci]; },
@@ -406,7 +369,7 @@ __global__ __launch_bounds__(256) void trinv_cols_small_kernel(const double* __r
     const int wi = (wave >> 1) * 16, wj = (wave & 1) * 16;
     for (int k0 = c0 + kSB; k0 < N; k0 += kSB) {
         const int nb = (N - k0 < kSB) ? (N - k0) : kSB;
-        sd4 acc = {0.0, 0.0, 0.0, 0.0};
+        d4 acc = {0.0, 0.0, 0.0, 0.0};
         const bool rowin = (wi + li < nb);
         const double* Ar = L + (size_t)(k0 + (rowin ? wi + li : 0)) * N;
         const double* Bc = Y + c0 + wj + li;                          // c0 + 31 < k0 <= N: always inside
@@ -414,7 +377,7 @@ __global__ __launch_bounds__(256) void trinv_cols_small_kernel(const double* __r
 #pragma unroll
         for (int r = 0; r < 4; ++r) Ws[(wi + lk + 4 * r) * 33 + wj + li] = acc[r];
         __syncthreads();
-        sd4 acc2 = {0.0, 0.0, 0.0, 0.0};
+        d4 acc2 = {0.0, 0.0, 0.0, 0.0};
         const double* Yk = Y + (size_t)(k0 + (rowin ? wi + li : 0)) * N + k0;
 #pragma unroll
         for (int kk = 0; kk < kSB; kk += 4) {

@@ -3,22 +3,11 @@
 // whole 128-column outer panel, and the batched product behind the recursive-doubling triangular inverse.  Drivers and the
 // panel-level kernels are in prepare.hip; DESIGN.md 4.2 has the measurements.
 #pragma once
-#include "gpmpc_internal.h"
+#include "device_common.h"
 
 namespace gpmpc_hip {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
 constexpr int NB = 32;   // panel width
-constexpr int kTPadRows = 72;   // zero rows after every T_a (= kTPad of rollout_kernel.h)
-
-// 1 / sqrt(d), d > 0: fp32 v_rsq seed + two Newton steps (6 dependent fp64 operations instead of ~35 for sqrt + divide)
-__device__ inline double inv_sqrt_pos_p(double d) {
-    double y = (double)__builtin_amdgcn_rsqf((float)d);
-    const double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
-    return y;
-}
 
 // ------------------------------------------------------------------------------------------
 // LDS-tiled symmetric rank-k products on the matrix cores (large N).  The round-1 kernels above give every wavefront one
@@ -104,7 +93,7 @@ __global__ __launch_bounds__(256) void syrk_inverse_tiled_kernel(const double* _
     const int a = blockIdx.z;
     const double* Y = Yall + (size_t)a * N * N;
     double* iK = iKall + (size_t)a * N * N;
-    double* T = Tall + (size_t)a * (N + kTPadRows) * N;
+    double* T = Tall + (size_t)a * (N + kTPad) * N;
     const double* be = beta + (size_t)a * N;
     const int i0 = ti * TS, j0 = tj * TS;                            // j0 <= i0
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -245,7 +234,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     tri_tile(t, ti, tj);
     const double* Y = Yall + (size_t)a * N * N;
     double* iK = iKall + (size_t)a * N * N;
-    double* T = Tall + (size_t)a * (N + kTPadRows) * N;
+    double* T = Tall + (size_t)a * (N + kTPad) * N;
     const double* be = beta + (size_t)a * N;
     const int i0 = ti * T2, j0 = tj * T2;                            // j0 <= i0
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -430,7 +419,7 @@ __global__ __launch_bounds__(1024) void potrf_block128_kernel(double* __restrict
         if (c32 == 0) { colb[r32] = a0; colb[NB + r32] = a1; }
         if (tid == 0) {
             if (!(a0 > 0.0) && info[a] == 0) info[a] = J0 + k0 + 1;
-            sinv[0] = inv_sqrt_pos_p(a0);
+            sinv[0] = inv_sqrt_pos(a0);
         }
         if (tid >= nb && tid < NB) sinv[tid] = 0.0;
         __syncthreads();
@@ -448,7 +437,7 @@ __global__ __launch_bounds__(1024) void potrf_block128_kernel(double* __restrict
                         cn[NB + r32] = a1;
                         if (r32 == k + 1) {
                             if (!(a0 > 0.0) && info[a] == 0) info[a] = J0 + k0 + k + 2;
-                            sinv[k + 1] = inv_sqrt_pos_p(a0);
+                            sinv[k + 1] = inv_sqrt_pos(a0);
                         }
                     }
                 }

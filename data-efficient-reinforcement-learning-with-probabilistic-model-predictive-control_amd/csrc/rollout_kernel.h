@@ -31,16 +31,13 @@
 // triangular diagonal pairs balance, and every reduction is a fixed-order wavefront butterfly
 // followed by a fixed-order sum, so results are bitwise reproducible run to run.
 #pragma once
-#include "gpmpc_internal.h"
-#include <type_traits>
+#include "device_common.h"
 
 #if defined(GPMPC_PROF_ON)
 // phase profile of workgroup 0 (debug build only): cycles between consecutive trace points, summed over steps
 #define GPMPC_TRACE(id) do { if (threadIdx.x == 0 && blockIdx.x == 0) { long long now_ = __builtin_readcyclecounter(); \
     prof_acc[id] += now_ - prof_last; prof_last = now_; } \
     if (CL && threadIdx.x == 0 && (blockIdx.x & 7) == 0) { long long w_ = wall_clock64(); prof_wall[id] += w_ - prof_wlast; prof_wlast = w_; } } while (0)
-#elif defined(GPMPC_TRACE_ON)
-#define GPMPC_TRACE(id) do { if (threadIdx.x == 0 && blockIdx.x == 0) printf("trace %d t=%d\n", id, t_dbg); } while (0)
 #else
 #define GPMPC_TRACE(id) do {} while (0)
 #endif
@@ -52,16 +49,12 @@ namespace gpmpc_hip {
 // 16 bytes per lane even for a broadcast (two ds_read_b64: 2 + 2), and for the A operand of the fp64 matrix instruction (row
 // l & 15 of a stage with an 18-double row stride) rows r and r + 8 of a group collide on top (16 cycles against 4); measured:
 // profiles/r04_lds_read_forms.txt.  An opaque copy of the address gives the read a base register of its own, which the
-// load/store optimiser cannot pair.  (-DGPMPC_LDS_MERGED: the compiler's pairing, kept for the A/B build `make ab`.)
+// load/store optimiser cannot pair.
 typedef const __attribute__((address_space(3))) double* lds_cptr;
 __device__ inline double lds_b64(const double* p) {
-#if defined(GPMPC_LDS_MERGED)
-    return *p;
-#else
     lds_cptr q = (lds_cptr)p;
     asm volatile("" : "+v"(q));
     return *q;
-#endif
 }
 
 // Row records of the pairwise pass (one per memory point and output pair, broadcast from LDS to every lane of a wavefront).
@@ -169,37 +162,6 @@ __host__ __device__ inline Layout make_layout(int N, int D, int A, int E, int G,
     L.lds_total = q;
     L.pp_total = q - o;
     return L;
-}
-
-// ------------------------------------------------------------------------------------------
-// Wavefront sum on the DPP crossbar (no LDS round trips): inclusive scan inside each row of 16 lanes
-// (row_shr 1,2,4,8), then row_bcast:15 / row_bcast:31 carry the row totals up; lane 63 holds the
-// total, which is broadcast through an SGPR.  Fixed order => bitwise reproducible.
-template <int CTRL, int ROW_MASK>
-__device__ inline double dpp_shifted(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline double wave_sum(double v) {
-    v += dpp_shifted<0x111, 0xf>(v);      // row_shr:1
-    v += dpp_shifted<0x112, 0xf>(v);      // row_shr:2
-    v += dpp_shifted<0x114, 0xf>(v);      // row_shr:4
-    v += dpp_shifted<0x118, 0xf>(v);      // row_shr:8
-    v += dpp_shifted<0x142, 0xa>(v);      // row_bcast:15 -> rows 1, 3
-    v += dpp_shifted<0x143, 0xc>(v);      // row_bcast:31 -> rows 2, 3
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
-}
-
-// LDS hand-off between lanes of ONE wavefront (no workgroup barrier): LDS operations of a wave
-// complete in issue order; the fences keep the compiler from moving accesses across.
-__device__ inline void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // (Measured and not adopted, round 5 -- the serial phases of a horizon step, P1 3.6 k + P4 1.5 k + P5 1.4 k of 33 k cycles at config 2:
@@ -376,8 +338,6 @@ __device__ inline double taylor_exp(double c) {
     return p;
 }
 
-constexpr int kTPad = 72;      // zero rows appended to every T_a: a wave may run CH <= 64 rows past the data and prefetches 4 more
-
 // One (pair, row-chunk, column) item of the pairwise work, Taylor form.  `nrows` is wave-uniform and a
 // multiple of 4; rows beyond the data are zero padding and T is zero below its diagonal, so the loop
 // body carries no predication (scalar loop, loads issue ahead of the math).
@@ -435,41 +395,6 @@ __device__ inline double item_taylor(const double* rec, int nrows, const double 
         }
     }
     return acc;
-}
-
-// exp(x) for the direct (fallback) evaluation: x = (64 m + j) ln2/64 + r, |r| <= ln2/128,
-// exp(x) = 2^m * 2^(j/64) * (1 + r + r^2/2 + ... + r^5/120); 2^(j/64) from a 64-entry table, truncation
-// 3.5e-17, total error ~1 ulp.  No overflow/underflow special-casing: arguments on this path are sums of
-// log-kernel terms (<= a few units), and ldexp flushes tiny results to zero like exp does.
-__device__ const double kExp2Tab[64] = {
-    0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,
-    0x1.0b5586cf9890fp+0, 0x1.0e3ec32d3d1a2p+0, 0x1.11301d0125b51p+0, 0x1.1429aaea92de0p+0,
-    0x1.172b83c7d517bp+0, 0x1.1a35beb6fcb75p+0, 0x1.1d4873168b9aap+0, 0x1.2063b88628cd6p+0,
-    0x1.2387a6e756238p+0, 0x1.26b4565e27cddp+0, 0x1.29e9df51fdee1p+0, 0x1.2d285a6e4030bp+0,
-    0x1.306fe0a31b715p+0, 0x1.33c08b26416ffp+0, 0x1.371a7373aa9cbp+0, 0x1.3a7db34e59ff7p+0,
-    0x1.3dea64c123422p+0, 0x1.4160a21f72e2ap+0, 0x1.44e086061892dp+0, 0x1.486a2b5c13cd0p+0,
-    0x1.4bfdad5362a27p+0, 0x1.4f9b2769d2ca7p+0, 0x1.5342b569d4f82p+0, 0x1.56f4736b527dap+0,
-    0x1.5ab07dd485429p+0, 0x1.5e76f15ad2148p+0, 0x1.6247eb03a5585p+0, 0x1.6623882552225p+0,
-    0x1.6a09e667f3bcdp+0, 0x1.6dfb23c651a2fp+0, 0x1.71f75e8ec5f74p+0, 0x1.75feb564267c9p+0,
-    0x1.7a11473eb0187p+0, 0x1.7e2f336cf4e62p+0, 0x1.82589994cce13p+0, 0x1.868d99b4492edp+0,
-    0x1.8ace5422aa0dbp+0, 0x1.8f1ae99157736p+0, 0x1.93737b0cdc5e5p+0, 0x1.97d829fde4e50p+0,
-    0x1.9c49182a3f090p+0, 0x1.a0c667b5de565p+0, 0x1.a5503b23e255dp+0, 0x1.a9e6b5579fdbfp+0,
-    0x1.ae89f995ad3adp+0, 0x1.b33a2b84f15fbp+0, 0x1.b7f76f2fb5e47p+0, 0x1.bcc1e904bc1d2p+0,
-    0x1.c199bdd85529cp+0, 0x1.c67f12e57d14bp+0, 0x1.cb720dcef9069p+0, 0x1.d072d4a07897cp+0,
-    0x1.d5818dcfba487p+0, 0x1.da9e603db3285p+0, 0x1.dfc97337b9b5fp+0, 0x1.e502ee78b3ff6p+0,
-    0x1.ea4afa2a490dap+0, 0x1.efa1bee615a27p+0, 0x1.f50765b6e4540p+0, 0x1.fa7c1819e90d8p+0};
-
-__device__ inline double fast_exp(double x, const double* tab /* kExp2Tab copied to LDS */) {
-    const double n = __builtin_rint(x * 0x1.71547652b82fep+6);
-    double r = fma(n, -0x1.62e42fefa0000p-7, x);
-    r = fma(n, -0x1.cf79abc9e3b3ap-46, r);
-    const int ni = (int)n;
-    const double t = tab[ni & 63];
-    double q = fma(r, 0x1.1111111111111p-7, 0x1.5555555555555p-5);     // 1/120, 1/24
-    q = fma(q, r, 0x1.5555555555555p-3);                                 // 1/6
-    q = fma(q, r, 0.5);
-    const double p = fma(q * r, r, r);                                    // e^r - 1
-    return ldexp(fma(t, p, t), ni >> 6);
 }
 
 // Same item, direct form exp(ka'_i + kb'_j + g_i . w_j)  (row record [0] = ka'_i, [1] = beta_ai).
@@ -638,66 +563,6 @@ __device__ inline double wave_sum8(const double (&v)[8], int lane) {
     return r;
 }
 
-// Sums over the wavefront of 16 (8) values per lane without the LDS crossbar: the halving "transpose" steps ride on
-// v_permlane32_swap / v_permlane16_swap (gfx950: lanes 0-31 <-> 32-63, even <-> odd rows of 16) and on DPP row rotations with
-// bank masks (lane bits 3 and 2) -- one exchange hands over the half a lane gives up AND brings in the partner's half of what it
-// keeps, no selects -- then two quad_perm butterflies.  Lane l ends with the total of value (l >> 2) [& 7].  57 VALU instructions for
-// 16 values against ~70 plus six dependent ds_bpermute round trips for the 8 values of wave_sum8.  Fixed order.
-__device__ inline double dbl_of(unsigned lo, unsigned hi) { return __hiloint2double((int)hi, (int)lo); }
-
-template <int KIND>                     // 32: lane bit 5, 16: lane bit 4
-__device__ inline double swap_add(double a, double b) {
-    const unsigned a0 = (unsigned)__double2loint(a), a1 = (unsigned)__double2hiint(a);
-    const unsigned b0 = (unsigned)__double2loint(b), b1 = (unsigned)__double2hiint(b);
-    if constexpr (KIND == 32) {
-        const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-        return dbl_of(r0[0], r1[0]) + dbl_of(r0[1], r1[1]);
-    } else {
-        const auto r0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-        return dbl_of(r0[0], r1[0]) + dbl_of(r0[1], r1[1]);
-    }
-}
-
-template <int CTRL, int BANKS>
-__device__ inline double dpp_merge(double old, double src) {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xf, BANKS, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xf, BANKS, false);
-    return __hiloint2double(hi, lo);
-}
-
-// lanes with bit 3 (2) clear keep `a`, the others `b`; both get the partner's (lane ^ 8, lane ^ 4) share of what they keep
-__device__ inline double rot_add8(double a, double b) { return dpp_merge<0x128, 0x3>(b, a) + dpp_merge<0x128, 0xc>(a, b); }
-__device__ inline double rot_add4(double a, double b) { return dpp_merge<0x12c, 0x5>(b, a) + dpp_merge<0x124, 0xa>(a, b); }
-
-__device__ inline double quad_total(double r) {
-    r += dpp_merge<0x4e, 0xf>(r, r);          // quad_perm [2, 3, 0, 1]
-    r += dpp_merge<0xb1, 0xf>(r, r);          // quad_perm [1, 0, 3, 2]
-    return r;
-}
-
-__device__ inline double wave_reduce16(const double (&v)[16]) {
-    double w8[8], w4[4], w2[2];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w8[k] = swap_add<32>(v[k], v[k + 8]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w4[k] = swap_add<16>(w8[k], w8[k + 4]);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) w2[k] = rot_add8(w4[k], w4[k + 2]);
-    return quad_total(rot_add4(w2[0], w2[1]));
-}
-
-__device__ inline double wave_reduce8(const double (&v)[8]) {
-    double w4[4], w2[2];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w4[k] = swap_add<16>(v[k], v[k + 4]);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) w2[k] = rot_add8(w4[k], w4[k + 2]);
-    const double r = quad_total(rot_add4(w2[0], w2[1]));
-    return swap_add<32>(r, r);
-}
-
 // ------------------------------------------------------------------------------------------
 // Separable moments for three state dimensions with the monomial structure known at compile time.
 // Bands of at most 16 monomials (ranges of the x0 exponent i and, where needed, of the x1 exponent j); fewer, larger
@@ -827,20 +692,6 @@ __device__ __attribute__((noinline)) void sep3_item(int band, int lane, int N, i
     }
 }
 
-__device__ inline int wave_max_i32(int v) {
-    auto step = [&](auto ctrl, auto rmask) {
-        const int o = __builtin_amdgcn_update_dpp(0, v, decltype(ctrl)::value, decltype(rmask)::value, 0xf, true);
-        v = o > v ? o : v;
-    };
-    step(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});
-    step(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});
-    step(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});
-    step(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});
-    step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});
-    step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});
-    return __builtin_amdgcn_readlane(v, 63);        // values are >= 0, so the zero fill is neutral
-}
-
 // ------------------------------------------------------------------------------------------
 // DX = exact state dimension known at compile time (0: runtime p.D <= DP): folds every D-dependent
 // offset and small loop, which is what keeps the 128-VGPR budget of a 1024-thread workgroup.
@@ -965,7 +816,6 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
     int* c_monoe = reinterpret_cast<int*>(smem + L.c_monoe);
     const double* act = p.actions + (size_t)c * H * A;
 
-    [[maybe_unused]] int t_dbg = -1;
 #if defined(GPMPC_PROF_ON)
     long long prof_x[3] = {0, 0, 0};
     long long prof_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1054,7 +904,6 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
         }
     }
     __syncthreads();
-#if !defined(GPMPC_NO_LANEMAP)
     bool use_lmap = false;
     if constexpr (!TILED) {
         const int wtri = (s_tri[p.RC] + 63) >> 6;
@@ -1085,9 +934,6 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
         }
         __syncthreads();
     }
-#else
-    constexpr bool use_lmap = false;
-#endif
     GPMPC_TRACE(1);
     if (!TILED && member == 0) {
         for (int i = tid; i < D; i += NT) p.mu_out[((size_t)c * (H + 1)) * D + i] = s_mu[i];
@@ -1166,10 +1012,6 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
     };
     [[maybe_unused]] auto acquire = [&](int vi) -> double {
         const unsigned long long* g = x_cur + 2 * (size_t)vi;
-#if defined(GPMPC_CL_DEBUG)
-        if (p.cl_dbg & 1) return 0.0;                                  // timing experiments: no wait at all / one read, no check
-        if (p.cl_dbg & 2) { const unsigned long long a = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return (double)a; }
-#endif
         for (int spins = 0; spins < (1 << 21); ++spins) {           // bounded: a member that never arrives must not hang the GPU
             const unsigned long long a = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long b = __hip_atomic_load(g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1207,7 +1049,6 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
     int cur = 0;
     const int tid_outer = tid;
     for (int t = TILED ? p.t_begin : 0; t < (TILED ? p.t_end : H); ++t) {
-        t_dbg = t;
         // Re-derive the thread coordinates inside every step from an opaque copy: otherwise the compiler
         // hoists dozens of per-thread address computations out of the horizon loop and keeps them live
         // across all phases, which overflows the 128-VGPR budget of a 1024-thread workgroup (spills).
@@ -2072,7 +1913,7 @@ __device__ __forceinline__ void traj_cost_body(int c, int lane, const double* __
         if (cv_out) cv_out[(size_t)c * (H + 1) + t] = cv;
     }
     // fixed-order sum over lanes (lane l holds steps l, l + 64, ...)
-    for (int off = 32; off >= 1; off >>= 1) jsum += __shfl_xor(jsum, off, 64);
+    jsum = wave_xor_sum(jsum);
     if (lane == 0 && J_out) J_out[c] = jsum / (double)(H + 1);
 }
 

@@ -79,8 +79,6 @@ __device__ inline double wave_gauss_solve(double* aug, int D, int nrhs, int ld, 
     return det;
 }
 
-typedef double mfma_d4 __attribute__((ext_vector_type(4)));
-
 // Row stride of the staged records: DP + 2 doubles.  Round-4 experiments on the A-operand reads of the matrix-core pass (lane l:
 // component 4 q + (l >> 4) of row l & 15), which the compiler emits as ds_read2_b64 pairs -- serviced per 16-lane group with
 // banks taken mod 32, so that at a stride of 18 doubles (36 dwords = 4 mod 32) rows r and r + 8 collide: 16 LDS cycles per
@@ -97,7 +95,7 @@ __host__ __device__ constexpr int stream_row_stride(int DP) { return DP + 2; }
 
 // c tiles of TWO 16-row tiles (rows 16 t0 .., 16 t0 + 16 ..) of the stage against the wave's 16 columns.
 template <int DP>
-__device__ inline void mfma_c_tiles(const double* st, int t0, const double (&bw)[DP / 4], int lane, mfma_d4& c0, mfma_d4& c1) {
+__device__ inline void mfma_c_tiles(const double* st, int t0, const double (&bw)[DP / 4], int lane, d4& c0, d4& c1) {
     constexpr int RS = stream_row_stride(DP);
     const double* a0p = st + (size_t)(16 * t0 + (lane & 15)) * RS + 2 + (lane >> 4);
     const double* a1p = a0p + 16 * RS;
@@ -134,7 +132,7 @@ __device__ inline double block_mfma_taylor(const double* st, int ntiles, const d
                 wt[4 + r] = Tp[(size_t)(16 * t + 16 + 4 * r) * N];
             }
         }
-        mfma_d4 c0, c1;
+        d4 c0, c1;
         mfma_c_tiles<DP>(st, t, bw, lane, c0, c1);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -196,7 +194,7 @@ __device__ inline double block_mfma_table(const double* st, int ntiles, const do
                 wt[4 + r] = Tp[(size_t)(16 * t + 16 + 4 * r) * N];
             }
         }
-        mfma_d4 c0, c1;
+        d4 c0, c1;
         mfma_c_tiles<DP>(st, t, bw, lane, c0, c1);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -253,7 +251,7 @@ __device__ inline double block_mfma_exp(const double* st, int ntiles, const doub
                 wt[4 + r] = Tp[(size_t)(16 * t + 16 + 4 * r) * N];
             }
         }
-        mfma_d4 c0, c1;
+        d4 c0, c1;
         mfma_c_tiles<DP>(st, t, bw, lane, c0, c1);
         double arg[8];
 #pragma unroll
@@ -351,7 +349,7 @@ __global__ __launch_bounds__(NT) void rollout_stream_kernel(const RolloutArgs p)
     for (int i = tid0; i < D * E; i += NT) c_ils2[i] = p.ils2[i];
     for (int i = tid0; i < 2 * E; i += NT) c_xr[i] = p.xrange[i];
     for (int i = tid0; i < H * A; i += NT) c_act[i] = act[i];
-    for (int i = tid0; i < 64; i += NT) c_exptab[i] = kExp2Tab[i];
+    stage_exp_tab(c_exptab, tid0, NT);
     double* c_etab = smem + L.c_etab + kTableHalf;                     // centre of the table
     double* s_ush = smem + L.ush;
     if constexpr (kMfma) {

@@ -41,6 +41,7 @@ SIGNATURES = {
     "gpmpc_get_factors": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "gpmpc_read_factors": (C.c_int, [_P, _P, _P, _P]),
     "gpmpc_predict": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "gpmpc_predict_backward": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_last_prepare_mode": (C.c_int, [_P]),

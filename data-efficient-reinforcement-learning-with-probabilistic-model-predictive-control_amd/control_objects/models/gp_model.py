@@ -55,6 +55,28 @@ class _MomentsFunction(torch.autograd.Function):
         return None, mu_bar, var_bar
 
 
+class _PredictFunction(torch.autograd.Function):
+    """engine.predict as an autograd node: inputs (M, E) -> (mean, var) (M, D), the variance with `noises` (D,) added when they
+    are given (a constant: no gradient); its backward is engine.predict_backward (gpmpc_predict_backward).  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, engine, noises, inputs):
+        ctx.engine = engine
+        ctx.set_materialize_grads(False)          # an unused output is a NULL upstream gradient (no var: no matrix product)
+        ctx.save_for_backward(inputs)
+        out = engine.predict(inputs, noises=noises)
+        return out["mean"], out["var"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, mean_bar, var_bar):
+        inputs, = ctx.saved_tensors
+        if (mean_bar is None and var_bar is None) or not ctx.needs_input_grad[2]:
+            return None, None, None
+        g = ctx.engine.predict_backward(inputs.detach(), mean_bar, var_bar)
+        return None, None, g.to(device=inputs.device, dtype=inputs.dtype)
+
+
 class _TrajectoryFunction(torch.autograd.Function):
     """engine.rollout as an autograd node: (actions (B, H, A), obs_mu (D,), obs_var (D, D)) -> the rollout's outputs named by
     ctx.keys (mu, Sig and, where the rollout returns them, cost_mu, cost_var, J; copied into `keys_out`); its backward is engine.rollout_backward
@@ -406,11 +428,17 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
     def predict(self, inputs, include_noise=True):
         """GP posterior at the model inputs (M, E) -> (mean, var), DEVICE tensors (M, D): what the reference's model plot gets
         from likelihood(model(x)) (static_3d_graph.py:77-80, 116) -- the exact posterior, with each GP's noise added when
-        `include_noise` (without it: the latent function's variance)."""
+        `include_noise` (without it: the latent function's variance).  Differentiable in `inputs` like the reference's
+        expression: when grad mode is on and `inputs` requires grad, both outputs carry a grad_fn and backward() reaches the
+        inputs (CPU or device) through gpmpc_predict_backward.  The noise is a constant; hyper-parameters and the memory get no
+        gradient, and double backward raises."""
         if self.x_mem is None:
             raise RuntimeError("call prepare_inference(inputs, state_changes) before predict")
-        out = self.engine.predict(inputs, noises=self.noises.detach().cpu().numpy() if include_noise else None)
-        return out["mean"], out["var"]
+        noises = self.noises.detach().cpu().numpy() if include_noise else None
+        if not (torch.is_grad_enabled() and isinstance(inputs, torch.Tensor) and inputs.requires_grad):
+            out = self.engine.predict(inputs, noises=noises)
+            return out["mean"], out["var"]
+        return _PredictFunction.apply(self.engine, noises, _t(inputs))
 
     def predict_next_state_change(self, input_mu, input_var):
         """Same signature / return as the reference (:112-180): one Gaussian model input, mean (E,) and covariance (E, E) ->

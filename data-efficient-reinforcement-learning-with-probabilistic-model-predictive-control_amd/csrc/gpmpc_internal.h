@@ -206,6 +206,7 @@ struct Handle {
     Buf tilews;   // batch-major path: step records of the candidates | per-tile partial sums | hand-over flags
     Buf tgradws;  // gradient's tile pass: records of a block of (candidate, step) items | per-tile partial moments
     Buf predws;   // gpmpc_predict: per-(query row, column block) partial sums of one chunk of query rows
+    Buf predbws;  // gpmpc_predict_backward: per-(output, column block, query row, input) partial sums of one chunk of query rows
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
@@ -290,6 +291,7 @@ struct Handle {
     int opt_fused_prepare = 1;       // N <= 256: the whole factorisation in one launch (prepare_small.hip); 0: panel path (A/B, tests)
     int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
+    int opt_predict_bwd_chunk = 0;   // gpmpc_predict_backward: the same for its chunks
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int lds_limit = 160 * 1024;
@@ -466,6 +468,9 @@ int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const
 int grow(Handle* h, Buf& b, size_t need);
 // predict.hip: posterior mean / variance at M query inputs from the cached model (mean_out / var_out may be NULL)
 int run_predict(Handle* h, const double* Xq, int M, const double* noises_host, double* mean_out, double* var_out, hipStream_t s);
+// ... and its gradient wrt Xq for upstream mean_bar / var_bar (each may be NULL = 0), written to Xq_bar (M, E)
+int run_predict_backward(Handle* h, const double* Xq, int M, const double* mean_bar, const double* var_bar, double* Xq_bar,
+                         hipStream_t s);
 // moments.hip: moment-matched prediction at P Gaussian inputs from the cached model (Sig NULL = 0; S_out / V_out may be NULL)
 int run_moments(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                 hipStream_t s);

@@ -187,6 +187,25 @@ class HipEngine:
         self._keep_predict = Xq              # alive until the asynchronous call has read it
         return out
 
+    def predict_backward(self, Xq, mean_bar=None, var_bar=None):
+        """Reverse-mode product of `predict` (autograd through likelihood(model(x)) with respect to x): Xq (M, E), upstream
+        gradients mean_bar (M, D) and var_bar (M, D), each None for zero -> Xq_bar (M, E), a device tensor.  The noise added
+        by `predict` is a constant and takes no part.  Without var_bar no matrix product runs.  Asynchronous on the current
+        stream."""
+        Xq = self._dev(Xq)
+        if Xq.dim() != 2:
+            raise ValueError(f"expected query inputs of shape (M, E), got {tuple(Xq.shape)}")
+        M, E = Xq.shape
+        D = self.D
+        mb = self._dev(mean_bar, (M, D)) if mean_bar is not None else None
+        vb = self._dev(var_bar, (M, D)) if var_bar is not None else None
+        out = torch.empty((M, E), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_predict_backward(self._h, Xq.data_ptr(), M, D, E, ptr(mb), ptr(vb), out.data_ptr(),
+                                                    self._stream()))
+        self._keep_predict_backward = (Xq, mb, vb)   # alive until the asynchronous call has read them
+        return out
+
     def moments(self, mu, var=None, S=True, V=True):
         """Moment-matched one-step prediction (predict_next_state_change, gp_model.py:112-180) at P Gaussian inputs from the
         cached model: mu (P, E), var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D), V (P, E, D)) of device tensors

@@ -79,6 +79,29 @@ int gpmpc_predict(gpmpc_t* h, const double* Xq_dev, int M, int D, int E, const d
                   double* var_out_dev, void* stream);
 
 /*
+ * gpmpc_predict_backward  <->  torch autograd through likelihood(model(x)) with respect to x (static_3d_graph.py:77-80, 116): the
+ * reverse-mode product (vector-Jacobian product) of gpmpc_predict at the same M query inputs.  For upstream gradients mean_bar,
+ * var_bar it returns the gradient of <mean_bar, mean> + <var_bar, var> with respect to Xq:
+ *   c_amj = mean_bar_ma beta_aj - 2 var_bar_ma P_amj   (P_a = K*_a iK_a, k_amj = k_a(x*_m)_j as in gpmpc_predict)
+ *   Xq_bar_me = sum_a (1 / l_ae^2) sum_j c_amj k_amj (x_je - x*_me)
+ *   Xq_dev (M,E)          query inputs, as in gpmpc_predict
+ *   mean_bar_dev (M,D)    upstream gradient of the mean, or NULL (= 0)
+ *   var_bar_dev (M,D)     upstream gradient of the variance, or NULL (= 0): then no matrix product is run (O(N E D) per query);
+ *                         with both NULL the call writes zeros and launches no tile kernel
+ *   Xq_bar_out_dev (M,E)  required; overwritten, not accumulated into
+ * The likelihood noise gpmpc_predict may add is a constant: it has no gradient, and this entry takes none.  2 K* iK is the
+ * gradient of k^T iK k only for a symmetric iK: prepare and mll store iK exactly symmetric; a non-symmetric iK passed through
+ * gpmpc_set_factors gets 2 K* iK, not K* (iK + iK^T).  Uses whatever prepare / set_factors / mll cached last.  A point's gradient
+ * is bitwise the same whatever M is, wherever it sits in the batch, whatever its neighbours are and however the call chunks the
+ * rows internally (workspace within 4 MB, or one 64-row tile's need if that is more: 2.6 MB at N = 4096, D = 16, E = 20); a NULL
+ * upstream and an all-zero one give the same bits.  Touches no other workspace and no gpmpc_last_* state.  Asynchronous on
+ * `stream`; M = 0 launches nothing.  GPMPC_ERR_ARG: no cached model, D / E different from the cached model, M < 0, Xq_dev or
+ * Xq_bar_out_dev NULL with M > 0.
+ */
+int gpmpc_predict_backward(gpmpc_t* h, const double* Xq_dev, int M, int D, int E, const double* mean_bar_dev,
+                           const double* var_bar_dev, double* Xq_bar_out_dev, void* stream);
+
+/*
  * gpmpc_moments  <->  predict_next_state_change(input_mu, input_var) (gp_model.py:112-180) at P independent Gaussian model inputs
  * N(m_p, Sigma_p): the moment-matched one-step prediction of the state change, with a general symmetric E x E Sigma_p (any block
  * may be non-zero: state, action and time inputs alike; the rollouts only ever pass a state-block one).
@@ -129,7 +152,8 @@ int gpmpc_moments_backward(gpmpc_t* h, const double* mu_dev, const double* var_d
  * 1 always, 2 never).  Dispatch hooks of the parity tests: "rows_per_chunk", "cols_per_lane", "force_path" (1 direct exp,
  * 2 element-wise Taylor), "force_separable", "force_global_scratch", "grad_separable" / "grad_tiles" / "grad_stream" /
  * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
- * query rows per internal chunk: 0 auto, else a multiple of 64), "moments_chunk_points" (gpmpc_moments' points per internal
+ * query rows per internal chunk: 0 auto, else a multiple of 64), "predict_backward_chunk_rows" (the same for
+ * gpmpc_predict_backward), "moments_chunk_points" (gpmpc_moments' points per internal
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */

@@ -44,6 +44,7 @@ SIGNATURES = {
     "gpmpc_predict_backward": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_forget": (C.c_int, [_P, C.POINTER(_I), _I, _P]),
     "gpmpc_last_prepare_mode": (C.c_int, [_P]),
     "gpmpc_last_rollout_path": (C.c_int, [_P]),
     "gpmpc_last_grad_path": (C.c_int, [_P]),
@@ -65,7 +66,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def load(path=LIB_PATH):

@@ -61,11 +61,16 @@ class ActionsConfig:
 
 class MemoryConfig:
     def __init__(self, check_errors_for_storage=True, min_error_prediction_state_for_memory=(3e-4, 3e-4, 3e-4),
-                 min_prediction_state_std_for_memory=(3e-3, 3e-3, 3e-3), points_batch_memory=1500):
+                 min_prediction_state_std_for_memory=(3e-3, 3e-3, 3e-3), points_batch_memory=1500, max_points_model=None):
         self.check_errors_for_storage = check_errors_for_storage
         self.min_error_prediction_state_for_memory = list(min_error_prediction_state_for_memory)
         self.min_prediction_state_std_for_memory = list(min_prediction_state_std_for_memory)
         self.points_batch_memory = points_batch_memory
+        # cap of the GP memory (None: it only grows, as in the reference): beyond it Memory.prepare_for_model evicts the oldest
+        # model points -- a sliding window, the natural memory of time-varying dynamics modelled with a time input
+        if max_points_model is not None and int(max_points_model) < 1:
+            raise ValueError(f"MemoryConfig.max_points_model={max_points_model!r}: None or a positive number of points")
+        self.max_points_model = None if max_points_model is None else int(max_points_model)
         _tensorise_lists(self)
 
 

@@ -34,7 +34,7 @@ from ..observations_states_mappers.normalization_observation_state_mapper import
 from ..states_reward_mappers.setpoint_distance_reward_mapper import SetpointStateRewardMapper
 from .abstract_controller import BaseControllerObject
 from .iteration_info_class import IterationInformation
-from ..._lib import GPMPC_ERR_LIMIT, GpmpcError
+from ..._lib import GPMPC_ERR_ARG, GPMPC_ERR_LIMIT, GpmpcError
 
 F64 = torch.float64
 FD_STEP = 1e-3           # 4th-order stencil: truncation ~ h^4, rounding ~ 1e-13 / h
@@ -239,6 +239,7 @@ class GpMpcController(BaseControllerObject):
                 for model, p in zip(self.transition_model.models, params):
                     model.initialize(**p)
             self.p_train.close()
+            self.memory.pop_evicted()          # new hyper-parameters: the whole memory is factorised anyway
             x_mem, y_mem = self.memory.get()
             self.transition_model.prepare_inference(x_mem, y_mem)
 
@@ -293,6 +294,20 @@ class GpMpcController(BaseControllerObject):
         self.cost_traj_mean_lcb = -packed[o[4]].clone()
 
     def _prepare(self):
+        # a capped memory (MemoryConfig.max_points_model) evicted its oldest points: they leave the cached factors by a
+        # downdate, and the prepare below border-updates the appended ones -- no factorisation at steady state.  The downdate is
+        # an economy, never a need: where it cannot be made -- evictions the model cannot match to rows it holds (nothing
+        # prepared yet, points that came and went between two prepares), an engine without `forget`, or one that holds no
+        # record to downdate from (GPMPC_ERR_ARG: e.g. after a failed factorisation) -- the prepare below sees a different
+        # memory and factorises the window in full.
+        evicted = self.memory.pop_evicted()
+        x_old = self.transition_model.x_mem
+        if len(evicted) and x_old is not None and len(evicted) < len(x_old) and hasattr(self.transition_model.engine, "forget"):
+            try:
+                self.transition_model.forget(evicted)
+            except GpmpcError as e:
+                if e.code != GPMPC_ERR_ARG:
+                    raise
         x_mem, y_mem = self.memory.get()
         self.transition_model.prepare_inference(x_mem, y_mem)
 

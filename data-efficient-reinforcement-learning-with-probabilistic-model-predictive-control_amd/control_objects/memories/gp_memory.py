@@ -30,6 +30,7 @@ class Memory:
         self.len_mem = 0
         self.len_mem_last_processed = 0
         self.len_mem_model = 0
+        self._evicted_pending = 0       # model points evicted (always the oldest) since the last pop_evicted
 
     @staticmethod
     def _grown(t, extra):
@@ -91,6 +92,21 @@ class Memory:
         self.model_targets[self.len_mem_model:self.len_mem_model + n_new] = y
         self.len_mem_model += n_new
         self.len_mem_last_processed = self.len_mem
+        cap = getattr(self.config, "max_points_model", None)
+        if cap is not None and self.len_mem_model > cap:
+            # sliding window: the oldest model points leave.  New tensors, not a shift in place: views handed out by get()
+            # (the model's x_mem / y_mem) keep the rows they were given.  The raw replay arrays and the mask stay as they are.
+            k = self.len_mem_model - cap
+            self.model_inputs = self._grown(self.model_inputs[k:], k)
+            self.model_targets = self._grown(self.model_targets[k:], k)
+            self.len_mem_model = cap
+            self._evicted_pending += k
+
+    def pop_evicted(self):
+        """Positions, in the model memory as it stood at the previous call (oldest first, before anything was appended), of the
+        points evicted since then -- always the oldest ones, so 0 .. k-1.  Consumed by the call: the next one starts empty."""
+        k, self._evicted_pending = self._evicted_pending, 0
+        return np.arange(k)
 
     def get_memory_total(self):
         return self.get_memory_by_index(self.get_indexes_processed())

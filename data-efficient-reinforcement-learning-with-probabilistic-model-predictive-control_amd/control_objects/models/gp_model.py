@@ -349,6 +349,19 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self.y_mem = state_changes
         self.engine.prepare(inputs, state_changes, self.lengthscales, self.variances, self.noises)
 
+    def forget(self, indices):
+        """Drop the memory points `indices` (strictly ascending rows of the memory of the last prepare_inference) from the
+        cached model (gpmpc_forget, O(k N^2)) and from x_mem / y_mem, so that save_state ships the reduced memory to training.
+        A prepare_inference of the reduced memory plus a few appended points is then a border update, not a factorisation."""
+        if self.x_mem is None:
+            raise RuntimeError("call prepare_inference(inputs, state_changes) before forget")
+        idx = np.asarray(indices).reshape(-1)
+        self.engine.forget(idx)
+        keep = torch.ones(len(self.x_mem), dtype=torch.bool)
+        keep[torch.as_tensor(idx, dtype=torch.long)] = False
+        self.x_mem = _t(self.x_mem)[keep]
+        self.y_mem = _t(self.y_mem)[keep]
+
     def set_cost(self, reward_config):
         """Load the quadratic-cost / LCB settings into the engine.  The reference reads its reward config on every
         evaluation (setpoint_distance_reward_mapper.py:36-66), so in-place edits of the config must take effect:

@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 12; }
+int gpmpc_abi_version(void) { return 13; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -81,12 +81,13 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->momws, &h->mombws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->momws, &h->mombws, &h->Xf, &h->Yf, &h->fgws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
     if (h->xch_uc) (void)hipFree(h->xch_uc);
     if (h->info) (void)hipFree(h->info);
+    if (h->fidx) (void)hipFree(h->fidx);
     if (h->mono_exp) (void)hipFree(h->mono_exp);
     if (h->septab) (void)hipFree(h->septab);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -276,6 +277,20 @@ int gpmpc_mll(gpmpc_t* g, const double* X, const double* Y, const double* ls, co
     if (rc) return rc;
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     return run_mll(H_(g), X, Y, ls, os, noise, N, D, E, out_host, (hipStream_t)stream);
+}
+
+int gpmpc_forget(gpmpc_t* g, const int* idx_host, int k, void* stream) {
+    Range roctx_range("gpmpc_forget");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready || !h->have_state) return bad(g, "forget: the handle holds no record of a gpmpc_prepare");
+    if (!idx_host) return bad(g, "null argument");
+    if (k < 1 || k >= h->N) return bad(g, "forget: need 1 <= k < N");
+    for (int q = 0; q < k; ++q)
+        if (idx_host[q] < 0 || idx_host[q] >= h->N || (q > 0 && idx_host[q] <= idx_host[q - 1]))
+            return bad(g, "forget: indices must be strictly ascending and in [0, N)");
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_forget(h, idx_host, k, (hipStream_t)stream);
 }
 
 int gpmpc_last_prepare_mode(gpmpc_t* g) { return g ? g->h.last_prepare_mode : GPMPC_ERR_ARG; }

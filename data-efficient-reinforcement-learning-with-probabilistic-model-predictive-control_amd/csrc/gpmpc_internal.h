@@ -222,6 +222,11 @@ struct Handle {
     int* mismatch = nullptr;     // device flag of the prefix comparison
     int inc_updates = 0;         // border updates since the last full factorisation
     bool have_state = false;     // Xc / Yc / hyp describe the cached factors
+    // gpmpc_forget: the record's ping-pong partners, the downdate's coefficients | a copy of hyp for the full path, removed rows
+    Buf Xf, Yf;   // (N, E), (N, D): trade places with Xc / Yc
+    Buf fgws;
+    int* fidx = nullptr;         // device copy of the removed rows when there are more than 8
+    size_t fidx_cap = 0;         // ints
     Buf hio;      // gpmpc_objective_grad_host: actions | J | grad | mu | Sig | cost_mu | cost_var of one candidate (device side)
     double* hio_host = nullptr;      // ... and its pinned, device-mapped host mirror (results)
     double* hio_host_dev = nullptr;
@@ -289,7 +294,7 @@ struct Handle {
     int opt_prepare_overlap = 1;     // 32-wide panel path: the inverse's launches on a side stream beside the factorisation's (0: one stream, A/B)
     int opt_gram_shared = 1;         // large N: K of all GPs by one workgroup per tile, squared differences shared (0: per-GP kernel, A/B)
     int opt_fused_prepare = 1;       // N <= 256: the whole factorisation in one launch (prepare_small.hip); 0: panel path (A/B, tests)
-    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit)
+    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
     int opt_predict_bwd_chunk = 0;   // gpmpc_predict_backward: the same for its chunks
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
@@ -425,6 +430,13 @@ struct PreparePlan {
     SyrkInvForm syrk;
 };
 
+// Rows gpmpc_forget removes, ascending (kernel argument): up to 8 ride in the block itself, more come from device memory
+struct ForgetRows {
+    int k;
+    int few[8];
+    const int* many;
+};
+
 // rollout.hip
 int ensure_rollout_tables(Handle* h, int N, int D);      // what the plan reads: monomial tables, the batch-major path's bands
 int plan_rollout(const Handle& h, int N, int D, int A, int E, int H, int Bp, const RolloutRequest& req, RolloutPlan& p);
@@ -466,6 +478,11 @@ int ensure_model_buffers(Handle* h, int N, int D, int E, bool need_factor_ws);
 int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
             int N, int D, int E, double* out_host, hipStream_t s);
 int grow(Handle* h, Buf& b, size_t need);
+// ... gpmpc_forget: rows idx_host (validated: strictly ascending, in range, 1 <= k < N) leave the cached model
+int run_forget(Handle* h, const int* idx_host, int k, hipStream_t s);
+// forget.hip: one removal (iK, linv, beta) -> (gram, Tm, zvec); the record (and, with `tables`, X^T and the data range) without the rows
+int launch_forget_step(Handle* h, int n, int j, int D, int ldw, hipStream_t s);
+int launch_forget_pack(Handle* h, const ForgetRows& rm, int n1, int D, int E, double* Xn, double* Yn, bool tables, hipStream_t s);
 // predict.hip: posterior mean / variance at M query inputs from the cached model (mean_out / var_out may be NULL)
 int run_predict(Handle* h, const double* Xq, int M, const double* noises_host, double* mean_out, double* var_out, hipStream_t s);
 // ... and its gradient wrt Xq for upstream mean_bar / var_bar (each may be NULL = 0), written to Xq_bar (M, E)

@@ -1627,6 +1627,66 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
     return GPMPC_OK;
 }
 
+// gpmpc_forget: the cached model without the rows idx (validated by the caller), in the state run_prepare would leave for the
+// reduced memory.  k downdates from the highest row down (the earlier rows keep their positions), each a compaction into the
+// ping-pong partners of the border update; then T, X^T, the data range and the record.  Removals count toward
+// "refresh_every" like appended points: past it (or with "incremental" = 0) the reduced memory is factorised in full from
+// the record, by the launcher run_prepare plans.
+int run_forget(Handle* h, const int* idx, int k, hipStream_t s) {
+    const int N = h->N, D = h->D, E = h->E, n1 = N - k;
+    const size_t DE = (size_t)D * E, nhyp = DE + 2 * (size_t)kMaxD;
+    int rc;
+    if ((rc = grow(h, h->Xf, h->Xc.cap))) return rc;
+    if ((rc = grow(h, h->Yf, h->Yc.cap))) return rc;
+    if ((rc = grow(h, h->fgws, (size_t)5 * D * N + D + nhyp))) return rc;
+    ForgetRows rm{};
+    rm.k = k;
+    if (k <= 8) {
+        for (int q = 0; q < k; ++q) rm.few[q] = idx[q];
+    } else {
+        if (h->fidx_cap < (size_t)k) {
+            if (h->fidx) GPMPC_HIP_CHECK(h, hipFree(h->fidx));
+            h->fidx = nullptr; h->fidx_cap = 0;
+            GPMPC_HIP_CHECK(h, hipMalloc(&h->fidx, (size_t)k * sizeof(int)));
+            h->fidx_cap = (size_t)k;
+        }
+        GPMPC_HIP_CHECK(h, hipMemcpy(h->fidx, idx, (size_t)k * sizeof(int), hipMemcpyHostToDevice));
+        rm.many = h->fidx;
+    }
+    const size_t NN = (size_t)D * N * N, TN = (size_t)D * (N + kTPad) * N, DN = (size_t)D * N;
+    const bool downdate = h->opt_incremental && h->inc_updates + k <= h->opt_refresh_every && fits(h->iK, NN) && fits(h->gram, NN) &&
+                          fits(h->linv, TN) && fits(h->Tm, TN) && fits(h->beta, DN) && fits(h->zvec, DN);
+    if (!downdate) {
+        double* hyp = h->fgws.p + (size_t)5 * D * N + D;           // run_prepare rewrites h->hyp while it reads these
+        GPMPC_HIP_CHECK(h, hipMemcpyAsync(hyp, h->hyp.p, nhyp * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if ((rc = launch_forget_pack(h, rm, n1, D, E, h->Xf.p, h->Yf.p, false, s))) return rc;
+        return run_prepare(h, h->Xf.p, h->Yf.p, hyp, hyp + DE, hyp + DE + kMaxD, n1, D, E, s, false);
+    }
+    // From the first launch on the buffers trade places: a HIP error on the way leaves no model (ready and the record are dropped,
+    // as after a failed factorisation) instead of a half-updated one.
+    h->ready = false;
+    h->have_state = false;
+    int n = N;
+    for (int q = k - 1; q >= 0; --q, --n) {                        // (info is zero when idle: check_info clears it after a failure)
+        if ((rc = launch_forget_step(h, n, idx[q], D, N, s))) return rc;
+        Buf t = h->iK; h->iK = h->gram; h->gram = t;
+        t = h->linv; h->linv = h->Tm; h->Tm = t;
+        t = h->beta; h->beta = h->zvec; h->zvec = t;
+    }
+    hipLaunchKernelGGL(tm_kernel, dim3((n1 + 63) / 64, (n1 + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, n1, h->Tm.p,
+                       nullptr);
+    if ((rc = launch_forget_pack(h, rm, n1, D, E, h->Xf.p, h->Yf.p, true, s))) return rc;
+    Buf t = h->Xc; h->Xc = h->Xf; h->Xf = t;
+    t = h->Yc; h->Yc = h->Yf; h->Yf = t;
+    if ((rc = check_info(h, D, s))) return rc;
+    h->N = n1;
+    h->ready = true;
+    h->have_state = true;
+    h->inc_updates += k;
+    h->last_prepare_mode = 3;
+    return GPMPC_OK;
+}
+
 int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
             int N, int D, int E, double* out_host, hipStream_t s) {
     // always a fresh factorisation: the hyper-parameters are the variables

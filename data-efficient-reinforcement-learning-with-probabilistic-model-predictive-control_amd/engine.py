@@ -121,9 +121,24 @@ class HipEngine:
         return {"loss": out[:, 0].copy(), "d_lengthscale": out[:, 1:1 + E].copy(), "d_outputscale": out[:, 1 + E].copy(),
                 "d_noise": out[:, 2 + E].copy()}
 
+    def forget(self, indices):
+        """Remove the memory points `indices` (strictly ascending rows of the X / Y of the last `prepare`) from the cached
+        model (gpmpc_forget): afterwards the engine is in the state `prepare` would leave for the reduced memory, so a
+        `prepare` of the reduced memory plus a few appended points is a border update.  O(k N^2), synchronises the current
+        stream.  `last_prepare_mode` is 3 (downdate), or 0 where the reduced memory was factorised in full (refresh interval,
+        "incremental" = 0).  Bad indices, or an engine without the record of a `prepare`: GpmpcError(GPMPC_ERR_ARG), the
+        cached model untouched."""
+        idx = np.asarray(indices).reshape(-1)
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise TypeError("forget: indices must be integers")
+        # (clipped so that an index beyond 32 bits stays out of range instead of wrapping into it)
+        idx = np.ascontiguousarray(np.clip(idx, -1, 2 ** 31 - 1), dtype=np.int32)
+        self._check(self.lib.gpmpc_forget(self._h, idx.ctypes.data_as(C.POINTER(C.c_int)), int(idx.size), self._stream()))
+        self.N -= int(idx.size)
+
     @property
     def last_prepare_mode(self):
-        """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit."""
+        """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit, 3 = downdate (`forget`)."""
         return int(self.lib.gpmpc_last_prepare_mode(self._h))
 
     @property

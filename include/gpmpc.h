@@ -43,11 +43,30 @@ const char* gpmpc_last_error(const gpmpc_t* h);
  *   X_dev (N,E)  Y_dev (N,D)  lengthscales_dev (D,E)  outputscales_dev (D)  noises_dev (D)
  * Synchronises `stream` (a failed factorisation is reported here: GPMPC_ERR_NOT_PD).  Reuse across control steps (the reference
  * refactorises every step, gp_mpc_controller.py:117): gpmpc_last_prepare_mode = 0 full factorisation, 1 border update (the
- * cached memory plus <= 8 appended points, same hyper-parameters), 2 cache hit.
+ * cached memory plus <= 8 appended points, same hyper-parameters), 2 cache hit, 3 downdate (gpmpc_forget).
  */
 int gpmpc_prepare(gpmpc_t* h, const double* X_dev, const double* Y_dev, const double* lengthscales_dev,
                   const double* outputscales_dev, const double* noises_dev, int N, int D, int E, void* stream);
 int gpmpc_last_prepare_mode(gpmpc_t* h);
+
+/*
+ * gpmpc_forget: the memory points idx_host (k rows of the X / Y of the last gpmpc_prepare) leave the cached model -- the
+ * shrinking half of the incremental factorisation (the reference has no counterpart: its memory only grows, gp_memory.py, and
+ * is refactorised every step).  Afterwards the handle is in the state gpmpc_prepare would leave for the reduced (X, Y) with the
+ * same hyper-parameters: iK, beta, the tables of the rollouts, N, and the record the reuse rules of gpmpc_prepare compare
+ * against -- so a following gpmpc_prepare of the reduced memory plus <= 8 appended points is a border update (mode 1, with nothing
+ * appended a cache hit), and predict / moments / the rollouts and their gradients run on the reduced model with no further call.
+ *   idx_host (k)  rows to remove: strictly ascending, each in [0, N), 1 <= k < N
+ * O(k N^2) per GP: iK' = iK[-j,-j] - c c^T / d (c = iK[-j, j], d = iK[j, j]; exactly symmetric), beta' = beta[-j] - c beta_j / d,
+ * and L^-1 is downdated to the inverse Cholesky factor of the reduced matrix (positive sums only), rows from the highest down.
+ * Removals count toward "refresh_every" together with appended points: past it, or with "incremental" = 0, the reduced memory
+ * is factorised in full from the record instead.  gpmpc_last_prepare_mode: 3 downdate, 0 that full factorisation.  Synchronises
+ * `stream`; a lost pivot is GPMPC_ERR_NOT_PD, as in gpmpc_prepare.  GPMPC_ERR_ARG, with the cached model untouched: no record of
+ * a gpmpc_prepare (no model yet, or gpmpc_set_factors supplied the factors; gpmpc_mll factorises through gpmpc_prepare's path
+ * and leaves a record, so rows can be forgotten from its model), idx_host NULL, k < 1, k >= N, an index out of range, unsorted or
+ * repeated.  GPMPC_ERR_NOT_PD and GPMPC_ERR_HIP leave no model, as after a failed gpmpc_prepare: prepare again.
+ */
+int gpmpc_forget(gpmpc_t* h, const int* idx_host, int k, void* stream);
 
 /* Training objective: per GP -log p(y_a | X, theta_a) / N and its gradient wrt lengthscales, outputscale and
  * noise -- what gpytorch's ExactMarginalLogLikelihood + autograd give the reference's LBFGS loop (gp_model.py:262-275).

@@ -42,6 +42,7 @@ SIGNATURES = {
     "gpmpc_read_factors": (C.c_int, [_P, _P, _P, _P]),
     "gpmpc_predict": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_predict_backward": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "gpmpc_predict_cov": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_forget": (C.c_int, [_P, C.POINTER(_I), _I, _P]),
@@ -66,7 +67,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def load(path=LIB_PATH):

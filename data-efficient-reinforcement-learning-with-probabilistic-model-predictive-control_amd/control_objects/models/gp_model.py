@@ -453,6 +453,18 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
             return out["mean"], out["var"]
         return _PredictFunction.apply(self.engine, noises, _t(inputs))
 
+    def predict_cov(self, inputs, other=None, include_noise=True):
+        """Joint GP posterior covariance at the model inputs, a DEVICE tensor: what the reference reads as
+        likelihood(model(x)).covariance_matrix (static_3d_graph.py:77-80, gp_model.py:394-397), per output -- the exact
+        posterior.  Joint form, `inputs` (M, E) alone: (D, M, M), exactly symmetric, diagonal = `predict`'s variance, each
+        GP's noise added to the diagonal when `include_noise`.  Cross form, `other` (Mb, E) given: (D, M, Mb), the covariance
+        between the two sets; no noise is ever added.  Not clamped and without jitter: regularise before factorising it.  No
+        autograd: the result carries no grad_fn even when the inputs require grad."""
+        if self.x_mem is None:
+            raise RuntimeError("call prepare_inference(inputs, state_changes) before predict_cov")
+        noises = self.noises.detach().cpu().numpy() if include_noise and other is None else None
+        return self.engine.predict_cov(_t(inputs).detach(), None if other is None else _t(other).detach(), noises=noises)
+
     def predict_next_state_change(self, input_mu, input_var):
         """Same signature / return as the reference (:112-180): one Gaussian model input, mean (E,) and covariance (E, E) ->
         (M.t() (1, D), S (D, D), V.t() (E, D)) CPU float64 tensors -- the moment-matched mean state change, its covariance and

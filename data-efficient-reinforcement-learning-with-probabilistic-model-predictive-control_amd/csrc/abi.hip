@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 13; }
+int gpmpc_abi_version(void) { return 14; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -81,7 +81,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->momws, &h->mombws, &h->Xf, &h->Yf, &h->fgws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->Xf, &h->Yf, &h->fgws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -124,6 +124,11 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
         const long long v = value;
         if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_backward_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
         h->opt_predict_bwd_chunk = (int)v;
+    }
+    else if (!strcmp(name, "predict_cov_chunk_rows")) {
+        const long long v = value;
+        if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_cov_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
+        h->opt_predict_cov_chunk = (int)v;
     }
     else if (!strcmp(name, "moments_chunk_points")) {
         if (value < 0 || value > (1 << 24)) { h->err = "moments_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
@@ -230,6 +235,22 @@ int gpmpc_predict_backward(gpmpc_t* g, const double* Xq, int M, int D, int E, co
     if (M == 0) return GPMPC_OK;
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_predict_backward(h, Xq, M, mean_bar, var_bar, Xq_bar_out, (hipStream_t)stream);
+}
+
+int gpmpc_predict_cov(gpmpc_t* g, const double* Xa, int Ma, const double* Xb, int Mb, int D, int E, const double* noises_host,
+                      double* cov_out, void* stream) {
+    Range roctx_range("gpmpc_predict_cov");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "predict_cov before prepare / set_factors / mll");
+    if (D != h->D || E != h->E) return bad(g, "predict_cov: D / E differ from the cached model");
+    if (Ma < 0 || (Xb && Mb < 0)) return bad(g, "predict_cov: negative number of points");
+    if (Xb && noises_host) return bad(g, "predict_cov: the cross form takes no noise");
+    if (Ma > (1 << 22) || (Xb && Mb > (1 << 22))) return bad(g, "predict_cov: more than 2^22 points");
+    if (Ma == 0 || (Xb && Mb == 0)) return GPMPC_OK;
+    if (!Xa || !cov_out) return bad(g, "null argument");
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_predict_cov(h, Xa, Ma, Xb, Mb, noises_host, cov_out, (hipStream_t)stream);
 }
 
 int gpmpc_moments(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, double* M_out, double* S_out,

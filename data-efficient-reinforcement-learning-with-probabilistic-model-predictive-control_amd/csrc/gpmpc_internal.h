@@ -207,6 +207,7 @@ struct Handle {
     Buf tgradws;  // gradient's tile pass: records of a block of (candidate, step) items | per-tile partial moments
     Buf predws;   // gpmpc_predict: per-(query row, column block) partial sums of one chunk of query rows
     Buf predbws;  // gpmpc_predict_backward: per-(output, column block, query row, input) partial sums of one chunk of query rows
+    Buf covws;    // gpmpc_predict_cov: P = K*_a(Xa) iK_a of one chunk of rows of Xa
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
@@ -297,6 +298,7 @@ struct Handle {
     int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
     int opt_predict_bwd_chunk = 0;   // gpmpc_predict_backward: the same for its chunks
+    int opt_predict_cov_chunk = 0;   // gpmpc_predict_cov: rows of Xa per chunk (0: as many as a 256 MB workspace holds; tests set a small one)
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int lds_limit = 160 * 1024;
@@ -488,6 +490,10 @@ int run_predict(Handle* h, const double* Xq, int M, const double* noises_host, d
 // ... and its gradient wrt Xq for upstream mean_bar / var_bar (each may be NULL = 0), written to Xq_bar (M, E)
 int run_predict_backward(Handle* h, const double* Xq, int M, const double* mean_bar, const double* var_bar, double* Xq_bar,
                          hipStream_t s);
+// predict_cov.hip: posterior covariance between the rows of Xa and of Xb (cross form), or of Xa with itself (Xb NULL: joint form,
+// exactly symmetric, noises_host on the diagonal), written to out (D, Ma, Mb)
+int run_predict_cov(Handle* h, const double* Xa, int Ma, const double* Xb, int Mb, const double* noises_host, double* out,
+                    hipStream_t s);
 // moments.hip: moment-matched prediction at P Gaussian inputs from the cached model (Sig NULL = 0; S_out / V_out may be NULL)
 int run_moments(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                 hipStream_t s);

@@ -221,6 +221,32 @@ class HipEngine:
         self._keep_predict_backward = (Xq, mb, vb)   # alive until the asynchronous call has read them
         return out
 
+    def predict_cov(self, Xa, Xb=None, noises=None):
+        """Joint GP posterior covariance between query points from the cached model (gpmpc_predict_cov), a device tensor.
+        Cross form, Xa (Ma, E) and Xb (Mb, E): (D, Ma, Mb), element [a, i, j] the covariance of output a at xa_i and xb_j;
+        `noises` must be None.  Joint form, Xb None: (D, Ma, Ma), the exactly symmetric covariance matrix of the set, whose
+        diagonal is `predict`'s variance; `noises` (D,) is added to the diagonal, as likelihood(model(x)) does.  Not clamped,
+        no jitter.  Asynchronous on the current stream."""
+        Xa = self._dev(Xa)
+        if Xa.dim() != 2:
+            raise ValueError(f"expected query inputs of shape (Ma, E), got {tuple(Xa.shape)}")
+        Ma, E = Xa.shape
+        D = self.D
+        Mb = Ma
+        if Xb is not None:
+            Xb = self._dev(Xb)
+            if Xb.dim() != 2 or Xb.shape[1] != E:
+                raise ValueError(f"expected query inputs of shape (Mb, {E}), got {tuple(Xb.shape)}")
+            Mb = Xb.shape[0]
+        nz = _host(noises, (D,)) if noises is not None else None
+        out = torch.empty((D, Ma, Mb), dtype=torch.float64, device=self.device)
+        if Xb is not None and Mb == 0:       # an empty tensor has no address: the library would read the NULL as the joint form
+            return out
+        self._check(self.lib.gpmpc_predict_cov(self._h, Xa.data_ptr(), Ma, Xb.data_ptr() if Xb is not None else None, Mb, D, E,
+                                               _hp(nz) if nz is not None else None, out.data_ptr(), self._stream()))
+        self._keep_predict_cov = (Xa, Xb)    # alive until the asynchronous call has read them
+        return out
+
     def moments(self, mu, var=None, S=True, V=True):
         """Moment-matched one-step prediction (predict_next_state_change, gp_model.py:112-180) at P Gaussian inputs from the
         cached model: mu (P, E), var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D), V (P, E, D)) of device tensors

@@ -121,6 +121,32 @@ int gpmpc_predict_backward(gpmpc_t* h, const double* Xq_dev, int M, int D, int E
                            const double* var_bar_dev, double* Xq_bar_out_dev, void* stream);
 
 /*
+ * gpmpc_predict_cov  <->  likelihood(model(x)).covariance_matrix (static_3d_graph.py:77-80, gp_model.py:394-397): the joint
+ * posterior covariance between query points, of which gpmpc_predict's variance is the diagonal -- what posterior function
+ * samples, joint confidence regions and the variance of a linear functional of the prediction need.  For every output a of the
+ * cached model, with k_a(x) as in gpmpc_predict,
+ *   t_a(x, x') = sigma2_a exp(-1/2 sum_e (x_e - x'_e)^2 / l_ae^2)  -  k_a(x)^T iK_a k_a(x')
+ *   Xa_dev (Ma,E), Xb_dev (Mb,E)  query inputs in the model-input space of the cached memory
+ *   cov_out_dev (D,Ma,Mb)         required; overwritten
+ * Cross form (Xb_dev non-NULL): cov[a,i,j] = t_a(xa_i, xb_j); noises_host must be NULL (two different sets share no likelihood
+ * noise).  Joint form (Xb_dev NULL, Mb ignored, output (D,Ma,Ma)): cov[a,i,j] = 1/2 (t_a(x_i, x_j) + t_a(x_j, x_i)), exactly
+ * symmetric (cov[a,i,j] and cov[a,j,i] are the same bits), plus noises_host[a] on the diagonal when noises_host (D) is non-NULL, as
+ * likelihood(...) adds.  Not clamped and no jitter added: the caller decides how to regularise before factorising it.  The exact
+ * posterior, not gpytorch's LOVE approximation.  iK is used as given: prepare and mll store it exactly symmetric; with a
+ * non-symmetric iK passed through gpmpc_set_factors the joint form still returns the symmetric average above, the posterior
+ * covariance of the symmetric part of iK.  An element's bits depend only on the two points it belongs to (cross form: the ordered
+ * pair; joint form: the unordered pair) -- not on Ma / Mb, on where the points sit, on their neighbours or on how the call chunks
+ * the rows internally; every sum runs in an order fixed by N alone, no atomics.  The diagonal agrees with gpmpc_predict's variance
+ * to rounding, not bit for bit (the sums are grouped differently).  Workspace of its own: P = K*_a(Xa) iK_a for a chunk of rows,
+ * within 256 MB, or one 64-row tile's need if that is more (32 MB at N = 4096, D = 16, which gives chunks of 512 rows), whatever
+ * Ma and Mb are.  Touches no other workspace and no gpmpc_last_* state.  Asynchronous on `stream`; Ma = 0 (or Mb = 0 in the cross
+ * form) launches nothing.  GPMPC_ERR_ARG: no cached model, D / E different from the cached model, a negative count or one beyond
+ * 2^22, Xa_dev or cov_out_dev NULL with work to do, noises_host with the cross form.
+ */
+int gpmpc_predict_cov(gpmpc_t* h, const double* Xa_dev, int Ma, const double* Xb_dev, int Mb, int D, int E,
+                      const double* noises_host, double* cov_out_dev, void* stream);
+
+/*
  * gpmpc_moments  <->  predict_next_state_change(input_mu, input_var) (gp_model.py:112-180) at P independent Gaussian model inputs
  * N(m_p, Sigma_p): the moment-matched one-step prediction of the state change, with a general symmetric E x E Sigma_p (any block
  * may be non-zero: state, action and time inputs alike; the rollouts only ever pass a state-block one).
@@ -172,7 +198,7 @@ int gpmpc_moments_backward(gpmpc_t* h, const double* mu_dev, const double* var_d
  * 2 element-wise Taylor), "force_separable", "force_global_scratch", "grad_separable" / "grad_tiles" / "grad_stream" /
  * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
  * query rows per internal chunk: 0 auto, else a multiple of 64), "predict_backward_chunk_rows" (the same for
- * gpmpc_predict_backward), "moments_chunk_points" (gpmpc_moments' points per internal
+ * gpmpc_predict_backward), "predict_cov_chunk_rows" (the same for gpmpc_predict_cov's rows of Xa),"moments_chunk_points" (gpmpc_moments' points per internal
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */

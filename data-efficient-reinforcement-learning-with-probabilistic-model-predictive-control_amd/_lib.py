@@ -44,6 +44,7 @@ SIGNATURES = {
     "gpmpc_predict_backward": (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_predict_cov": (C.c_int, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "gpmpc_moments_linear": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_forget": (C.c_int, [_P, C.POINTER(_I), _I, _P]),
     "gpmpc_last_prepare_mode": (C.c_int, [_P]),
@@ -55,6 +56,7 @@ SIGNATURES = {
     "gpmpc_set_option": (C.c_int, [_P, C.c_char_p, C.c_longlong]),
     "gpmpc_set_cost": (C.c_int, [_P, _P, _P, _P, _D, _I, _P, _P, _I, _I]),
     "gpmpc_rollout": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_grad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_objective_grad_host": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _D, C.POINTER(C.POINTER(_D)), _P]),
@@ -67,7 +69,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def load(path=LIB_PATH):

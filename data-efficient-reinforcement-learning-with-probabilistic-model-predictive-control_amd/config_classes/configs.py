@@ -144,10 +144,20 @@ def _with_time_column(ls, ls_time, num_models, num_inputs):
     return out
 
 
+UNCERTAINTY_PROPAGATIONS = ("moment_matching", "linearized")
+
+
 class ModelConfig:
     def __init__(self, gp_init=None, init_lengthscale_time=100, min_std_noise=1e-3, max_std_noise=3e-1,
                  min_outputscale=1e-5, max_outputscale=0.95, min_lengthscale=4e-3, max_lengthscale=25.0,
-                 min_lengthscale_time=10, max_lengthscale_time=10000, include_time_model=False):
+                 min_lengthscale_time=10, max_lengthscale_time=10000, include_time_model=False,
+                 uncertainty_propagation="moment_matching"):
+        """uncertainty_propagation: how an uncertain state goes through the GP -- "moment_matching" (the reference's exact
+        moment matching, gp_model.py:112-180) or "linearized" (first-order Taylor propagation at the input mean,
+        gpmpc_moments_linear / gpmpc_rollout_linear: no D^2 pair pass, but a different approximation)."""
+        if uncertainty_propagation not in UNCERTAINTY_PROPAGATIONS:
+            raise ValueError(f"uncertainty_propagation must be one of {UNCERTAINTY_PROPAGATIONS}, got {uncertainty_propagation!r}")
+        self.uncertainty_propagation = uncertainty_propagation
         if gp_init is None:
             gp_init = {"noise_covar.noise": [1e-4] * 3, "base_kernel.lengthscale": [[0.75] * 4] * 3,
                        "outputscale": [5e-2] * 3}

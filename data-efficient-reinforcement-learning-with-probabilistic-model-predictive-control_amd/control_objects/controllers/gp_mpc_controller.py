@@ -66,6 +66,23 @@ class GpMpcController(BaseControllerObject):
         self.num_rollouts = 0          # candidate trajectories evaluated so far (throughput accounting)
         self.analytic_gradient = True  # gradient kernels (gpmpc_rollout_grad); False: 4th-order differences of the rollout
         self.process_group = None      # torch.distributed group the candidates shard over (None: the default group)
+        self._check_propagation_supported()
+
+    LINEARIZED_OPTIMIZERS = "optimize=False (random shooting) or candidate_optimizer='cem'"
+
+    def _check_propagation_supported(self, what=None):
+        """ModelConfig.uncertainty_propagation = "linearized" has objective values only (gpmpc_rollout_linear): the searches
+        that go through `evaluate_candidates` work; the device-side search, the batched L-BFGS and the scipy L-BFGS-B loop
+        need kernels (search, gradient) the linearised path does not have."""
+        if self.transition_model.propagation() != "linearized":
+            return
+        cc = self.config.controller
+        if what is None:
+            if not cc.optimize or getattr(cc, "candidate_optimizer", None) == "cem":
+                return
+            what = f"candidate_optimizer={getattr(cc, 'candidate_optimizer', None)!r} with optimize=True"
+        raise ValueError(f"uncertainty_propagation='linearized' does not support {what}: it has no gradient or device-search "
+                         f"kernels; supported optimisers: {self.LINEARIZED_OPTIMIZERS}")
 
     def _ranks(self):
         """(world, rank) of the candidate sharding.  Sharding is OPT-IN (`ControllerConfig.shard_over_ranks`): a process that
@@ -139,6 +156,7 @@ class GpMpcController(BaseControllerObject):
     def compute_mean_lcb_trajectory(self, actions_mpc, obs_mu, obs_var):
         """Reference :229-285: (mean-LCB cost, d cost / d actions_mpc) for ONE optimiser vector; also caches
         the predicted trajectory and its costs on `self` for IterationInformation (:279-283)."""
+        self._check_propagation_supported("compute_mean_lcb_trajectory (the gradient path)")
         H, A = self.config.controller.len_horizon, self.actions_mapper.dim_action
         base = self.actions_mapper.mpc_to_model_batch(np.asarray(actions_mpc, dtype=np.float64).reshape(1, -1))[0]
         n = H * A
@@ -313,6 +331,7 @@ class GpMpcController(BaseControllerObject):
 
     def _get_optimal_actions(self, state_mu, state_var):
         """Reference :114-153."""
+        self._check_propagation_supported()
         self._prepare()
         cc = self.config.controller
         H, A = cc.len_horizon, self.actions_mapper.dim_action
@@ -505,6 +524,7 @@ class GpMpcController(BaseControllerObject):
 
     def objective_and_gradient_batch(self, actions_mpc_batch, obs_mu, obs_var):
         """(B, H*A) optimiser vectors -> (J (B,), dJ/d(actions_mpc) (B, H*A)) in one gpmpc_rollout_grad launch."""
+        self._check_propagation_supported("objective_and_gradient_batch (the gradient path)")
         X = np.asarray(actions_mpc_batch, dtype=np.float64)
         acts = self.actions_mapper.mpc_to_model_batch(X)
         self.transition_model.set_cost(self.config.reward)

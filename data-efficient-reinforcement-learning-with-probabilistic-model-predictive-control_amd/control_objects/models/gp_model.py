@@ -124,6 +124,16 @@ def _check_trajectory_grad_shape(D, A, include_time):
                      "chaining predict_next_state_change, whose gradients cover them")
 
 
+PROPAGATIONS = ("moment_matching", "linearized")
+
+
+def _no_linearized_autograd(what, *tensors):
+    """The linearised propagation has no backward kernels: refuse rather than return tensors without a grad_fn."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"{what}: propagation='linearized' has no autograd; detach the inputs or run under "
+                                  "torch.no_grad(), or use propagation='moment_matching'")
+
+
 class SavedState:
     """In-memory snapshot shipped to the training process (reference gp_model.py:13-36)."""
 
@@ -381,9 +391,17 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self._cost_key = key
         self.engine._cost_token = key          # engines can be shared between models: remember WHAT is loaded
 
+    def propagation(self, propagation=None):
+        """The uncertainty propagation a call uses: its own `propagation` argument, or ModelConfig.uncertainty_propagation."""
+        if propagation is None:
+            propagation = getattr(self.config, "uncertainty_propagation", "moment_matching")
+        if propagation not in PROPAGATIONS:
+            raise ValueError(f"propagation must be one of {PROPAGATIONS}, got {propagation!r}")
+        return propagation
+
     # -- a3/a4 -------------------------------------------------------------------------
     def predict_trajectory_batch(self, actions, obs_mu, obs_var, len_horizon=None, current_time_idx=0,
-                                 trajectories=True, stage_costs=True):
+                                 trajectories=True, stage_costs=True, propagation=None):
         """actions (B,H,A) -> dict of DEVICE tensors: J (B,), mu (B,H+1,D), Sig (B,H+1,D,D),
         cost_mu / cost_var (B,H+1).  Costs need set_cost() first.  Differentiable like the reference's predict_trajectory
         followed by get_rewards_trajectory: when grad mode is on and actions, obs_mu or obs_var requires grad, mu, Sig and
@@ -392,9 +410,18 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         shared by the candidates: their gradients are the sums over the batch, obs_var's the symmetric part of the
         reference's.  The time input, hyper-parameters and memory get no gradient, and double backward raises.  Shapes outside
         the gradient kernels (D <= 8 with A (+ time) <= 6, or 8 < D <= 16) raise GpmpcError(GPMPC_ERR_LIMIT) here, before any
-        launch; chain predict_next_state_change to differentiate those."""
+        launch; chain predict_next_state_change to differentiate those.
+        `propagation` (None: ModelConfig.uncertainty_propagation): "linearized" runs gpmpc_rollout_linear instead -- the same
+        dict, no autograd (NotImplementedError when grad mode is on and an input requires grad)."""
         if self._cost_key is None and stage_costs:
             raise RuntimeError("call set_cost(reward_config) before predicting costs")
+        if self.propagation(propagation) == "linearized":
+            _no_linearized_autograd("predict_trajectory", actions, obs_mu, obs_var)
+            actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
+            if len_horizon is not None and actions.shape[1] != len_horizon:
+                raise ValueError("actions.shape[1] != len_horizon")
+            return self.engine.rollout_linear(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model,
+                                              float(current_time_idx), trajectories, stage_costs)
         grads = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (actions, obs_mu, obs_var))
         actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
         if len_horizon is not None and actions.shape[1] != len_horizon:
@@ -429,13 +456,13 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         return self.engine.objective_grad_host(np.asarray(actions, dtype=np.float64), _t(obs_mu).numpy(), _t(obs_var).numpy(),
                                                self.config.include_time_model, float(current_time_idx))
 
-    def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx):
+    def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx, propagation=None):
         """Same signature / return shapes as the reference (:60-110): ((H+1,D), (H+1,D,D)) CPU tensors.  Differentiable like
         the reference: when grad mode is on and actions, obs_mu or obs_var requires grad, both outputs carry a grad_fn and
         backward() reaches the inputs through gpmpc_rollout_backward (see predict_trajectory_batch); obs_var's gradient is the
-        symmetric part of the reference's."""
+        symmetric part of the reference's.  `propagation`: see predict_trajectory_batch."""
         out = self.predict_trajectory_batch(_t(actions)[None], obs_mu, obs_var, len_horizon, current_time_idx,
-                                            trajectories=True, stage_costs=False)
+                                            trajectories=True, stage_costs=False, propagation=propagation)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()
 
     def predict(self, inputs, include_noise=True):
@@ -465,24 +492,30 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         noises = self.noises.detach().cpu().numpy() if include_noise and other is None else None
         return self.engine.predict_cov(_t(inputs).detach(), None if other is None else _t(other).detach(), noises=noises)
 
-    def predict_next_state_change(self, input_mu, input_var):
+    def predict_next_state_change(self, input_mu, input_var, propagation=None):
         """Same signature / return as the reference (:112-180): one Gaussian model input, mean (E,) and covariance (E, E) ->
         (M.t() (1, D), S (D, D), V.t() (E, D)) CPU float64 tensors -- the moment-matched mean state change, its covariance and
         Sigma^-1 Cov[x, delta].  Differentiable like the reference: when grad mode is on and input_mu or input_var requires
         grad, the outputs carry a grad_fn and backward() reaches the inputs (CPU or device) through gpmpc_moments_backward.
         input_var's gradient is the symmetric part of the reference's.  Hyper-parameters and the memory get no gradient, and
-        double backward raises."""
+        double backward raises.  `propagation`: see predict_next_state_change_batch."""
         mu = _t(input_mu).reshape(1, -1)
         var = _t(input_var).reshape(1, mu.shape[1], mu.shape[1])
-        out = self.predict_next_state_change_batch(mu, var)
+        out = self.predict_next_state_change_batch(mu, var, propagation=propagation)
         return out["M"].cpu(), out["S"][0].cpu(), out["V"][0].cpu()
 
-    def predict_next_state_change_batch(self, input_mu, input_var=None):
+    def predict_next_state_change_batch(self, input_mu, input_var=None, propagation=None):
         """predict_next_state_change at P independent inputs: input_mu (P, E), input_var (P, E, E) or None (deterministic
         inputs) -> dict of DEVICE tensors M (P, D), S (P, D, D), V (P, E, D).  Differentiable as predict_next_state_change is
-        when grad mode is on and an input requires grad (input_var None: the mean's gradient only)."""
+        when grad mode is on and an input requires grad (input_var None: the mean's gradient only).
+        `propagation` (None: ModelConfig.uncertainty_propagation): "linearized" returns the first-order propagation instead
+        (gpmpc_moments_linear: M the posterior mean at input_mu, V its Jacobian, S = V^T input_var V + the posterior variance
+        on the diagonal) -- no autograd (NotImplementedError when grad mode is on and an input requires grad)."""
         if self.x_mem is None:
             raise RuntimeError("call prepare_inference(inputs, state_changes) before predict_next_state_change")
+        if self.propagation(propagation) == "linearized":
+            _no_linearized_autograd("predict_next_state_change", input_mu, input_var)
+            return self.engine.moments_linear(input_mu, input_var)
         grads = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (input_mu, input_var))
         if not grads:
             return self.engine.moments(input_mu, input_var)
@@ -495,7 +528,8 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
     def save_state(self):
         return SavedState(inputs=self.x_mem, states_change=self.y_mem,
                           parameters=[m.state_dict() for m in self.models],
-                          constraints_hyperparams={k: v for k, v in vars(self.config).items() if k != "gp_init"})
+                          constraints_hyperparams={k: v for k, v in vars(self.config).items()
+                                                   if k not in ("gp_init", "uncertainty_propagation")})
 
     def load_state(self, saved_state):
         for m, p in zip(self.models, saved_state.parameters):

@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 14; }
+int gpmpc_abi_version(void) { return 15; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -81,7 +81,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->Xf, &h->Yf, &h->fgws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->Xf, &h->Yf, &h->fgws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -137,6 +137,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "moments_backward_chunk_points")) {
         if (value < 0 || value > (1 << 24)) { h->err = "moments_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
         h->opt_moments_bwd_chunk = (int)value;
+    }
+    else if (!strcmp(name, "moments_linear_chunk_points")) {
+        if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
+        h->opt_moments_linear_chunk = (int)value;
     }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
@@ -271,6 +275,24 @@ int gpmpc_moments(gpmpc_t* g, const double* mu, const double* var, int P, int D,
     return run_moments(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
 }
 
+int gpmpc_moments_linear(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, double* M_out, double* S_out,
+                         double* V_out, void* stream) {
+    Range roctx_range("gpmpc_moments_linear");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "moments_linear before prepare / set_factors / mll");
+    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
+        h->err = "moments_linear: D or E beyond the compiled limits";
+        return GPMPC_ERR_LIMIT;
+    }
+    if (D != h->D || E != h->E) return bad(g, "moments_linear: D / E differ from the cached model");
+    if (P < 0) return bad(g, "moments_linear: P < 0");
+    if (P > 0 && !mu) return bad(g, "null argument");
+    if (P == 0) return GPMPC_OK;
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_moments_linear(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+}
+
 int gpmpc_moments_backward(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, const double* M_bar,
                            const double* S_bar, const double* V_bar, double* mu_bar_out, double* var_bar_out, void* stream) {
     Range roctx_range("gpmpc_moments_backward");
@@ -381,6 +403,20 @@ int gpmpc_rollout(gpmpc_t* g, const double* actions, const double* mu0, const do
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
     return launch_rollout(H_(g), a, (hipStream_t)stream);
+}
+
+int gpmpc_rollout_linear(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
+                         int include_time, double time0, double* mu_out, double* Sig_out, double* cm_out, double* cv_out,
+                         double* J_out, void* stream) {
+    Range roctx_range("gpmpc_rollout_linear");
+    if (!g) return GPMPC_ERR_ARG;
+    RolloutArgs a;
+    // as gpmpc_rollout: the trajectory alone needs no cost settings
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
+    return run_rollout_linear(H_(g), a, (hipStream_t)stream);
 }
 
 int gpmpc_rollout_grad(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,

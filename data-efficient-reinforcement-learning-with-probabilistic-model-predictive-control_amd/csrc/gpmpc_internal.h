@@ -210,6 +210,7 @@ struct Handle {
     Buf covws;    // gpmpc_predict_cov: P = K*_a(Xa) iK_a of one chunk of rows of Xa
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
+    Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -301,6 +302,7 @@ struct Handle {
     int opt_predict_cov_chunk = 0;   // gpmpc_predict_cov: rows of Xa per chunk (0: as many as a 256 MB workspace holds; tests set a small one)
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
+    int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int lds_limit = 160 * 1024;
     int num_cu = 256;
 };
@@ -497,6 +499,11 @@ int run_predict_cov(Handle* h, const double* Xa, int Ma, const double* Xb, int M
 // moments.hip: moment-matched prediction at P Gaussian inputs from the cached model (Sig NULL = 0; S_out / V_out may be NULL)
 int run_moments(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                 hipStream_t s);
+// moments_linear.hip: first-order (linearised) propagation at P Gaussian inputs from the cached model (Sig NULL = 0; each output may
+// be NULL; without S_out no matrix product runs), and the horizon rollout built on it (`a` as fill_args leaves it plus the outputs)
+int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
+                       hipStream_t s);
+int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s);
 // moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
 int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                          const double* Vb, double* mb_out, double* vb_out, hipStream_t s);

@@ -268,6 +268,29 @@ class HipEngine:
         self._keep_moments = (mu, vr)        # alive until the asynchronous call has read them
         return out
 
+    def moments_linear(self, mu, var=None, S=True, V=True):
+        """First-order (linearised) one-step prediction at P Gaussian inputs from the cached model (gpmpc_moments_linear): the
+        posterior at the input mean, the input covariance pushed through the Jacobian of the posterior mean.  mu (P, E),
+        var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D) = V^T var V + diag(posterior variance), V (P, E, D) =
+        dM/dmu) of device tensors (S / V only when requested).  Without S no matrix product runs: M and the whole mean
+        Jacobian in one GEMV-class pass.  Asynchronous on the current stream."""
+        mu = self._dev(mu)
+        if mu.dim() != 2:
+            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
+        P, E = mu.shape
+        D = self.D
+        vr = self._dev(var, (P, E, E)) if var is not None else None
+        out = {"M": torch.empty((P, D), dtype=torch.float64, device=self.device)}
+        if S:
+            out["S"] = torch.empty((P, D, D), dtype=torch.float64, device=self.device)
+        if V:
+            out["V"] = torch.empty((P, E, D), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_moments_linear(self._h, mu.data_ptr(), vr.data_ptr() if vr is not None else None, P, D, E,
+                                                  out["M"].data_ptr(), out["S"].data_ptr() if S else None,
+                                                  out["V"].data_ptr() if V else None, self._stream()))
+        self._keep_moments_linear = (mu, vr)     # alive until the asynchronous call has read them
+        return out
+
     def moments_backward(self, mu, var=None, M_bar=None, S_bar=None, V_bar=None, mu_bar=True, var_bar=True):
         """Reverse-mode product of `moments` (autograd through predict_next_state_change, gp_model.py:112-180): mu (P, E),
         var (P, E, E) or None (zero), upstream gradients M_bar (P, D), S_bar (P, D, D), V_bar (P, E, D), each None for zero ->
@@ -336,6 +359,35 @@ class HipEngine:
         self._check(self.lib.gpmpc_rollout(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
                                            float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"), ptr("cost_var"),
                                            ptr("J"), self._stream()))
+        return out
+
+    def rollout_linear(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None):
+        """`rollout` with the linearised step (gpmpc_rollout_linear) in place of moment matching: the same arguments, the same
+        dict.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        if out is None:
+            out = {}
+            if stage_costs or self._cost == (D, A):
+                out["J"] = torch.empty(B, dtype=torch.float64, device=self.device)
+            if trajectories:
+                out["mu"] = torch.empty((B, H + 1, D), dtype=torch.float64, device=self.device)
+                out["Sig"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
+            if stage_costs:
+                out["cost_mu"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
+                out["cost_var"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
+        elif ("J" in out and out["J"].shape != (B,)) or ("mu" in out and out["mu"].shape != (B, H + 1, D)):
+            raise ValueError("`out` does not match the batch shape")
+
+        def ptr(k):
+            return out[k].data_ptr() if k in out else None
+        self._check(self.lib.gpmpc_rollout_linear(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A,
+                                                  int(bool(include_time)), float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"),
+                                                  ptr("cost_var"), ptr("J"), self._stream()))
+        self._keep_rollout_linear = actions      # alive until the asynchronous call has read it
         return out
 
     def rollout_grad(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=False):

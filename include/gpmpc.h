@@ -191,6 +191,32 @@ int gpmpc_moments_backward(gpmpc_t* h, const double* mu_dev, const double* var_d
                            void* stream);
 
 /*
+ * gpmpc_moments_linear: the first-order (Taylor) propagation of Girard et al. / Hewing et al. ("Cautious MPC using GP regression")
+ * at P independent Gaussian model inputs N(m_p, Sigma_p), with the arguments of gpmpc_moments and the same cached factors: the
+ * posterior is evaluated at the input mean and the input covariance goes through the Jacobian of the posterior mean.  Per point
+ * and output a, with k_aj = sigma2_a exp(-1/2 sum_e (m_e - x_je)^2 / l_ae^2) as in gpmpc_predict:
+ *   M_a    = sum_j k_aj beta_aj
+ *   V[e,a] = (1 / l_ae^2) sum_j beta_aj k_aj (x_je - m_e)     = dM_a / dm_e  (differences formed per element)
+ *   v_a    = sigma2_a - k_a^T iK_a k_a                         (not clamped, no noise added)
+ *   S      = V^T Sigma V + diag(v)
+ *   mu_dev (P,E), var_dev (P,E,E) or NULL (= 0); M_out_dev (P,D), S_out_dev (P,D,D), V_out_dev (P,E,D), each may be NULL
+ * It is a different approximation from moment matching, not a faster evaluation of it: it drops the 1/2 tr(H Sigma) term of the
+ * mean and the curvature terms of S; the two agree to first order in Sigma and coincide at Sigma = 0 (M, V and the then diagonal
+ * S, to rounding).  It costs one K* iK product per output, O(N^2 D) per point, and no O(N^2 D^2) pair pass.  Without S_out_dev no
+ * matrix product runs at all: M and the whole mean Jacobian V come from one O(N E D) pass.  Sigma is used as given and not
+ * checked.  S is exactly symmetric (S[a,b] and S[b,a] are the same bits) and exactly diagonal with var_dev NULL.  A point's M, S
+ * and V are bitwise the same whatever P is, wherever the point sits in the batch, whatever its neighbours are and however the call
+ * chunks the batch internally; M and V keep their bits when S_out / V_out are NULL.  Every sum runs in an order fixed by N, E and
+ * D alone; no atomics.  M, V and diag S agree with gpmpc_predict / gpmpc_predict_backward / gpmpc_moments (var NULL) to rounding,
+ * not bit for bit.  Workspace of its own: partial sums of one chunk of points, within 16 MB (or one 64-row tile's need if that is
+ * more).  Touches no other workspace and no gpmpc_last_* state.  Asynchronous on `stream`; P = 0 launches nothing.
+ * GPMPC_ERR_ARG: no cached model, D / E different from the cached model, P < 0, mu_dev NULL with P > 0.  GPMPC_ERR_LIMIT:
+ * D > GPMPC_MAX_D or E > GPMPC_MAX_E.
+ */
+int gpmpc_moments_linear(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P, int D, int E, double* M_out_dev,
+                         double* S_out_dev, double* V_out_dev, void* stream);
+
+/*
  * Options.  Behaviour: "incremental" (0/1, default 1: reuse / border-update the cached factors), "refresh_every" (32: border
  * updates between full factorisations), "cluster" (few-candidate cooperative form: 0 auto, 1 never, 2..32 workgroups per
  * candidate), "threads" (fused-horizon workgroup: 0 auto, 256 / 512 / 1024), "pair_tiles" (batch-major rollout path: 0 auto,
@@ -199,7 +225,8 @@ int gpmpc_moments_backward(gpmpc_t* h, const double* mu_dev, const double* var_d
  * "grad_mean" / "grad_share_cu" / "grad_chunk_rows", "fused_prepare", "outer_min_n", "predict_chunk_rows" (gpmpc_predict's
  * query rows per internal chunk: 0 auto, else a multiple of 64), "predict_backward_chunk_rows" (the same for
  * gpmpc_predict_backward), "predict_cov_chunk_rows" (the same for gpmpc_predict_cov's rows of Xa),"moments_chunk_points" (gpmpc_moments' points per internal
- * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward).  Measurement (A/B) switches of single
+ * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
+ * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);
@@ -231,6 +258,26 @@ int gpmpc_rollout(gpmpc_t* h, const double* actions_dev, const double* mu0_host,
                   double* cost_var_out_dev, double* J_out_dev, void* stream);
 int gpmpc_last_rollout_path(gpmpc_t* h);
 int gpmpc_last_cluster(gpmpc_t* h);
+
+/*
+ * gpmpc_rollout_linear: gpmpc_rollout -- the same arguments and outputs -- with the step of gpmpc_moments_linear in place of
+ * predict_next_state_change in the recurrence of predict_trajectory (gp_model.py:95-108).  The model input of step t is
+ * [mu_t | action_t | time0 + t], its covariance non-zero in the state block only; with V_s the first D rows of V,
+ *   mu_{t+1} = mu_t + M,   T = Sigma_t V_s,   Sigma_{t+1} = Sigma_t + (V_s^T Sigma_t V_s + diag v) + T + T^T
+ * Index 0 of the outputs is the input state; Sigma_t (t >= 1) is exactly symmetric.  Stage costs, terminal cost and J come from
+ * the trajectory cost kernel gpmpc_rollout uses, on the stored trajectory with the loaded gpmpc_set_cost settings: constraints,
+ * clipping and kappa behave as there.  The cost outputs need gpmpc_set_cost for this (D, A); with all three NULL the call is the
+ * plain trajectory.  Batch-major: per horizon step one tile launch over all candidates of a chunk and one small finish launch
+ * (there is no fused-horizon form: with few candidates a 64-row tile is mostly padding).  A candidate's results are bitwise the
+ * same alone and at any position of any batch, whatever "moments_linear_chunk_points" is.  Workspace of its own (the partial
+ * sums and model inputs of one chunk of candidates, and their trajectory where the caller keeps none; a chunk runs its whole
+ * horizon), within 16 MB or one 64-row tile's need.  Touches no other workspace and no gpmpc_last_* state.  Asynchronous on
+ * `stream`.  Argument errors as gpmpc_rollout (GPMPC_ERR_ARG: no cached model, NULL actions / mu0 / S0, B < 1, H < 1, A < 0,
+ * D + A (+1) != E, cost outputs without gpmpc_set_cost for this (D, A)).
+ */
+int gpmpc_rollout_linear(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B, int H, int A,
+                         int include_time, double time0, double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev,
+                         double* cost_var_out_dev, double* J_out_dev, void* stream);
 
 /*
  * Objective AND analytic gradient: J_out_dev (B), grad_out_dev (B,H,A) = dJ/d(actions) -- what the reference obtains with

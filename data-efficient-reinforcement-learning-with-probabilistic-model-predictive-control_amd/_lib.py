@@ -46,6 +46,7 @@ SIGNATURES = {
     "gpmpc_moments": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_linear": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_moments_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_moments_linear_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_forget": (C.c_int, [_P, C.POINTER(_I), _I, _P]),
     "gpmpc_last_prepare_mode": (C.c_int, [_P]),
     "gpmpc_last_rollout_path": (C.c_int, [_P]),
@@ -59,6 +60,7 @@ SIGNATURES = {
     "gpmpc_rollout_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_grad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout_linear_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_objective_grad_host": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _D, C.POINTER(C.POINTER(_D)), _P]),
     "gpmpc_rollout_timed": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I, C.POINTER(C.c_float), _P]),
     "gpmpc_cem_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, C.c_ulonglong, _P, _I, _P, _P, _P, _P, _P]),
@@ -69,7 +71,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def load(path=LIB_PATH):

@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 15; }
+int gpmpc_abi_version(void) { return 16; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -81,7 +81,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->Xf, &h->Yf, &h->fgws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->Xf, &h->Yf, &h->fgws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -141,6 +141,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "moments_linear_chunk_points")) {
         if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
         h->opt_moments_linear_chunk = (int)value;
+    }
+    else if (!strcmp(name, "moments_linear_backward_chunk_points")) {
+        if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
+        h->opt_moments_linear_bwd_chunk = (int)value;
     }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
@@ -311,6 +315,25 @@ int gpmpc_moments_backward(gpmpc_t* g, const double* mu, const double* var, int 
     return run_moments_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
 }
 
+int gpmpc_moments_linear_backward(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, const double* M_bar,
+                                  const double* S_bar, const double* V_bar, double* mu_bar_out, double* var_bar_out,
+                                  void* stream) {
+    Range roctx_range("gpmpc_moments_linear_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "moments_linear_backward before prepare / set_factors / mll");
+    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
+        h->err = "moments_linear_backward: D or E beyond the compiled limits";
+        return GPMPC_ERR_LIMIT;
+    }
+    if (D != h->D || E != h->E) return bad(g, "moments_linear_backward: D / E differ from the cached model");
+    if (P < 0) return bad(g, "moments_linear_backward: P < 0");
+    if (P > 0 && !mu) return bad(g, "null argument");
+    if (P == 0) return GPMPC_OK;
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_moments_linear_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
+}
+
 int gpmpc_mll(gpmpc_t* g, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
               int N, int D, int E, double* out_host, void* stream) {
     Range roctx_range("gpmpc_mll");
@@ -449,6 +472,23 @@ int gpmpc_rollout_backward(gpmpc_t* g, const double* actions, const double* mu0,
     if (A < 1) return bad(g, "gradient needs A >= 1");
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     return launch_rollout_grad(H_(g), a, actions_bar_out, (hipStream_t)stream, &sd);
+}
+
+int gpmpc_rollout_linear_backward(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
+                                  int include_time, double time0, const double* mu_bar, const double* Sig_bar,
+                                  const double* cm_bar, const double* cv_bar, const double* J_bar, double* actions_bar_out,
+                                  double* mu0_bar_out, double* S0_bar_out, void* stream) {
+    Range roctx_range("gpmpc_rollout_linear_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!actions_bar_out) return bad(g, "null argument");
+    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
+    RolloutArgs a;
+    // as gpmpc_rollout_backward: the trajectory's cotangents alone need no cost settings
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "gradient needs A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_rollout_linear_backward(H_(g), a, sd, actions_bar_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

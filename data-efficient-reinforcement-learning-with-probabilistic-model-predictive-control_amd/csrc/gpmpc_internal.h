@@ -211,6 +211,7 @@ struct Handle {
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
+    Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -303,6 +304,7 @@ struct Handle {
     int opt_moments_chunk = 0;       // gpmpc_moments: points per chunk (0: as many as a 32 MB workspace holds; tests set small ones)
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
+    int opt_moments_linear_bwd_chunk = 0;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: the same for their chunks
     int lds_limit = 160 * 1024;
     int num_cu = 256;
 };
@@ -507,6 +509,11 @@ int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s);
 // moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
 int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                          const double* Vb, double* mb_out, double* vb_out, hipStream_t s);
+// moments_linear_backward.hip: gradients of run_moments_linear wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may
+// be NULL), and of run_rollout_linear wrt the actions and the initial state for the cotangents `sd` (forward recomputed inside)
+int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
+                                const double* Vb, double* mb_out, double* vb_out, hipStream_t s);
+int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, double* actions_bar, hipStream_t s);
 // search.hip: cross-entropy search whose loop stays on the device (actions / J_out of `a` are set inside)
 int run_cem_search(Handle* h, RolloutArgs& a, int iterations, int n_elite, unsigned long long seed, const double* first_host,
                    int mapper, const double* max_change_host, const double* a_prev_host, const double* noise_dev,

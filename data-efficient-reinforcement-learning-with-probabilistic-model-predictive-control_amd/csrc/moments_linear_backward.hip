@@ -1,0 +1,747 @@
+// moments_linear_backward.hip -- reverse-mode products of the linearised propagation: gpmpc_moments_linear_backward (one step) and
+// gpmpc_rollout_linear_backward (a trajectory with its costs).  Per point, with d_je = x_je - m_e (formed per element, as the
+// forward does), r_aje = d_je / l_ae^2, k_aj as in the forward and q_a = iK_a k_a (a row of K* iK; iK taken as symmetric):
+//   var_bar = sym(V S_bar V^T)
+//   W = V_bar + Sigma V (S_bar + S_bar^T)                      (E x D)
+//   s_a = S_bar[a,a],   u_aj = sum_e W[e,a] r_aje,   c_aj = beta_aj (M_bar_a + u_aj) - 2 s_a q_aj
+//   mu_bar_g = sum_a [ sum_j c_aj k_aj r_ajg  -  W[g,a] M_a / l_ag^2 ]
+// from dM_a/dm_g = V[g,a], dV[e,a]/dm_g = sum_j beta k r_e r_g - delta_eg M_a / l_ae^2, dv_a/dm_g = -2 sum_j q_aj k_aj r_ajg.
+//
+// Structure ("Gradients of the linearised propagation"):
+//   lin_bwd_tile_kernel       the forward's tile kernel in this file's own copy (moments_linear.hip, predict.hip and
+//                             predict_cov.hip are unchanged): one workgroup per (64 rows, 256-column block of iK_a, output a), the
+//                             k loop P = K*_a iK_a on v_mfma_f64_16x16x4_f64, compiled out where no variance term is needed.  Forward
+//                             form: the block's partial sums  sum_j P k | sum_j k beta | E sums beta k (x_j - m).  Reverse form:
+//                             every lane forms k and c for its 16 rows x 1 column from the row's coefficients
+//                             M_bar_a | s_a | W[e,a] / l_ae^2 (staged in LDS) and P, stages c k in LDS, and the contraction of the
+//                             forward leaves the E sums  sum_j c k (x_jg - m_g).
+//   lin_bwd_point_kernel      one wavefront per point, between the two tile launches: adds the forward sums in block order, forms
+//                             V, var_bar, W, the coefficients and  sum_a W[g,a] M_a / l_ag^2.
+//   lin_bwd_finish_kernel     one wavefront per point: adds the reverse sums in block order, scales, subtracts.
+//   rollout_linear_bwd_*      the trajectory: per chunk of candidates the forward is recomputed batch-major (one tile launch + one
+//                             wavefront per candidate and step, as gpmpc_rollout_linear) and KEEPS every step's M and the state
+//                             rows of V beside the trajectory; the cost variances come from the trajectory cost kernel.  Reverse
+//                             sweep t = H-1 .. 0 with A_t = I + V_s (Sigma_{t+1} = A_t^T Sigma_t A_t + diag v): one wavefront per
+//                             candidate closes step t + 1 (x_bar from the tile sums -> lambda, actions_bar) and opens step t (cost
+//                             partials by cost_adjoint_wave, W = 2 Sigma_t A_t Lambda on the state rows, the coefficients,
+//                             Lambda_t = sym(seeds) + A_t Lambda A_t^T, the model inputs), then one reverse tile launch over the
+//                             chunk: H + 1 small launches and H tile launches.
+// Every sum runs in an order fixed by N, E and D alone; a point's or candidate's bits do not depend on the batch, on its place in
+// it or on the chunks.  Plain kernels: no atomics, no waits between workgroups.  The workspace (Handle::linbws) is this file's
+// own, laid out by plan_moments_linear_backward (moments_linear_backward_plan.h).
+#include "grad_kernels.h"
+#include "moments_linear_backward_plan.h"
+
+namespace gpmpc_hip {
+
+namespace {
+
+constexpr int kBM = kLinBwdBM;           // rows per workgroup
+constexpr int kBN = kLinBwdBN;           // columns of iK per workgroup (64 per wave)
+constexpr int kBK = 16;                  // memory points per k step
+constexpr int kAPitch = kBM + 16;        // LDS row pitch (doubles) of the K* tile, stored [k][row]: rows 32 banks apart
+constexpr int kBPitch = kBN + 16;        // ... and of the iK tile [k][column]
+constexpr int kSlice = 64;               // columns of c k staged in LDS at a time (16 per wave)
+constexpr int kCkPitch = kBM + 2;        // LDS pitch (doubles) of s_ck [column][row]
+
+struct LbTileArgs {
+    const double* Xq;        // (rows, E) input means of this chunk
+    const double* Xt;        // (E, N)
+    const double* ils2;      // (D, E)
+    const double* var;       // (D)
+    const double* beta;      // (D, N)
+    const double* iK;        // (D, N, N)
+    const double* coef;      // (D, NW, Mc) reverse form: M_bar_a | s_a | E weights W[e,a] / l_ae^2
+    double* part;            // (D, nCB, NW, Mc) forward: sum_j P k | sum_j k beta | E sums; reverse: - | - | E sums
+    int rows, N, E, D, nCB, NW;
+    long long Mc;
+};
+
+struct LbPointArgs {
+    const double* part;
+    const double* ils2;      // (D, E)
+    const double* Sig;       // (rows, E, E) of this chunk, or NULL (= 0)
+    const double* Mb;        // (rows, D) or NULL
+    const double* Sb;        // (rows, D, D) or NULL
+    const double* Vb;        // (rows, E, D) or NULL
+    double* coef;            // written when mu_bar is asked for (with base)
+    double* base;            // (rows, E)
+    double* var_bar;         // (rows, E, E) of this chunk, or NULL
+    double* mu_bar;          // (rows, E) of this chunk, or NULL (finish kernel)
+    int E, D, nCB, NW;
+    long long Mc;
+};
+
+struct LbRollArgs {
+    const double* part;
+    const double* ils2;      // (D, E)
+    const double* var;       // (D)
+    const double* cost;      // target | W | W_T | smin | smax
+    const double* actions;   // (rows, H, A) of this chunk
+    double* mu;              // (rows, H + 1, D) recomputed trajectory of this chunk
+    double* Sig;             // (rows, H + 1, D, D)
+    double* stepM;           // (rows, H, D)
+    double* stepV;           // (rows, H, D, D) state rows of V [state input][output]
+    const double* cv;        // (rows, H + 1) cost variances (read with an objective seed only)
+    double* adj;             // (rows, 2 D + D D + A): lambda | Lambda | cost partials of the open step wrt mu and the action
+    double* coef;            // (D, NW, Mc)
+    double* base;            // (rows, E)
+    double* Xq;              // (Mc, E) model inputs of the next tile launch
+    SweepSeeds sd;           // this chunk's cotangents (each NULL = 0) and initial-state outputs (each NULL = not written)
+    double* actions_bar;     // (rows, H, A) of this chunk
+    int E, D, A, H, nCB, NW, t, include_time, use_constraints;
+    long long Mc;
+    double time0, kappa;
+    double mu0[kMaxD];       // read by the init kernel
+    double S0[kMaxD * kMaxD];
+};
+
+template <int EP>
+__device__ inline double kstar(const double* xq, const double (&xi)[EP], const double (&il)[EP], double sig2) {
+    double s = 0.0;
+#pragma unroll
+    for (int e = 0; e < EP; ++e) {
+        const double d = xq[e] - xi[e];
+        s = fma(d * d, il[e], s);
+    }
+    return sig2 * exp(-0.5 * s);
+}
+
+// P = K*_a iK_a for the workgroup's 64 rows and 256 columns (acc: the f64 MFMA C/D layout, see the epilogue).  The k loop of
+// moments_linear_tile_kernel / predict_tile_kernel: the same operations in the same order.
+template <int EP>
+__device__ inline void kstar_ik_product(const double* Xt, const double* iKa, int N, int E, int j0, const double (&il)[EP],
+                                        double sig2, const double (&s_xq)[kBM][EP + 1], double (&s_A)[kBK][kAPitch],
+                                        double (&s_B)[kBK][kBPitch], d4 (&acc)[4][4]) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // staging map: K* element (row gr + 16 q, point gi); iK elements (row bk, columns bc + 16 q)
+    const int gi = tid & 15, gr = tid >> 4;
+    const int bk = tid >> 4, bc = tid & 15;
+    const int nk = (N + kBK - 1) / kBK;
+    double breg[16];
+    auto load_b = [&](int i0) {
+        const int i = i0 + bk;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int j = j0 + bc + 16 * q;
+            breg[q] = (i < N && j < N) ? iKa[(size_t)i * N + j] : 0.0;
+        }
+    };
+    load_b(0);
+    for (int ks = 0; ks < nk; ++ks) {
+        const int i0 = ks * kBK;
+        __syncthreads();                         // the previous step's MFMAs have read s_A / s_B
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s_B[bk][bc + 16 * q] = breg[q];
+        {
+            const int i = i0 + gi;
+            double xi[EP];
+#pragma unroll
+            for (int e = 0; e < EP; ++e) xi[e] = (e < E && i < N) ? Xt[(size_t)e * N + i] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = gr + 16 * q;
+                s_A[gi][r] = (i < N) ? kstar<EP>(s_xq[r], xi, il, sig2) : 0.0;
+            }
+        }
+        __syncthreads();
+        if (ks + 1 < nk) load_b(i0 + kBK);       // next iK tile in flight under the MFMAs
+#pragma unroll
+        for (int s = 0; s < kBK / 4; ++s) {
+            const int k = 4 * s + (lane >> 4);
+            double av[4], bv[4];
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt) av[rt] = s_A[k][16 * rt + (lane & 15)];
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) bv[ct] = s_B[k][64 * w + 16 * ct + (lane & 15)];
+#pragma unroll
+            for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
+        }
+    }
+}
+
+// KLOOP: P = K* iK is formed (forward: the variance sum is wanted; reverse: s_a may be non-zero).  BWD: the reverse form.
+template <int EP, bool KLOOP, bool BWD>
+__global__ __launch_bounds__(256) void lin_bwd_tile_kernel(LbTileArgs p) {
+    constexpr int kLoop = kBK * kAPitch + kBK * kBPitch;
+    constexpr int kMem = (KLOOP && kLoop > kSlice * kCkPitch) ? kLoop : kSlice * kCkPitch;
+    constexpr int kQ = EP / 4;                       // inputs per thread in the contraction
+    constexpr int kCfRows = BWD ? kBM : 1;
+    __shared__ double s_xq[kBM][EP + 1];
+    __shared__ double s_xj[kSlice][EP + 1];
+    __shared__ double s_cf[kCfRows][EP + 3];         // reverse form: M_bar_a | s_a | W[e,a] / l_ae^2 of the tile's rows
+    __shared__ double s_red[4][kBM];
+    __shared__ double s_mem[kMem];
+    double (*s_ck)[kCkPitch] = reinterpret_cast<double (*)[kCkPitch]>(s_mem);
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int m0 = blockIdx.x * kBM;                 // first row of the tile (within the chunk)
+    const int cb = blockIdx.y, j0 = cb * kBN;
+    const int a = blockIdx.z;
+    const int N = p.N, E = p.E;
+    const double sig2 = p.var[a];
+    double il[EP];
+#pragma unroll
+    for (int e = 0; e < EP; ++e) il[e] = (e < E) ? p.ils2[a * E + e] : 0.0;
+    for (int idx = tid; idx < kBM * EP; idx += 256) {
+        const int r = idx / EP, e = idx - r * EP;
+        s_xq[r][e] = (e < E && m0 + r < p.rows) ? p.Xq[(size_t)(m0 + r) * E + e] : 0.0;
+    }
+    if constexpr (BWD) {
+        for (int idx = tid; idx < kBM * (EP + 2); idx += 256) {
+            const int c = idx / kBM, r = idx - c * kBM;
+            s_cf[r][c] = (c < E + 2 && m0 + r < p.rows) ? p.coef[((size_t)a * p.NW + c) * (size_t)p.Mc + m0 + r] : 0.0;
+        }
+    }
+    __syncthreads();
+
+    d4 acc[4][4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
+    if constexpr (KLOOP) {
+        auto& s_A = *reinterpret_cast<double (*)[kBK][kAPitch]>(s_mem);
+        auto& s_B = *reinterpret_cast<double (*)[kBK][kBPitch]>(s_mem + kBK * kAPitch);
+        kstar_ik_product<EP>(p.Xt, p.iK + (size_t)a * N * N, N, E, j0, il, sig2, s_xq, s_A, s_B, acc);
+    }
+
+    // epilogue: f64 C/D layout -- acc[rt][ct][r] = P[16 rt + (lane >> 4) + 4 r][64 w + 16 ct + (lane & 15)]
+    [[maybe_unused]] double rd[4][4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rd[rt][r] = 0.0;
+    // contraction state: row `crow`, inputs e = w + 4 q; forward form: wave 0 also sums beta k itself (the mean)
+    const int crow = tid & 63;
+    double xo[kQ], g[kQ];
+    [[maybe_unused]] double mn = 0.0;
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) {
+        xo[q] = s_xq[crow][w + 4 * q];
+        g[q] = 0.0;
+    }
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        __syncthreads();                             // the k loop's MFMAs / the previous slice's contraction are done
+        const int c = 16 * w + (lane & 15);          // this lane's column within the slice
+        const int j = j0 + 64 * w + 16 * ct + (lane & 15);
+        double xj[EP];
+#pragma unroll
+        for (int e = 0; e < EP; ++e) xj[e] = (e < E && j < N) ? p.Xt[(size_t)e * N + j] : 0.0;
+        if ((lane >> 4) == 0) {
+#pragma unroll
+            for (int e = 0; e < EP; ++e) s_xj[c][e] = xj[e];
+        }
+        const double bj = (j < N) ? p.beta[(size_t)a * N + j] : 0.0;
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * rt + (lane >> 4) + 4 * r;
+                double ck = 0.0;                     // columns past N contribute nothing (P there is 0 as well)
+                if (j < N) {
+                    const double k = kstar<EP>(s_xq[row], xj, il, sig2);
+                    if constexpr (BWD) {
+                        double u = 0.0;              // sum_e W[e,a] r_aje
+#pragma unroll
+                        for (int e = 0; e < EP; ++e) u = fma(s_cf[row][2 + e], xj[e] - s_xq[row][e], u);
+                        double cc = bj * (s_cf[row][0] + u);
+                        if constexpr (KLOOP) cc = fma(-2.0 * s_cf[row][1], acc[rt][ct][r], cc);
+                        ck = cc * k;
+                    } else {
+                        if constexpr (KLOOP) rd[rt][r] = fma(acc[rt][ct][r], k, rd[rt][r]);
+                        ck = bj * k;
+                    }
+                }
+                s_ck[c][row] = ck;
+            }
+        __syncthreads();
+#pragma unroll 4
+        for (int cs = 0; cs < kSlice; ++cs) {
+            const double ck = s_ck[cs][crow];
+            if constexpr (!BWD) {
+                if (w == 0) mn += ck;
+            }
+#pragma unroll
+            for (int q = 0; q < kQ; ++q) g[q] = fma(ck, s_xj[cs][w + 4 * q] - xo[q], g[q]);
+        }
+    }
+    const size_t rstride = (size_t)p.Mc;
+    double* dst = p.part + ((size_t)a * p.nCB + cb) * p.NW * rstride;      // [which][row]
+    if (m0 + crow < p.rows) {
+        if constexpr (!BWD) {
+            if (w == 0) dst[rstride + m0 + crow] = mn;
+        }
+#pragma unroll
+        for (int q = 0; q < kQ; ++q)
+            if (w + 4 * q < E) dst[(size_t)(2 + w + 4 * q) * rstride + m0 + crow] = g[q];
+    }
+    if constexpr (KLOOP && !BWD) {
+        // sum_j P k: the 16 lanes of a row (lane & 15), then the 4 waves in order
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                for (int off = 8; off >= 1; off >>= 1) rd[rt][r] += __shfl_xor(rd[rt][r], off, 64);
+                if ((lane & 15) == 0) s_red[w][16 * rt + (lane >> 4) + 4 * r] = rd[rt][r];
+            }
+        __syncthreads();
+        if (tid < kBM && m0 + tid < p.rows)
+            dst[m0 + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+    }
+}
+
+// sum over the column blocks, in block order, of partial sum `which` of (output a, row)
+__device__ inline double block_sum(const double* part, int a, int which, size_t row, int nCB, int NW, size_t Mc) {
+    const double* src = part + ((size_t)a * nCB * NW + which) * Mc + row;
+    double s = 0.0;
+    for (int cb = 0; cb < nCB; ++cb) s += src[(size_t)cb * NW * Mc];
+    return s;
+}
+
+// One wavefront per point, after the forward-form tile launch (no k loop: M and the Jacobian sums only).
+__global__ __launch_bounds__(64) void lin_bwd_point_kernel(LbPointArgs p) {
+    __shared__ double s_sum[kMaxD][kMaxE + 2];
+    __shared__ double s_V[kMaxE][kMaxD];
+    __shared__ double s_S2[kMaxD][kMaxD];            // S_bar + S_bar^T
+    __shared__ double s_T[kMaxE][kMaxD];             // V (S_bar + S_bar^T)
+    __shared__ double s_W[kMaxE][kMaxD];
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int D = p.D, E = p.E, NW = p.NW;
+    const size_t Mc = (size_t)p.Mc;
+    for (int idx = tid; idx < D * NW; idx += 64) {
+        const int a = idx / NW, which = idx - a * NW;
+        s_sum[a][which] = which == 0 ? 0.0 : block_sum(p.part, a, which, (size_t)m, p.nCB, NW, Mc);
+    }
+    const double* Sb = p.Sb ? p.Sb + (size_t)m * D * D : nullptr;
+    for (int idx = tid; idx < D * D; idx += 64) {
+        const int a = idx / D, b = idx - a * D;
+        s_S2[a][b] = Sb ? Sb[a * D + b] + Sb[b * D + a] : 0.0;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < E * D; idx += 64) {
+        const int e = idx / D, a = idx - e * D;
+        s_V[e][a] = p.ils2[a * E + e] * s_sum[a][2 + e];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < E * D; idx += 64) {
+        const int e = idx / D, b = idx - e * D;
+        double t = 0.0;
+        for (int a = 0; a < D; ++a) t = fma(s_V[e][a], s_S2[a][b], t);
+        s_T[e][b] = t;
+    }
+    __syncthreads();
+    if (p.var_bar) {                                 // sym(V S_bar V^T) = 1/2 T V^T: e <= f, mirrored -- exactly symmetric
+        double* vb = p.var_bar + (size_t)m * E * E;
+        for (int idx = tid; idx < E * E; idx += 64) {
+            const int e = idx / E, f = idx - e * E;
+            if (e > f) continue;
+            double q = 0.0;
+            for (int b = 0; b < D; ++b) q = fma(s_T[e][b], s_V[f][b], q);
+            q *= 0.5;
+            vb[e * E + f] = q;
+            vb[f * E + e] = q;
+        }
+    }
+    if (!p.mu_bar) return;
+    const double* Sg = p.Sig ? p.Sig + (size_t)m * E * E : nullptr;
+    const double* Vb = p.Vb ? p.Vb + (size_t)m * E * D : nullptr;
+    for (int idx = tid; idx < E * D; idx += 64) {    // W = V_bar + Sigma T
+        const int e = idx / D, b = idx - e * D;
+        double t = 0.0;
+        if (Sg)
+            for (int f = 0; f < E; ++f) t = fma(Sg[e * E + f], s_T[f][b], t);
+        s_W[e][b] = (Vb ? Vb[idx] : 0.0) + t;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * NW; idx += 64) {
+        const int a = idx / NW, which = idx - a * NW;
+        double v;
+        if (which == 0) v = p.Mb ? p.Mb[(size_t)m * D + a] : 0.0;
+        else if (which == 1) v = Sb ? Sb[a * D + a] : 0.0;
+        else v = s_W[which - 2][a] * p.ils2[a * E + which - 2];
+        p.coef[((size_t)a * NW + which) * Mc + m] = v;
+    }
+    for (int g = tid; g < E; g += 64) {
+        double t = 0.0;
+        for (int a = 0; a < D; ++a) t = fma(s_W[g][a] * p.ils2[a * E + g], s_sum[a][1], t);
+        p.base[(size_t)m * E + g] = t;
+    }
+}
+
+// x_bar_g = sum_a (1 / l_ag^2) sum_j c k (x_jg - m_g)  -  sum_a W[g,a] M_a / l_ag^2   (outputs in order, column blocks in order)
+__device__ inline double input_adjoint(const double* part, const double* ils2, const double* base_row, int g, size_t row, int D,
+                                       int E, int nCB, int NW, size_t Mc) {
+    double t = 0.0;
+    for (int a = 0; a < D; ++a) t = fma(ils2[a * E + g], block_sum(part, a, 2 + g, row, nCB, NW, Mc), t);
+    return t - base_row[g];
+}
+
+// One wavefront per point, after the reverse-form tile launch.
+__global__ __launch_bounds__(64) void lin_bwd_finish_kernel(LbPointArgs p) {
+    const int m = blockIdx.x, E = p.E;
+    for (int g = threadIdx.x; g < E; g += 64)
+        p.mu_bar[(size_t)m * E + g] = input_adjoint(p.part, p.ils2, p.base + (size_t)m * E, g, (size_t)m, p.D, E, p.nCB, p.NW,
+                                                   (size_t)p.Mc);
+}
+
+// ---- the trajectory ------------------------------------------------------------------------------------------------------------
+// Index 0 of the recomputed trajectory and the model inputs of step 0 (rollout_linear_init_kernel).
+__global__ __launch_bounds__(64) void rollout_linear_bwd_init_kernel(LbRollArgs p) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int D = p.D, E = p.E, A = p.A, H = p.H;
+    double* mu = p.mu + (size_t)b * (H + 1) * D;
+    double* Sg = p.Sig + (size_t)b * (H + 1) * D * D;
+    double* xq = p.Xq + (size_t)b * E;
+    for (int idx = tid; idx < D * D; idx += 64) Sg[idx] = p.S0[idx];
+    if (tid < D) {
+        mu[tid] = p.mu0[tid];
+        xq[tid] = p.mu0[tid];
+    }
+    if (tid < A) xq[D + tid] = p.actions[(size_t)b * H * A + tid];
+    if (p.include_time && tid == 0) xq[E - 1] = p.time0;
+}
+
+// One wavefront per candidate: step t -> t + 1 of the recomputed trajectory (the arithmetic of rollout_linear_step_kernel), the
+// step's M and V_s kept for the reverse sweep, and the model inputs of step t + 1.
+__global__ __launch_bounds__(64) void rollout_linear_bwd_forward_kernel(LbRollArgs p) {
+    __shared__ double s_sum[kMaxD][kMaxD + 2];       // sum P k | sum k beta | the Jacobian sums of the state inputs
+    __shared__ double s_V[kMaxD][kMaxD];             // V_s [state input][output]
+    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
+    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t V_s
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, NS = D + 2;
+    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
+    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
+    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
+    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
+    double* keepM = p.stepM + ((size_t)b * H + t) * D;
+    double* keepV = p.stepV + ((size_t)b * H + t) * D * D;
+    for (int idx = tid; idx < D * NS; idx += 64) {
+        const int a = idx / NS, which = idx - a * NS;
+        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
+    }
+    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {
+        const int i = idx / D, a = idx - i * D;
+        const double v = p.ils2[a * E + i] * s_sum[a][2 + i];
+        s_V[i][a] = v;
+        keepV[idx] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t V_s
+        const int i = idx / D, c = idx - i * D;
+        double v = 0.0;
+        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_V[k][c], v);
+        s_T[i][c] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
+        const int a = idx / D, c = idx - a * D;
+        if (a > c) continue;
+        double q = 0.0;
+        for (int i = 0; i < D; ++i) q = fma(s_V[i][a], s_T[i][c], q);
+        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
+        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
+        Sg_n[a * D + c] = v;
+        Sg_n[c * D + a] = v;
+    }
+    const bool more = t + 1 < H;
+    double* xq = p.Xq + (size_t)b * E;
+    if (tid < D) {
+        const double v = mu_t[tid] + s_sum[tid][1];
+        keepM[tid] = s_sum[tid][1];
+        mu_n[tid] = v;
+        if (more) xq[tid] = v;
+    }
+    if (more) {
+        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
+        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
+    }
+}
+
+// One wavefront per candidate of the reverse sweep.  t_post >= 0: the reverse tile launch of step t_post is done -- x_bar from its
+// sums, lambda_t = lambda_{t+1} + x_bar[:D] + (cost partial + seed), actions_bar_t = (cost partial) + x_bar[D:D+A]; t_post < 0
+// (first launch): the adjoints start at the terminal index H.  t_pre >= 0: step t_pre is opened -- its cost partials and seeds,
+// A = I + V_s, W = 2 Sigma_t A Lambda, the coefficients and model inputs of its tile launch, Lambda_t = sym(.) + A Lambda A^T;
+// t_pre < 0 (last launch): lambda_0 / Lambda_0 go to mu0_bar / S0_bar.
+__global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollArgs p, int t_post, int t_pre) {
+    constexpr int kN = kMaxE;                        // D + A <= E <= kMaxE
+    __shared__ double s_cost[kN + kN * kN + kMaxD * kMaxD + 2 * kMaxD];
+    __shared__ double s_tmp[2 * kN * kN + 3 * kN];
+    __shared__ double s_lam[kMaxD], s_Lam[kMaxD * kMaxD];
+    __shared__ double s_gmu[kMaxD], s_gSig[kMaxD * kMaxD], s_gu[kN];
+    __shared__ double s_mu[kMaxD], s_Sg[kMaxD * kMaxD], s_act[kN], s_M[kMaxD];
+    __shared__ double s_A[kMaxD][kMaxD], s_AL[kMaxD][kMaxD], s_W[kMaxD][kMaxD];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int D = p.D, E = p.E, A = p.A, H = p.H, DD = D * D, n = D + A, NW = p.NW;
+    const size_t Mc = (size_t)p.Mc;
+    const SweepSeeds& sd = p.sd;
+    const bool has_cm = sd.cm != nullptr, has_cv = sd.cv != nullptr, has_J = sd.J != nullptr;
+    const bool cost_on = has_cm || has_cv || has_J;
+    const double inv_n = 1.0 / (double)(H + 1);
+    double* adj = p.adj + (size_t)b * (2 * D + DD + A);
+    double* g_lam = adj;
+    double* g_Lam = adj + D;
+    double* g_gmu = g_Lam + DD;
+    double* g_gu = g_gmu + D;
+    if (cost_on)
+        for (int i = lane; i < n + n * n + DD + 2 * D; i += 64) s_cost[i] = p.cost[i];
+    const double* target = s_cost;
+    const double* Wst = s_cost + n;
+    const double* WT = Wst + n * n;
+    const double* smin = WT + DD;
+    const double* smax = smin + D;
+    const double jb = has_J ? sd.J[b] : 0.0;
+
+    // cost partials (weighted by the seeds) and trajectory seeds of time index t -> s_gmu, s_gSig, s_gu; reads s_mu / s_Sg / s_act
+    auto stage_adjoint = [&](int t) {
+        const bool terminal = (t == H);
+        const size_t bt = (size_t)b * (H + 1) + t;
+        for (int i = lane; i < D; i += 64) s_mu[i] = p.mu[bt * D + i];
+        for (int i = lane; i < DD; i += 64) s_Sg[i] = p.Sig[bt * DD + i];
+        if (!terminal)
+            for (int i = lane; i < A; i += 64) s_act[i] = p.actions[((size_t)b * H + t) * A + i];
+        wave_lds_sync();
+        if (cost_on) {
+            double wm, wv;
+            seeded_cost_weights(has_cm, has_cm ? sd.cm[bt] : 0.0, has_cv, has_cv ? sd.cv[bt] : 0.0, has_J, jb, p.kappa,
+                                has_J ? p.cv[bt] : 1.0, inv_n, wm, wv);
+            cost_adjoint_wave(lane, D, A, terminal, s_mu, s_Sg, s_act, target, terminal ? WT : Wst, smin, smax,
+                              p.use_constraints != 0, wm, wv, s_tmp, s_gmu, s_gSig, s_gu);
+            wave_lds_sync();
+        }
+        for (int i = lane; i < D; i += 64) {
+            double v = cost_on ? s_gmu[i] : 0.0;
+            if (sd.mu) v += sd.mu[bt * D + i];
+            s_gmu[i] = v;
+        }
+        for (int i = lane; i < DD; i += 64) {
+            double v = cost_on ? s_gSig[i] : 0.0;
+            if (sd.Sig) v += sd.Sig[bt * DD + i];
+            s_gSig[i] = v;
+        }
+        if (!cost_on || terminal)
+            for (int i = lane; i < A; i += 64) s_gu[i] = 0.0;
+        wave_lds_sync();
+    };
+
+    wave_lds_sync();
+    if (t_post >= 0) {
+        double x = 0.0;
+        if (lane < D + A) x = input_adjoint(p.part, p.ils2, p.base + (size_t)b * E, lane, (size_t)b, D, E, p.nCB, NW, Mc);
+        if (lane < D) s_lam[lane] = (g_lam[lane] + x) + g_gmu[lane];
+        else if (lane < D + A) p.actions_bar[((size_t)b * H + t_post) * A + lane - D] = g_gu[lane - D] + x;      // (time: no gradient)
+        for (int i = lane; i < DD; i += 64) s_Lam[i] = g_Lam[i];
+    } else {
+        stage_adjoint(H);
+        for (int i = lane; i < D; i += 64) s_lam[i] = s_gmu[i];
+        for (int i = lane; i < DD; i += 64) {
+            const int r = i / D, q = i - r * D;
+            s_Lam[i] = 0.5 * (s_gSig[i] + s_gSig[q * D + r]);
+        }
+    }
+    wave_lds_sync();
+    if (t_pre < 0) {
+        if (sd.mu0_bar)
+            for (int i = lane; i < D; i += 64) sd.mu0_bar[(size_t)b * D + i] = s_lam[i];
+        if (sd.S0_bar)
+            for (int i = lane; i < DD; i += 64) sd.S0_bar[(size_t)b * DD + i] = s_Lam[i];
+        return;
+    }
+    const int t = t_pre;
+    stage_adjoint(t);
+    const double* keepM = p.stepM + ((size_t)b * H + t) * D;
+    const double* keepV = p.stepV + ((size_t)b * H + t) * DD;
+    for (int i = lane; i < D; i += 64) s_M[i] = keepM[i];
+    for (int idx = lane; idx < DD; idx += 64) {
+        const int i = idx / D, a = idx - i * D;
+        s_A[i][a] = keepV[idx] + (i == a ? 1.0 : 0.0);
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < DD; idx += 64) {                  // A Lambda
+        const int i = idx / D, a = idx - i * D;
+        double v = 0.0;
+        for (int c = 0; c < D; ++c) v = fma(s_A[i][c], s_Lam[c * D + a], v);
+        s_AL[i][a] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < DD; idx += 64) {                  // W = 2 Sigma_t A Lambda
+        const int i = idx / D, a = idx - i * D;
+        double v = 0.0;
+        for (int k = 0; k < D; ++k) v = fma(s_Sg[i * D + k], s_AL[k][a], v);
+        s_W[i][a] = 2.0 * v;
+    }
+    for (int idx = lane; idx < DD; idx += 64) {                  // Lambda_t: i <= j, mirrored -- exactly symmetric
+        const int i = idx / D, j = idx - i * D;
+        if (i > j) continue;
+        double v = 0.0;
+        for (int a = 0; a < D; ++a) v = fma(s_AL[i][a], s_A[j][a], v);
+        v += 0.5 * (s_gSig[i * D + j] + s_gSig[j * D + i]);
+        g_Lam[i * D + j] = v;
+        g_Lam[j * D + i] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < D * NW; idx += 64) {
+        const int a = idx / NW, which = idx - a * NW;
+        double v;
+        if (which == 0) v = s_lam[a];
+        else if (which == 1) v = s_Lam[a * D + a];
+        else v = (which - 2 < D) ? s_W[which - 2][a] * p.ils2[a * E + which - 2] : 0.0;
+        p.coef[((size_t)a * NW + which) * Mc + b] = v;
+    }
+    for (int g = lane; g < E; g += 64) {
+        double v = 0.0;
+        if (g < D)
+            for (int a = 0; a < D; ++a) v = fma(s_W[g][a] * p.ils2[a * E + g], s_M[a], v);
+        p.base[(size_t)b * E + g] = v;
+    }
+    double* xq = p.Xq + (size_t)b * E;
+    for (int i = lane; i < D; i += 64) {
+        g_lam[i] = s_lam[i];
+        g_gmu[i] = s_gmu[i];
+        xq[i] = s_mu[i];
+    }
+    for (int i = lane; i < A; i += 64) {
+        g_gu[i] = s_gu[i];
+        xq[D + i] = s_act[i];
+    }
+    if (p.include_time && lane == 0) xq[E - 1] = p.time0 + (double)t;
+}
+
+template <int EP>
+void launch_tiles_ep(const LbTileArgs& p, bool kloop, bool bwd, hipStream_t s) {
+    const dim3 grid((p.rows + kBM - 1) / kBM, p.nCB, p.D);
+    if (bwd) {
+        if (kloop) hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, true, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, false, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (kloop) hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, true, false>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, false, false>), grid, dim3(256), 0, s, p);
+    }
+}
+
+void launch_tiles(const LbTileArgs& p, bool kloop, bool bwd, hipStream_t s) {
+    if (p.E <= 4) launch_tiles_ep<4>(p, kloop, bwd, s);
+    else if (p.E <= 8) launch_tiles_ep<8>(p, kloop, bwd, s);
+    else if (p.E <= 16) launch_tiles_ep<16>(p, kloop, bwd, s);
+    else launch_tiles_ep<24>(p, kloop, bwd, s);
+}
+
+}  // namespace
+
+int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
+                                const double* Vb, double* mb_out, double* vb_out, hipStream_t s) {
+    const int N = h->N, D = h->D, E = h->E;
+    if (P == 0 || (!mb_out && !vb_out)) return GPMPC_OK;
+    if (vb_out && !Sb) {                             // var_bar = sym(V S_bar V^T) = 0
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(vb_out, 0, (size_t)P * E * E * sizeof(double), s));
+        vb_out = nullptr;
+    }
+    if (mb_out && !Mb && !Sb && !Vb) {
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(mb_out, 0, (size_t)P * E * sizeof(double), s));
+        mb_out = nullptr;
+    }
+    if (!mb_out && !vb_out) return GPMPC_OK;
+    LinearBwdPlan pl;
+    plan_moments_linear_backward(N, D, E, 0, P, 0, h->opt_moments_linear_bwd_chunk, pl);
+    int rc = grow(h, h->linbws, pl.total);
+    if (rc) return rc;
+    double* ws = h->linbws.p;
+    LbTileArgs p{};
+    p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.beta = h->beta.p; p.iK = h->iK.p;
+    p.part = ws + pl.part; p.coef = ws + pl.coef;
+    p.N = N; p.E = E; p.D = D; p.nCB = pl.nCB; p.NW = pl.NW; p.Mc = pl.Mc;
+    LbPointArgs f{};
+    f.part = p.part; f.ils2 = p.ils2; f.coef = ws + pl.coef; f.base = ws + pl.base;
+    f.E = E; f.D = D; f.nCB = pl.nCB; f.NW = pl.NW; f.Mc = pl.Mc;
+    for (long long m0 = 0; m0 < P; m0 += pl.chunk) {
+        const int rows = (int)((P - m0) < pl.chunk ? (P - m0) : pl.chunk);
+        p.rows = rows;
+        p.Xq = mu + (size_t)m0 * E;
+        launch_tiles(p, false, false, s);            // M and the Jacobian sums: no matrix product
+        f.Sig = Sig ? Sig + (size_t)m0 * E * E : nullptr;
+        f.Mb = Mb ? Mb + (size_t)m0 * D : nullptr;
+        f.Sb = Sb ? Sb + (size_t)m0 * D * D : nullptr;
+        f.Vb = Vb ? Vb + (size_t)m0 * E * D : nullptr;
+        f.var_bar = vb_out ? vb_out + (size_t)m0 * E * E : nullptr;
+        f.mu_bar = mb_out ? mb_out + (size_t)m0 * E : nullptr;
+        hipLaunchKernelGGL(lin_bwd_point_kernel, dim3(rows), dim3(64), 0, s, f);
+        if (mb_out) {
+            launch_tiles(p, Sb != nullptr, true, s);
+            hipLaunchKernelGGL(lin_bwd_finish_kernel, dim3(rows), dim3(64), 0, s, f);
+        }
+    }
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    return GPMPC_OK;
+}
+
+// a: filled by the entry point (model, cost settings, actions, shape, initial state); sd: the cotangents and initial-state outputs
+int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, double* actions_bar, hipStream_t s) {
+    const int N = a.N, D = a.D, E = a.E, A = a.A, H = a.H, B = a.B;
+    LinearBwdPlan pl;
+    plan_moments_linear_backward(N, D, E, A, B, H, h->opt_moments_linear_bwd_chunk, pl);
+    int rc = grow(h, h->linbws, pl.total);
+    if (rc) return rc;
+    double* ws = h->linbws.p;
+    LbTileArgs p{};
+    p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.beta = h->beta.p; p.iK = h->iK.p;
+    p.part = ws + pl.part; p.coef = ws + pl.coef; p.Xq = ws + pl.xq;
+    p.N = N; p.E = E; p.D = D; p.nCB = pl.nCB; p.NW = pl.NW; p.Mc = pl.Mc;
+    LbRollArgs q{};
+    q.part = p.part; q.ils2 = p.ils2; q.var = p.var; q.cost = a.cost;
+    q.mu = ws + pl.mu; q.Sig = ws + pl.Sig; q.stepM = ws + pl.stepM; q.stepV = ws + pl.stepV; q.cv = ws + pl.cv;
+    q.adj = ws + pl.adj; q.coef = ws + pl.coef; q.base = ws + pl.base; q.Xq = ws + pl.xq;
+    q.E = E; q.D = D; q.A = A; q.H = H; q.nCB = pl.nCB; q.NW = pl.NW; q.Mc = pl.Mc;
+    q.include_time = a.include_time; q.time0 = a.time0; q.kappa = a.kappa; q.use_constraints = a.use_constraints;
+    for (int d = 0; d < D; ++d) q.mu0[d] = a.mu0[d];
+    for (int d = 0; d < D * D; ++d) q.S0[d] = a.S0[d];
+    const size_t T1 = (size_t)(H + 1);
+    for (long long b0 = 0; b0 < B; b0 += pl.chunk) {
+        const int rows = (int)((B - b0) < pl.chunk ? (B - b0) : pl.chunk);
+        const size_t o = (size_t)b0;
+        p.rows = rows;
+        q.actions = a.actions + o * H * A;
+        q.actions_bar = actions_bar + o * H * A;
+        q.sd.mu = sd.mu ? sd.mu + o * T1 * D : nullptr;
+        q.sd.Sig = sd.Sig ? sd.Sig + o * T1 * D * D : nullptr;
+        q.sd.cm = sd.cm ? sd.cm + o * T1 : nullptr;
+        q.sd.cv = sd.cv ? sd.cv + o * T1 : nullptr;
+        q.sd.J = sd.J ? sd.J + o : nullptr;
+        q.sd.mu0_bar = sd.mu0_bar ? sd.mu0_bar + o * D : nullptr;
+        q.sd.S0_bar = sd.S0_bar ? sd.S0_bar + o * D * D : nullptr;
+        // the forward, recomputed
+        q.t = 0;
+        hipLaunchKernelGGL(rollout_linear_bwd_init_kernel, dim3(rows), dim3(64), 0, s, q);
+        for (int t = 0; t < H; ++t) {
+            launch_tiles(p, true, false, s);
+            q.t = t;
+            hipLaunchKernelGGL(rollout_linear_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, q);
+        }
+        GPMPC_HIP_CHECK(h, hipGetLastError());
+        if (sd.J) {                                   // the objective's weights need the cost variances
+            RolloutArgs c = a;
+            c.B = rows;
+            c.actions = q.actions;
+            c.mu_out = q.mu; c.Sig_out = q.Sig;
+            rc = launch_traj_cost(h, c, nullptr, ws + pl.cv, nullptr, s);
+            if (rc) return rc;
+        }
+        // the reverse sweep
+        hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel, dim3(rows), dim3(64), 0, s, q, -1, H - 1);
+        for (int t = H - 1; t >= 0; --t) {
+            launch_tiles(p, true, true, s);
+            hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel, dim3(rows), dim3(64), 0, s, q, t, t - 1);
+        }
+        GPMPC_HIP_CHECK(h, hipGetLastError());
+    }
+    return GPMPC_OK;
+}
+
+}  // namespace gpmpc_hip

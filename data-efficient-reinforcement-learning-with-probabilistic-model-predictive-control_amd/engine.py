@@ -316,6 +316,31 @@ class HipEngine:
         self._keep_moments_backward = (mu, vr, Mb, Sb, Vb)   # alive until the asynchronous call has read them
         return out
 
+    def moments_linear_backward(self, mu, var=None, M_bar=None, S_bar=None, V_bar=None, mu_bar=True, var_bar=True):
+        """Reverse-mode product of `moments_linear` (gpmpc_moments_linear_backward): mu (P, E), var (P, E, E) or None (zero),
+        upstream gradients M_bar (P, D), S_bar (P, D, D), V_bar (P, E, D), each None for zero -> dict(mu_bar (P, E),
+        var_bar (P, E, E)) of device tensors (each only when requested).  var_bar is the symmetric part of the covariance
+        gradient, exactly symmetric.  Without S_bar no matrix product runs.  Asynchronous on the current stream."""
+        mu = self._dev(mu)
+        if mu.dim() != 2:
+            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
+        P, E = mu.shape
+        D = self.D
+        vr = self._dev(var, (P, E, E)) if var is not None else None
+        Mb = self._dev(M_bar, (P, D)) if M_bar is not None else None
+        Sb = self._dev(S_bar, (P, D, D)) if S_bar is not None else None
+        Vb = self._dev(V_bar, (P, E, D)) if V_bar is not None else None
+        out = {}
+        if mu_bar:
+            out["mu_bar"] = torch.empty((P, E), dtype=torch.float64, device=self.device)
+        if var_bar:
+            out["var_bar"] = torch.empty((P, E, E), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_moments_linear_backward(self._h, mu.data_ptr(), ptr(vr), P, D, E, ptr(Mb), ptr(Sb), ptr(Vb),
+                                                           ptr(out.get("mu_bar")), ptr(out.get("var_bar")), self._stream()))
+        self._keep_moments_linear_backward = (mu, vr, Mb, Sb, Vb)   # alive until the asynchronous call has read them
+        return out
+
     # -- a6 ----------------------------------------------------------------------------
     def set_cost(self, target, W, W_T, kappa, clip_to_zero=False, state_min=None, state_max=None):
         W_T = _host(W_T)
@@ -448,6 +473,45 @@ class HipEngine:
                                                     ptr(out.get("S0_bar")), self._stream()))
         self._keep_rollout_backward = (actions, mb, Sb, cmb, cvb, Jb)   # alive until the asynchronous call has read them
         return out
+
+    def rollout_linear_backward(self, actions, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None,
+                                cost_mu_bar=None, cost_var_bar=None, J_bar=None, want_initial=True):
+        """Reverse-mode product of `rollout_linear` (gpmpc_rollout_linear_backward), with the arguments and the result of
+        `rollout_backward`: dict of device tensors actions_bar (B,H,A) and, with `want_initial`, mu0_bar (B,D) and S0_bar (B,D,D)
+        per candidate (S0_bar the symmetric part).  The forward is recomputed inside the call.  Cost / J seeds need set_cost.
+        Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
+        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
+        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
+        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
+        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
+        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
+        if want_initial:
+            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
+            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_rollout_linear_backward(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A,
+                                                           int(bool(include_time)), float(time0), ptr(mb), ptr(Sb), ptr(cmb),
+                                                           ptr(cvb), ptr(Jb), out["actions_bar"].data_ptr(),
+                                                           ptr(out.get("mu0_bar")), ptr(out.get("S0_bar")), self._stream()))
+        self._keep_rollout_linear_backward = (actions, mb, Sb, cmb, cvb, Jb)   # alive until the asynchronous call has read them
+        return out
+
+    def rollout_linear_grad(self, actions, mu0, S0, include_time=False, time0=0.0):
+        """Objective of the linearised rollout and its analytic gradient: dict(J (B,), grad (B,H,A) = dJ/d(actions)) of device
+        tensors, from `rollout_linear` followed by `rollout_linear_backward` with J_bar = 1."""
+        actions = self._dev(actions)
+        B = actions.shape[0]
+        J = torch.empty(B, dtype=torch.float64, device=self.device)
+        self.rollout_linear(actions, mu0, S0, include_time, time0, trajectories=False, stage_costs=False, out={"J": J})
+        ones = torch.ones(B, dtype=torch.float64, device=self.device)
+        back = self.rollout_linear_backward(actions, mu0, S0, include_time, time0, J_bar=ones, want_initial=False)
+        return {"J": J, "grad": back["actions_bar"]}
 
     def objective_grad_host(self, actions, mu0, S0, include_time=False, time0=0.0):
         """ONE action sequence (H, A) on the host -> objective, gradient, trajectory and stage costs on the host

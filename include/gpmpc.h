@@ -217,6 +217,38 @@ int gpmpc_moments_linear(gpmpc_t* h, const double* mu_dev, const double* var_dev
                          double* S_out_dev, double* V_out_dev, void* stream);
 
 /*
+ * gpmpc_moments_linear_backward: the reverse-mode product (vector-Jacobian product) of gpmpc_moments_linear at the same P inputs
+ * -- what torch autograd gives through the formulas of gpmpc_moments_linear.  For upstream gradients M_bar, S_bar, V_bar it
+ * returns the gradients of <M_bar, M> + <S_bar, S> + <V_bar, V> with respect to the input mean m and the input covariance Sigma.
+ * Arguments, layouts and NULL rules are those of gpmpc_moments_backward:
+ *   mu_dev (P,E), var_dev (P,E,E) or NULL (= 0; the gradient at Sigma = 0 is still returned)
+ *   M_bar_dev (P,D), S_bar_dev (P,D,D), V_bar_dev (P,E,D)   upstream gradients, each NULL (= 0)
+ *   mu_bar_out_dev (P,E), var_bar_out_dev (P,E,E)           each NULL (not written); overwritten, not accumulated into
+ * With d_je = x_je - m_e (formed per element, as the forward does), r_aje = d_je / l_ae^2, k_aj as in gpmpc_moments_linear and
+ * q_a = iK_a k_a (a row of K* iK):
+ *   var_bar  = sym(V S_bar V^T)                       (E x E, exactly symmetric; the symmetric part, by the rule of
+ *                                                      gpmpc_moments_backward)
+ *   W        = V_bar + Sigma V (S_bar + S_bar^T)      (E x D)
+ *   s_a      = S_bar[a,a],   u_aj = sum_e W[e,a] r_aje,   c_aj = beta_aj (M_bar_a + u_aj) - 2 s_a q_aj
+ *   mu_bar_g = sum_a [ sum_j c_aj k_aj r_ajg  -  W[g,a] M_a / l_ag^2 ]
+ * (dM_a/dm_g = V[g,a]; dV[e,a]/dm_g = sum_j beta k r_e r_g - delta_eg M_a / l_ae^2; dv_a/dm_g = -2 sum_j q_aj k_aj r_ajg).  Sigma
+ * is taken as symmetric in W.  iK is treated as symmetric, with the caveat of gpmpc_predict_backward: a non-symmetric iK passed
+ * through gpmpc_set_factors gets 2 K* iK, not K* (iK + iK^T).  Hyper-parameters and the memory get no gradient.  W depends on
+ * the forward's V: the call runs the forward's M / V pass (O(N E D) per point, no matrix product), then one tile launch whose k
+ * loop forms q on the matrix cores and whose epilogue contracts c k r.  With S_bar_dev NULL no matrix product runs at all; with
+ * all three upstream gradients NULL the outputs are zeros and no kernel of the model runs.  A point's results are bitwise the
+ * same whatever P is, wherever the point sits, whatever its neighbours are and however the batch is chunked
+ * ("moments_linear_backward_chunk_points"); a NULL upstream and an all-zero one give the same bits.  Every sum runs in an order
+ * fixed by N, E and D alone; no atomics.  Workspace of its own, within 16 MB (or one 64-row tile's need if that is more).  Touches
+ * no other workspace and no gpmpc_last_* state.  Asynchronous on `stream`; P = 0 launches nothing.  Errors as
+ * gpmpc_moments_backward: GPMPC_ERR_ARG for no cached model, D / E different from the cached model, P < 0, mu_dev NULL with
+ * P > 0; GPMPC_ERR_LIMIT for D > GPMPC_MAX_D or E > GPMPC_MAX_E.
+ */
+int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double* var_dev, int P, int D, int E,
+                                  const double* M_bar_dev, const double* S_bar_dev, const double* V_bar_dev,
+                                  double* mu_bar_out_dev, double* var_bar_out_dev, void* stream);
+
+/*
  * Options.  Behaviour: "incremental" (0/1, default 1: reuse / border-update the cached factors), "refresh_every" (32: border
  * updates between full factorisations), "cluster" (few-candidate cooperative form: 0 auto, 1 never, 2..32 workgroups per
  * candidate), "threads" (fused-horizon workgroup: 0 auto, 256 / 512 / 1024), "pair_tiles" (batch-major rollout path: 0 auto,
@@ -226,7 +258,8 @@ int gpmpc_moments_linear(gpmpc_t* h, const double* mu_dev, const double* var_dev
  * query rows per internal chunk: 0 auto, else a multiple of 64), "predict_backward_chunk_rows" (the same for
  * gpmpc_predict_backward), "predict_cov_chunk_rows" (the same for gpmpc_predict_cov's rows of Xa),"moments_chunk_points" (gpmpc_moments' points per internal
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
- * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto).  Measurement (A/B) switches of single
+ * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
+ * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);
@@ -324,6 +357,42 @@ int gpmpc_rollout_backward(gpmpc_t* h, const double* actions_dev, const double* 
                            int include_time, double time0, const double* mu_bar_dev, const double* Sig_bar_dev,
                            const double* cost_mu_bar_dev, const double* cost_var_bar_dev, const double* J_bar_dev,
                            double* actions_bar_out_dev, double* mu0_bar_out_dev, double* S0_bar_out_dev, void* stream);
+
+/*
+ * gpmpc_rollout_linear_backward: the reverse-mode product (vector-Jacobian product) of gpmpc_rollout_linear for B candidates, with
+ * the arguments of gpmpc_rollout_backward without any change of meaning.  It returns the gradients of
+ *     sum_t <mu_bar_t, mu_t> + <Sig_bar_t, Sig_t> + cost_mu_bar_t cost_mu_t + cost_var_bar_t cost_var_t  +  J_bar J
+ * (mu_t, Sig_t, cost_mu_t, cost_var_t, J: what gpmpc_rollout_linear writes for the same inputs and the same loaded cost) with
+ * respect to each candidate's actions and to the initial mean and covariance, per candidate.  Cotangents (each NULL = 0):
+ *   mu_bar_dev (B,H+1,D)  Sig_bar_dev (B,H+1,D,D)  cost_mu_bar_dev (B,H+1)  cost_var_bar_dev (B,H+1)  J_bar_dev (B)
+ * Outputs, overwritten (not accumulated into):
+ *   actions_bar_out_dev (B,H,A)  required
+ *   mu0_bar_out_dev (B,D)        or NULL (not written)
+ *   S0_bar_out_dev (B,D,D)       or NULL (not written): the symmetric part of the covariance gradient, exactly symmetric;
+ *                                Sig_bar is symmetrised on entry
+ * clip_to_zero is pass-through for J; the time input is not differentiated; the cost cotangents weigh the stage-cost partials by
+ * the rule of gpmpc_rollout_backward: wm_t = cost_mu_bar_t + J_bar / (H+1), wv_t = cost_var_bar_t + J_bar (-kappa /
+ * (2 sqrt(cost_var_t))) / (H+1); constraints and the terminal weight enter as there.
+ * Reverse sweep: with A_t = I + V_s (V_s: the state rows of step t's V) the forward recurrence is Sigma_{t+1} = A_t^T Sigma_t A_t
+ * + diag v.  The adjoints lambda_t (D) and Lambda_t (D x D, symmetric) start from mu_bar_t, sym(Sig_bar_t) and the stage /
+ * terminal cost partials; for t = H-1 .. 0 the step formula of gpmpc_moments_linear_backward runs with M_bar = lambda_{t+1},
+ * W = 2 Sigma_t A_t Lambda_{t+1} on the state rows (0 elsewhere), s_a = Lambda_{t+1}[a,a] and gives x_bar (E); then
+ *   lambda_t += lambda_{t+1} + x_bar[:D],   actions_bar_t = (cost partial) + x_bar[D:D+A],   Lambda_t += A_t Lambda_{t+1} A_t^T
+ * The forward is RECOMPUTED inside the call (the entry is stateless) and keeps every step's M and V_s beside the trajectory, per
+ * chunk of candidates.  Batch-major like the forward: per reverse step one tile launch over all candidates of a chunk (its k
+ * loop on the matrix cores) and one wavefront per candidate for the D x E algebra.  A candidate's results are bitwise the same
+ * alone and at any position of any batch, whatever "moments_linear_backward_chunk_points" is; a NULL cotangent and an all-zero
+ * one give the same bits.  Every sum runs in an order fixed by N, E and D alone; no atomics.  Workspace of its own (a chunk runs
+ * its forward and its whole reverse sweep), within 16 MB or one 64-row tile's need.  Touches no other workspace and no
+ * gpmpc_last_* state.  Asynchronous on `stream`.  GPMPC_ERR_ARG: actions_bar_out_dev NULL, A < 1, a cost / J cotangent without
+ * gpmpc_set_cost for this (D, A) (the trajectory's cotangents alone need no cost settings), and the argument errors of
+ * gpmpc_rollout_linear (no cached model, NULL actions / mu0 / S0, B < 1, H < 1, D + A (+1) != E).
+ */
+int gpmpc_rollout_linear_backward(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B,
+                                  int H, int A, int include_time, double time0, const double* mu_bar_dev,
+                                  const double* Sig_bar_dev, const double* cost_mu_bar_dev, const double* cost_var_bar_dev,
+                                  const double* J_bar_dev, double* actions_bar_out_dev, double* mu0_bar_out_dev,
+                                  double* S0_bar_out_dev, void* stream);
 
 /*
  * gpmpc_objective_grad_host  <->  ONE call of compute_mean_lcb_trajectory (gp_mpc_controller.py:229-285) as scipy's L-BFGS-B

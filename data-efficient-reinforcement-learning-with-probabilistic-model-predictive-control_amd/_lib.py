@@ -58,6 +58,7 @@ SIGNATURES = {
     "gpmpc_set_cost": (C.c_int, [_P, _P, _P, _P, _D, _I, _P, _P, _I, _I]),
     "gpmpc_rollout": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout_linear_feedback": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_grad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -71,7 +72,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 def load(path=LIB_PATH):

@@ -73,8 +73,12 @@ class GpMpcController(BaseControllerObject):
     def _check_propagation_supported(self, what=None):
         """ModelConfig.uncertainty_propagation = "linearized" has objective values only (gpmpc_rollout_linear): the searches
         that go through `evaluate_candidates` work; the device-side search, the batched L-BFGS and the scipy L-BFGS-B loop
-        need kernels (search, gradient) the linearised path does not have."""
+        need kernels (search, gradient) the linearised path does not have.  ControllerConfig.feedback_gain (closed-loop
+        planning, gpmpc_rollout_linear_feedback) exists for the linearised propagation only."""
         if self.transition_model.propagation() != "linearized":
+            if getattr(self.config.controller, "feedback_gain", None) is not None:
+                raise ValueError("ControllerConfig.feedback_gain needs ModelConfig.uncertainty_propagation='linearized': "
+                                 "moment matching has no closed-loop rollout")
             return
         cc = self.config.controller
         if what is None:
@@ -146,12 +150,26 @@ class GpMpcController(BaseControllerObject):
         """Objective of B optimiser vectors (B, H*A) in one launch -> dict of device tensors + 'actions_model'."""
         acts = self.actions_mapper.mpc_to_model_batch(np.asarray(actions_mpc_batch, dtype=np.float64))
         self.transition_model.set_cost(self.config.reward)
+        gain = getattr(self.config.controller, "feedback_gain", None)
+        if gain is not None:
+            self._check_propagation_supported()
+        kw = {} if gain is None else {"feedback_gains": self._feedback_gain_on_device(gain)}      # open loop: the call as ever
         out = self.transition_model.predict_trajectory_batch(
             acts, obs_mu, obs_var, self.config.controller.len_horizon, self.iter_ctrl,
-            trajectories=trajectories, stage_costs=True)
+            trajectories=trajectories, stage_costs=True, **kw)
         self.num_rollouts += acts.shape[0]
         out["actions_model"] = acts
         return out
+
+    def _feedback_gain_on_device(self, gain):
+        """ControllerConfig.feedback_gain as a tensor on the engine's device, uploaded once: compared by CONTENT with what was
+        uploaded last, as set_cost does, so that in-place edits of the config take effect."""
+        host = np.ascontiguousarray(np.asarray(gain, dtype=np.float64))
+        key = (host.shape, host.tobytes())
+        if getattr(self, "_gain_key", None) != key:
+            self._gain_dev = torch.as_tensor(host).to(self.transition_model.engine.device)
+            self._gain_key = key
+        return self._gain_dev
 
     def compute_mean_lcb_trajectory(self, actions_mpc, obs_mu, obs_var):
         """Reference :229-285: (mean-LCB cost, d cost / d actions_mpc) for ONE optimiser vector; also caches

@@ -401,7 +401,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
 
     # -- a3/a4 -------------------------------------------------------------------------
     def predict_trajectory_batch(self, actions, obs_mu, obs_var, len_horizon=None, current_time_idx=0,
-                                 trajectories=True, stage_costs=True, propagation=None):
+                                 trajectories=True, stage_costs=True, propagation=None, feedback_gains=None):
         """actions (B,H,A) -> dict of DEVICE tensors: J (B,), mu (B,H+1,D), Sig (B,H+1,D,D),
         cost_mu / cost_var (B,H+1).  Costs need set_cost() first.  Differentiable like the reference's predict_trajectory
         followed by get_rewards_trajectory: when grad mode is on and actions, obs_mu or obs_var requires grad, mu, Sig and
@@ -412,14 +412,24 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         the gradient kernels (D <= 8 with A (+ time) <= 6, or 8 < D <= 16) raise GpmpcError(GPMPC_ERR_LIMIT) here, before any
         launch; chain predict_next_state_change to differentiate those.
         `propagation` (None: ModelConfig.uncertainty_propagation): "linearized" runs gpmpc_rollout_linear instead -- the same
-        dict, no autograd (NotImplementedError when grad mode is on and an input requires grad)."""
+        dict, no autograd (NotImplementedError when grad mode is on and an input requires grad).
+        `feedback_gains` (model space; (A, D), (H, A, D) or (B, H, A, D)): the linearised rollout in closed loop under
+        u = actions_t + K_t (x - mu_t) (gpmpc_rollout_linear_feedback) -- Sig and the stage costs are the closed-loop ones, mu
+        is unchanged.  Only with "linearized" (ValueError with moment matching), and without autograd like it."""
         if self._cost_key is None and stage_costs:
             raise RuntimeError("call set_cost(reward_config) before predicting costs")
+        if feedback_gains is not None and self.propagation(propagation) != "linearized":
+            raise ValueError("feedback_gains need propagation='linearized': moment matching has no closed-loop rollout")
         if self.propagation(propagation) == "linearized":
-            _no_linearized_autograd("predict_trajectory", actions, obs_mu, obs_var)
+            _no_linearized_autograd("predict_trajectory", actions, obs_mu, obs_var, feedback_gains)
             actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
             if len_horizon is not None and actions.shape[1] != len_horizon:
                 raise ValueError("actions.shape[1] != len_horizon")
+            if feedback_gains is not None:
+                gains = feedback_gains if isinstance(feedback_gains, torch.Tensor) else np.asarray(feedback_gains)
+                return self.engine.rollout_linear_feedback(actions, torch.as_tensor(gains, dtype=F64), _t(obs_mu).numpy(),
+                                                           _t(obs_var).numpy(), self.config.include_time_model,
+                                                           float(current_time_idx), trajectories, stage_costs)
             return self.engine.rollout_linear(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model,
                                               float(current_time_idx), trajectories, stage_costs)
         grads = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (actions, obs_mu, obs_var))
@@ -456,13 +466,16 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         return self.engine.objective_grad_host(np.asarray(actions, dtype=np.float64), _t(obs_mu).numpy(), _t(obs_var).numpy(),
                                                self.config.include_time_model, float(current_time_idx))
 
-    def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx, propagation=None):
+    def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx, propagation=None,
+                           feedback_gains=None):
         """Same signature / return shapes as the reference (:60-110): ((H+1,D), (H+1,D,D)) CPU tensors.  Differentiable like
         the reference: when grad mode is on and actions, obs_mu or obs_var requires grad, both outputs carry a grad_fn and
         backward() reaches the inputs through gpmpc_rollout_backward (see predict_trajectory_batch); obs_var's gradient is the
-        symmetric part of the reference's.  `propagation`: see predict_trajectory_batch."""
+        symmetric part of the reference's.  `propagation`, `feedback_gains` ((A, D) or (H, A, D)): see
+        predict_trajectory_batch."""
         out = self.predict_trajectory_batch(_t(actions)[None], obs_mu, obs_var, len_horizon, current_time_idx,
-                                            trajectories=True, stage_costs=False, propagation=propagation)
+                                            trajectories=True, stage_costs=False, propagation=propagation,
+                                            feedback_gains=feedback_gains)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()
 
     def predict(self, inputs, include_noise=True):

@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 16; }
+int gpmpc_abi_version(void) { return 17; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -440,6 +440,24 @@ int gpmpc_rollout_linear(gpmpc_t* g, const double* actions, const double* mu0, c
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
     return run_rollout_linear(H_(g), a, (hipStream_t)stream);
+}
+
+int gpmpc_rollout_linear_feedback(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate,
+                                  const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
+                                  double* mu_out, double* Sig_out, double* cm_out, double* cv_out, double* J_out, void* stream) {
+    // without gains the call IS gpmpc_rollout_linear: the same launches, the same bits
+    if (!gains)
+        return gpmpc_rollout_linear(g, actions, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out, cv_out, J_out,
+                                    stream);
+    Range roctx_range("gpmpc_rollout_linear_feedback");
+    if (!g) return GPMPC_ERR_ARG;
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "feedback gains need A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
+    return run_rollout_linear(H_(g), a, (hipStream_t)stream, gains, gains_per_candidate != 0);
 }
 
 int gpmpc_rollout_grad(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,

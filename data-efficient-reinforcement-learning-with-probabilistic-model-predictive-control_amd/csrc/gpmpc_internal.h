@@ -505,7 +505,9 @@ int run_moments(Handle* h, const double* mu, const double* Sig, int P, double* M
 // be NULL; without S_out no matrix product runs), and the horizon rollout built on it (`a` as fill_args leaves it plus the outputs)
 int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                        hipStream_t s);
-int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s);
+// (gains != NULL: in closed loop under the linear feedback u = ubar_t + K_t (x - mu_t), gains (B, H, A, D) when per_candidate, else
+// (H, A, D) shared by the candidates)
+int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const double* gains = nullptr, bool per_candidate = false);
 // moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
 int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                          const double* Vb, double* mb_out, double* vb_out, hipStream_t s);

@@ -23,6 +23,9 @@
 //   rollout_linear_step_kernel    then one wavefront per candidate adds the blocks, advances (mu, Sigma) in the stored trajectory
 //                                   mu' = mu + M,  T = Sigma V_s,  Sigma' = Sigma + (V_s^T Sigma V_s + diag v) + T + T^T
 //                                 (V_s: the state rows of V) and writes the next step's model inputs [mu' | action | time0 + t + 1].
+//   rollout_linear_feedback_step_kernel /   the closed-loop rollout (gpmpc_rollout_linear_feedback): the same init kernel and tile
+//   traj_cost_feedback_kernel     launches; the step uses C = V_s + K_t^T V_u in place of V_s, the cost kernel the state-action
+//                                 covariance [I ; K_t] Sigma_t [I ; K_t]^T in place of block_diag(Sigma_t, 0).
 // Every sum runs in an order fixed by N, E and D alone (k steps, lanes, waves, slices, column blocks): a point's bits do not depend
 // on the batch size, on its place in the batch, on its neighbours or on the chunks.  Plain kernels: no atomics, no waits between
 // workgroups.  The workspace (Handle::linws) is this file's own, sized by plan_moments_linear (moments_linear_plan.h); a chunk of
@@ -383,6 +386,185 @@ __global__ __launch_bounds__(64) void rollout_linear_step_kernel(LinStepArgs p) 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Closed-loop form (gpmpc_rollout_linear_feedback): the policy u = ubar_t + K_t (x - mu_t) makes the model input's covariance
+// G Sigma_t G^T with G = [I ; K_t ; 0], so the step's D x D Jacobian is C = G^T V = V_s + K_t^T V_u (V_u: the action rows of V).
+struct LinFbStepArgs {
+    const double* part;
+    const double* ils2;      // (D, E)
+    const double* var;       // (D)
+    const double* actions;   // (rows, H, A) of this chunk
+    const double* gains;     // (H, A, D) of the chunk's first candidate
+    long long gain_stride;   // doubles between two candidates' gains (0: one gain sequence shared by all)
+    double* mu;              // (rows, H + 1, D) of this chunk
+    double* Sig;             // (rows, H + 1, D, D) of this chunk
+    double* Xq;              // (Mc, E) model inputs of the next tile launch
+    int rows, E, D, A, H, nCB, NW, t, include_time;
+    long long Mc;
+    double time0;
+};
+
+// One wavefront per candidate: rollout_linear_step_kernel with C in place of V_s.  The mean takes the same operations as there
+// (its bits do not depend on the gains).
+__global__ __launch_bounds__(64) void rollout_linear_feedback_step_kernel(LinFbStepArgs p) {
+    __shared__ double s_sum[kMaxD][kMaxE + 2];       // sum P k | sum k beta | the Jacobian sums of the state and action inputs
+    __shared__ double s_V[kMaxE][kMaxD];             // V [state or action input][output]
+    __shared__ double s_K[kMaxE][kMaxD];             // K_t [action][state]
+    __shared__ double s_C[kMaxD][kMaxD];             // C = V_s + K_t^T V_u
+    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
+    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t C
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, DA = D + A, NS = DA + 2;
+    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
+    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
+    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
+    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
+    const double* K = p.gains + (size_t)b * (size_t)p.gain_stride + (size_t)t * A * D;
+    for (int idx = tid; idx < D * NS; idx += 64) {
+        const int a = idx / NS, which = idx - a * NS;
+        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
+    }
+    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
+    for (int idx = tid; idx < A * D; idx += 64) s_K[idx / D][idx % D] = K[idx];
+    __syncthreads();
+    for (int idx = tid; idx < DA * D; idx += 64) {
+        const int i = idx / D, a = idx - i * D;
+        s_V[i][a] = p.ils2[a * E + i] * s_sum[a][2 + i];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // C = V_s + K^T V_u, the actions in order
+        const int i = idx / D, c = idx - i * D;
+        double v = 0.0;
+        for (int u = 0; u < A; ++u) v = fma(s_K[u][i], s_V[D + u][c], v);
+        s_C[i][c] = s_V[i][c] + v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t C
+        const int i = idx / D, c = idx - i * D;
+        double v = 0.0;
+        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_C[k][c], v);
+        s_T[i][c] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
+        const int a = idx / D, c = idx - a * D;
+        if (a > c) continue;
+        double q = 0.0;
+        for (int i = 0; i < D; ++i) q = fma(s_C[i][a], s_T[i][c], q);
+        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
+        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
+        Sg_n[a * D + c] = v;
+        Sg_n[c * D + a] = v;
+    }
+    const bool more = t + 1 < H;
+    double* xq = p.Xq + (size_t)b * E;
+    if (tid < D) {
+        const double v = mu_t[tid] + s_sum[tid][1];
+        mu_n[tid] = v;
+        if (more) xq[tid] = v;
+    }
+    if (more) {
+        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
+        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
+    }
+}
+
+// Stage / terminal costs and the objective of the closed-loop trajectory: traj_cost_body (one wavefront per candidate, lanes over
+// the H + 1 steps, wave_xor_sum for J) with the state-action covariance Sigma_z = G Sigma_t G^T, G = [I ; K_t], in place of
+// block_diag(Sigma_t, 0).  Sigma_z enters the quadratic cost only through
+//   tr(Sigma_z W) = tr(Sigma_t Wg),  tr(2 (W Sigma_z)^2) = tr(2 (Wg Sigma_t)^2),  e^T W Sigma_z W e = (G^T W^T e)^T Sigma_t (G^T W e)
+// with Wg = G^T W G, so a lane keeps D^2 + 2 D values (DP: the array bound) instead of (D + A)^2.  Terminal step: G = I, W = W_T.
+template <int DP>
+__global__ __launch_bounds__(64) void traj_cost_feedback_kernel(const double* __restrict__ mu, const double* __restrict__ Sig,
+                                                                const double* __restrict__ actions,
+                                                                const double* __restrict__ gains, long long gain_stride,
+                                                                const double* __restrict__ cost, int D, int A, int H,
+                                                                double kappa, int clip, int use_constraints,
+                                                                double* __restrict__ cm_out, double* __restrict__ cv_out,
+                                                                double* __restrict__ J_out) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    const int DA = D + A;
+    const double* target = cost;
+    const double* W = cost + DA;
+    const double* WT = W + DA * DA;
+    const double* smin = WT + D * D;
+    const double* smax = smin + D;
+    double jsum = 0.0;
+    for (int t = lane; t <= H; t += 64) {
+        const bool terminal = (t == H);
+        const int n = terminal ? D : DA, Au = terminal ? 0 : A;
+        const double* Wm = terminal ? WT : W;
+        const double* m = mu + ((size_t)c * (H + 1) + t) * D;
+        const double* S = Sig + ((size_t)c * (H + 1) + t) * D * D;
+        const double* a = actions + ((size_t)c * H + (terminal ? 0 : t)) * A;
+        const double* K = gains + (size_t)c * (size_t)gain_stride + (size_t)(terminal ? 0 : t) * A * D;      // [action][state]
+        auto err = [&](int i) { return (i < D ? m[i] : a[i - D]) - target[i]; };
+        double Wg[DP * DP], p1[DP], p2[DP];
+        for (int i = 0; i < D; ++i) {
+            for (int j = 0; j < D; ++j) {
+                double w = Wm[i * n + j];
+                for (int u = 0; u < Au; ++u) {
+                    w = fma(Wm[i * n + D + u], K[u * D + j], w);
+                    w = fma(K[u * D + i], Wm[(D + u) * n + j], w);
+                    double kw = 0.0;
+                    for (int v = 0; v < Au; ++v) kw = fma(Wm[(D + u) * n + D + v], K[v * D + j], kw);
+                    w = fma(K[u * D + i], kw, w);
+                }
+                Wg[i * DP + j] = w;
+            }
+            double v1 = 0.0, v2 = 0.0;                           // (G^T W^T e)_i, (G^T W e)_i
+            for (int k = 0; k < n; ++k) {
+                v1 = fma(err(k), Wm[k * n + i], v1);
+                v2 = fma(Wm[i * n + k], err(k), v2);
+            }
+            for (int u = 0; u < Au; ++u) {
+                double r1 = 0.0, r2 = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    r1 = fma(err(k), Wm[k * n + D + u], r1);
+                    r2 = fma(Wm[(D + u) * n + k], err(k), r2);
+                }
+                v1 = fma(K[u * D + i], r1, v1);
+                v2 = fma(K[u * D + i], r2, v2);
+            }
+            p1[i] = v1;
+            p2[i] = v2;
+        }
+        double cm = 0.0, cv = 0.0;
+        // tr(Sigma Wg) and e^T W e
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) cm = fma(S[i * D + j], Wg[j * DP + i], cm);
+        for (int i = 0; i < n; ++i) {
+            const double ei = err(i);
+            for (int j = 0; j < n; ++j) cm = fma(ei * Wm[i * n + j], err(j), cm);
+        }
+        // tr(2 TS TS) with TS = Wg Sigma, 4 p1^T Sigma p2
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) {
+                double tij = 0.0, tji = 0.0;
+                for (int k = 0; k < D; ++k) {
+                    tij = fma(Wg[i * DP + k], S[k * D + j], tij);
+                    tji = fma(Wg[j * DP + k], S[k * D + i], tji);
+                }
+                cv = fma(2.0 * tij, tji, cv);
+                cv = fma(4.0 * p1[i] * S[i * D + j], p2[j], cv);
+            }
+        if (use_constraints && !terminal) {                      // state marginals only, as traj_cost_body
+            for (int d = 0; d < D; ++d) {
+                const double sg = S[d * D + d];
+                cm += 0.5 * (1.0 + erf((smin[d] - m[d]) / (sg * 1.4142135623730951)))
+                    + (1.0 - 0.5 * (1.0 + erf((smax[d] - m[d]) / (sg * 1.4142135623730951))));
+            }
+        }
+        double ucb = -cm + kappa * sqrt(cv);
+        if (clip) ucb = fmin(ucb, 0.0);
+        jsum -= ucb;
+        if (cm_out) cm_out[(size_t)c * (H + 1) + t] = cm;
+        if (cv_out) cv_out[(size_t)c * (H + 1) + t] = cv;
+    }
+    jsum = wave_xor_sum(jsum);
+    if (lane == 0 && J_out) J_out[c] = jsum / (double)(H + 1);
+}
+
 template <int EP>
 void launch_lin_tiles_ep(const LinTileArgs& p, bool var, hipStream_t s) {
     const dim3 grid((p.rows + kBM - 1) / kBM, p.nCB, p.D);
@@ -430,8 +612,11 @@ int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, do
     return GPMPC_OK;
 }
 
-// a: filled by the entry point (model, cost settings, actions, shape, initial state, outputs -- each output may be NULL)
-int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s) {
+// a: filled by the entry point (model, cost settings, actions, shape, initial state, outputs -- each output may be NULL).
+// gains != NULL: the closed-loop rollout under u = ubar_t + K_t (x - mu_t), gains (B, H, A, D) when per_candidate, else (H, A, D)
+// shared by all candidates -- the same plan, workspace, init kernel and tile launches with the step and cost kernels exchanged; a
+// chunk of candidates offsets the gain pointer only when the gains are per candidate.
+int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const double* gains, bool per_candidate) {
     const int N = a.N, D = a.D, E = a.E, A = a.A, H = a.H, B = a.B;
     const bool own_traj = !a.mu_out || !a.Sig_out;
     const bool costs = a.cm_out || a.cv_out || a.J_out;
@@ -453,21 +638,43 @@ int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s) {
     q.include_time = a.include_time; q.time0 = a.time0;
     for (int d = 0; d < D; ++d) q.mu0[d] = a.mu0[d];
     for (int d = 0; d < D * D; ++d) q.S0[d] = a.S0[d];
+    LinFbStepArgs f{};
+    f.part = p.part; f.ils2 = p.ils2; f.var = p.var;
+    f.Xq = q.Xq;
+    f.E = E; f.D = D; f.A = A; f.H = H; f.nCB = pl.nCB; f.NW = pl.NW; f.Mc = pl.Mc;
+    f.include_time = a.include_time; f.time0 = a.time0;
+    f.gain_stride = per_candidate ? (long long)H * A * D : 0;
     for (long long b0 = 0; b0 < B; b0 += pl.chunk) {
         const int rows = (int)((B - b0) < pl.chunk ? (B - b0) : pl.chunk);
-        p.rows = rows; q.rows = rows;
+        p.rows = rows; q.rows = rows; f.rows = rows;
         q.actions = a.actions + (size_t)b0 * H * A;
         q.mu = a.mu_out ? a.mu_out + (size_t)b0 * (H + 1) * D : own_mu;
         q.Sig = a.Sig_out ? a.Sig_out + (size_t)b0 * (H + 1) * D * D : own_Sig;
         q.t = 0;
+        f.actions = q.actions; f.mu = q.mu; f.Sig = q.Sig;
+        f.gains = gains ? gains + (size_t)b0 * (size_t)f.gain_stride : nullptr;
         hipLaunchKernelGGL(rollout_linear_init_kernel, dim3(rows), dim3(64), 0, s, q);
         for (int t = 0; t < H; ++t) {
             launch_lin_tiles(p, true, s);
-            q.t = t;
-            hipLaunchKernelGGL(rollout_linear_step_kernel, dim3(rows), dim3(64), 0, s, q);
+            q.t = t; f.t = t;
+            if (gains) hipLaunchKernelGGL(rollout_linear_feedback_step_kernel, dim3(rows), dim3(64), 0, s, f);
+            else hipLaunchKernelGGL(rollout_linear_step_kernel, dim3(rows), dim3(64), 0, s, q);
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());
-        if (costs) {                                  // stage costs + objective of the chunk's stored trajectory
+        if (costs && gains) {                         // closed-loop stage costs + objective of the chunk's stored trajectory
+            double* cm = a.cm_out ? a.cm_out + (size_t)b0 * (H + 1) : nullptr;
+            double* cv = a.cv_out ? a.cv_out + (size_t)b0 * (H + 1) : nullptr;
+            double* J = a.J_out ? a.J_out + b0 : nullptr;
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(rows), dim3(64), 0, s, (const double*)f.mu, (const double*)f.Sig, f.actions,
+                                   f.gains, f.gain_stride, a.cost, D, A, H, a.kappa, a.clip, a.use_constraints, cm, cv, J);
+            };
+            static_assert(kMaxD <= 16, "traj_cost_feedback_kernel: per-lane arrays");
+            if (D <= 4) launch(traj_cost_feedback_kernel<4>);
+            else if (D <= 8) launch(traj_cost_feedback_kernel<8>);
+            else launch(traj_cost_feedback_kernel<16>);
+            GPMPC_HIP_CHECK(h, hipGetLastError());
+        } else if (costs) {                           // stage costs + objective of the chunk's stored trajectory
             RolloutArgs c = a;
             c.B = rows;
             c.actions = q.actions;

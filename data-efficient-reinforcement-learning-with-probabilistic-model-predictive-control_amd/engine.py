@@ -19,6 +19,21 @@ def _hp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def feedback_gains_layout(shape, B, H, A, D):
+    """How a feedback-gain array of `shape` reaches gpmpc_rollout_linear_feedback: (per_candidate, every_step).  (A, D) is one
+    gain for every step (every_step: broadcast over H, passed as shared), (H, A, D) a shared sequence, (B, H, A, D) one sequence
+    per candidate; anything else raises ValueError."""
+    shape = tuple(int(s) for s in shape)
+    if shape == (A, D):
+        return False, True
+    if shape == (H, A, D):
+        return False, False
+    if shape == (B, H, A, D):
+        return True, False
+    raise ValueError(f"feedback gains must have shape (A, D) = {(A, D)}, (H, A, D) = {(H, A, D)} or (B, H, A, D) = "
+                     f"{(B, H, A, D)}, got {shape}")
+
+
 class _HostEvaluationPlan:
     """Per (H, A): staging arrays of gpmpc_objective_grad_host's inputs, the layout of its result buffer and a view of it."""
 
@@ -413,6 +428,46 @@ class HipEngine:
                                                   int(bool(include_time)), float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"),
                                                   ptr("cost_var"), ptr("J"), self._stream()))
         self._keep_rollout_linear = actions      # alive until the asynchronous call has read it
+        return out
+
+    def rollout_linear_feedback(self, actions, gains, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True,
+                                out=None):
+        """`rollout_linear` in closed loop (gpmpc_rollout_linear_feedback): the policy is u = actions_t + K_t (x - mu_t), and
+        Sig and the stage costs are those of that policy; mu is `rollout_linear`'s.  `gains` (model space): (A, D) one gain for
+        every step and candidate, (H, A, D) one sequence shared by the candidates, or (B, H, A, D); None: `rollout_linear`.
+        The same dict.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        per_candidate = False
+        if gains is not None:
+            gains = torch.as_tensor(gains, dtype=torch.float64)
+            per_candidate, every_step = feedback_gains_layout(gains.shape, B, H, A, D)
+            if every_step:
+                gains = gains.expand(H, A, D)
+            gains = self._dev(gains)
+        if out is None:
+            out = {}
+            if stage_costs or self._cost == (D, A):
+                out["J"] = torch.empty(B, dtype=torch.float64, device=self.device)
+            if trajectories:
+                out["mu"] = torch.empty((B, H + 1, D), dtype=torch.float64, device=self.device)
+                out["Sig"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
+            if stage_costs:
+                out["cost_mu"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
+                out["cost_var"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
+        elif ("J" in out and out["J"].shape != (B,)) or ("mu" in out and out["mu"].shape != (B, H + 1, D)):
+            raise ValueError("`out` does not match the batch shape")
+
+        def ptr(k):
+            return out[k].data_ptr() if k in out else None
+        self._check(self.lib.gpmpc_rollout_linear_feedback(
+            self._h, actions.data_ptr(), gains.data_ptr() if gains is not None else None, int(per_candidate), _hp(mu0), _hp(S0),
+            B, H, A, int(bool(include_time)), float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"), ptr("cost_var"), ptr("J"),
+            self._stream()))
+        self._keep_rollout_linear_feedback = (actions, gains)      # alive until the asynchronous call has read them
         return out
 
     def rollout_grad(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=False):

@@ -313,6 +313,33 @@ int gpmpc_rollout_linear(gpmpc_t* h, const double* actions_dev, const double* mu
                          double* cost_var_out_dev, double* J_out_dev, void* stream);
 
 /*
+ * gpmpc_rollout_linear_feedback: gpmpc_rollout_linear in closed loop, under the ancillary linear feedback of cautious GP-MPC
+ *   u = ubar_t + K_t (x - mu_t),  x ~ N(mu_t, Sigma_t),  ubar = actions_dev,  K_t (A, D) in model space.
+ * gains_dev is (B,H,A,D) when gains_per_candidate != 0, else (H,A,D) shared by all candidates.  The gains never move the mean:
+ * the model input mean of step t is [mu_t | ubar_t | time0 + t], and mu_out is bit for bit gpmpc_rollout_linear's for the same
+ * actions, whatever the gains are.  The model input covariance is G_t Sigma_t G_t^T with G_t = [I_D ; K_t ; 0] (E x D, the time
+ * row zero); with M, V, v of gpmpc_moments_linear at that mean, V_s / V_u the state / action rows of V,
+ *   C_t = G_t^T V = V_s + K_t^T V_u,   T = Sigma_t C_t,
+ *   mu_{t+1} = mu_t + M,   Sigma_{t+1} = Sigma_t + (C_t^T Sigma_t C_t + diag v) + T + T^T
+ * computed for a <= b and mirrored: Sigma_t (t >= 1) is exactly symmetric.  Stage costs (t < H): the quadratic cost with the full
+ * state-action covariance Sigma_z = [I ; K_t] Sigma_t [I ; K_t]^T in place of block_diag(Sigma_t, 0),
+ *   cost_mu = tr(Sigma_z W) + e^T W e,   cost_var = tr(2 (W Sigma_z)^2) + 4 e^T W Sigma_z W e,   e = [mu_t | ubar_t] - target;
+ * the constraint term (state marginals only), the terminal cost, kappa, clipping and J are those of gpmpc_rollout_linear.
+ * NOT modelled: the realised action u is not clipped to [0, 1] -- this is a linearisation, and the covariance it propagates is
+ * that of the unclipped policy.
+ * gains_dev == NULL: the call IS gpmpc_rollout_linear (every output has the same bits).  Outputs, their nullability, the cost
+ * rules and the asynchrony are gpmpc_rollout_linear's; so are the workspace (its own, within 16 MB or one 64-row tile's need; no
+ * other workspace and no gpmpc_last_* state is touched) and the option "moments_linear_chunk_points".  A candidate's results
+ * are bitwise the same alone and at any position of any batch, whatever the chunk size is, and whether its gains arrive shared
+ * or per candidate.  Every sum runs in an order fixed by N, E, D and A alone; no atomics.  Errors: those of
+ * gpmpc_rollout_linear, plus GPMPC_ERR_ARG for a non-NULL gains_dev with A < 1.
+ */
+int gpmpc_rollout_linear_feedback(gpmpc_t* h, const double* actions_dev, const double* gains_dev, int gains_per_candidate,
+                                  const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time,
+                                  double time0, double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev,
+                                  double* cost_var_out_dev, double* J_out_dev, void* stream);
+
+/*
  * Objective AND analytic gradient: J_out_dev (B), grad_out_dev (B,H,A) = dJ/d(actions) -- what the reference obtains with
  * `mean_cost.backward()` (gp_mpc_controller.py:277) and hands to scipy as `jac` (:132-139, :285): forward rollout, pairwise
  * moment pass over the stored trajectory, reverse sweep.  clip_lower_bound_cost_to_0 clips the value only (pass-through clamp).

@@ -53,7 +53,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 17; }
+int gpmpc_abi_version(void) { return 18; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -507,6 +507,31 @@ int gpmpc_rollout_linear_backward(gpmpc_t* g, const double* actions, const doubl
     if (A < 1) return bad(g, "gradient needs A >= 1");
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     return run_rollout_linear_backward(H_(g), a, sd, actions_bar_out, (hipStream_t)stream);
+}
+
+int gpmpc_rollout_linear_feedback_backward(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate,
+                                           const double* mu0, const double* S0, int B, int H, int A, int include_time,
+                                           double time0, const double* mu_bar, const double* Sig_bar, const double* cm_bar,
+                                           const double* cv_bar, const double* J_bar, double* actions_bar_out,
+                                           double* gains_bar_out, double* mu0_bar_out, double* S0_bar_out, void* stream) {
+    if (!gains) {
+        if (!g) return GPMPC_ERR_ARG;
+        if (gains_bar_out) return bad(g, "gains_bar_out without gains");
+        // without gains the call IS gpmpc_rollout_linear_backward: the same launches, the same bits
+        return gpmpc_rollout_linear_backward(g, actions, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar, cm_bar, cv_bar,
+                                             J_bar, actions_bar_out, mu0_bar_out, S0_bar_out, stream);
+    }
+    Range roctx_range("gpmpc_rollout_linear_feedback_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!actions_bar_out) return bad(g, "null argument");
+    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "gradient needs A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_rollout_linear_feedback_backward(H_(g), a, sd, gains, gains_per_candidate != 0, actions_bar_out, gains_bar_out,
+                                                (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

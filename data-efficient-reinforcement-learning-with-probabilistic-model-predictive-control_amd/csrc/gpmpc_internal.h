@@ -211,7 +211,7 @@ struct Handle {
     Buf momws;    // gpmpc_moments: per-point setup results (C_a^-1, Q_ab, log dets) | per-(point, pair, tile) partial sums of one chunk
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
-    Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
+    Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward / gpmpc_rollout_linear_feedback_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -508,6 +508,11 @@ int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, do
 // (gains != NULL: in closed loop under the linear feedback u = ubar_t + K_t (x - mu_t), gains (B, H, A, D) when per_candidate, else
 // (H, A, D) shared by the candidates)
 int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const double* gains = nullptr, bool per_candidate = false);
+// ... the closed-loop stage costs and objective (traj_cost_feedback_kernel) of `rows` stored trajectories mu (rows, H + 1, D),
+// Sig (rows, H + 1, D, D): gains of the first of them, gain_stride doubles between two candidates' gains (0: shared); cost
+// settings of `a`; each output may be NULL
+int launch_traj_cost_feedback(Handle* h, const RolloutArgs& a, int rows, const double* mu, const double* Sig, const double* actions,
+                              const double* gains, long long gain_stride, double* cm, double* cv, double* J, hipStream_t s);
 // moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
 int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                          const double* Vb, double* mb_out, double* vb_out, hipStream_t s);
@@ -516,6 +521,10 @@ int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, 
 int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                                 const double* Vb, double* mb_out, double* vb_out, hipStream_t s);
 int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, double* actions_bar, hipStream_t s);
+// ... and of the closed-loop run_rollout_linear (gains as there, not NULL) wrt the actions, the gains (gains_bar (B, H, A, D) per
+// candidate, or NULL) and the initial state
+int run_rollout_linear_feedback_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, const double* gains,
+                                         bool per_candidate, double* actions_bar, double* gains_bar, hipStream_t s);
 // search.hip: cross-entropy search whose loop stays on the device (actions / J_out of `a` are set inside)
 int run_cem_search(Handle* h, RolloutArgs& a, int iterations, int n_elite, unsigned long long seed, const double* first_host,
                    int mapper, const double* max_change_host, const double* a_prev_host, const double* noise_dev,

@@ -581,6 +581,21 @@ void launch_lin_tiles(const LinTileArgs& p, bool var, hipStream_t s) {
 
 }  // namespace
 
+int launch_traj_cost_feedback(Handle* h, const RolloutArgs& a, int rows, const double* mu, const double* Sig, const double* actions,
+                              const double* gains, long long gain_stride, double* cm, double* cv, double* J, hipStream_t s) {
+    const int D = a.D, A = a.A, H = a.H;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(rows), dim3(64), 0, s, mu, Sig, actions, gains, gain_stride, a.cost, D, A, H, a.kappa,
+                           a.clip, a.use_constraints, cm, cv, J);
+    };
+    static_assert(kMaxD <= 16, "traj_cost_feedback_kernel: per-lane arrays");
+    if (D <= 4) launch(traj_cost_feedback_kernel<4>);
+    else if (D <= 8) launch(traj_cost_feedback_kernel<8>);
+    else launch(traj_cost_feedback_kernel<16>);
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    return GPMPC_OK;
+}
+
 int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, double* M_out, double* S_out, double* V_out,
                        hipStream_t s) {
     const int N = h->N, D = h->D, E = h->E;
@@ -665,15 +680,8 @@ int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const dou
             double* cm = a.cm_out ? a.cm_out + (size_t)b0 * (H + 1) : nullptr;
             double* cv = a.cv_out ? a.cv_out + (size_t)b0 * (H + 1) : nullptr;
             double* J = a.J_out ? a.J_out + b0 : nullptr;
-            auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(rows), dim3(64), 0, s, (const double*)f.mu, (const double*)f.Sig, f.actions,
-                                   f.gains, f.gain_stride, a.cost, D, A, H, a.kappa, a.clip, a.use_constraints, cm, cv, J);
-            };
-            static_assert(kMaxD <= 16, "traj_cost_feedback_kernel: per-lane arrays");
-            if (D <= 4) launch(traj_cost_feedback_kernel<4>);
-            else if (D <= 8) launch(traj_cost_feedback_kernel<8>);
-            else launch(traj_cost_feedback_kernel<16>);
-            GPMPC_HIP_CHECK(h, hipGetLastError());
+            rc = launch_traj_cost_feedback(h, a, rows, f.mu, f.Sig, f.actions, f.gains, f.gain_stride, cm, cv, J, s);
+            if (rc) return rc;
         } else if (costs) {                           // stage costs + objective of the chunk's stored trajectory
             RolloutArgs c = a;
             c.B = rows;

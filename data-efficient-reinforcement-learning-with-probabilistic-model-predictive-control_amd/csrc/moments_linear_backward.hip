@@ -1,5 +1,5 @@
-// moments_linear_backward.hip -- reverse-mode products of the linearised propagation: gpmpc_moments_linear_backward (one step) and
-// gpmpc_rollout_linear_backward (a trajectory with its costs).  Per point, with d_je = x_je - m_e (formed per element, as the
+// moments_linear_backward.hip -- reverse-mode products of the linearised propagation: gpmpc_moments_linear_backward (one step),
+// gpmpc_rollout_linear_backward (a trajectory with its costs) and gpmpc_rollout_linear_feedback_backward (the same in closed loop).  Per point, with d_je = x_je - m_e (formed per element, as the
 // forward does), r_aje = d_je / l_ae^2, k_aj as in the forward and q_a = iK_a k_a (a row of K* iK; iK taken as symmetric):
 //   var_bar = sym(V S_bar V^T)
 //   W = V_bar + Sigma V (S_bar + S_bar^T)                      (E x D)
@@ -26,9 +26,18 @@
 //                             partials by cost_adjoint_wave, W = 2 Sigma_t A_t Lambda on the state rows, the coefficients,
 //                             Lambda_t = sym(seeds) + A_t Lambda A_t^T, the model inputs), then one reverse tile launch over the
 //                             chunk: H + 1 small launches and H tile launches.
-// Every sum runs in an order fixed by N, E and D alone; a point's or candidate's bits do not depend on the batch, on its place in
+//   closed loop (FB)          u = ubar_t + K_t (x - mu_t): C_t = V_s + K_t^T V_u takes the place of V_s (A_t = I + C_t).  The forward
+//                             is recomputed by rollout_linear_fb_bwd_forward_kernel (the arithmetic of
+//                             rollout_linear_feedback_step_kernel) and keeps the D + A state and action rows of V; the cost
+//                             variances come from the closed-loop cost kernel (launch_traj_cost_feedback).  The reverse kernel's
+//                             FB instantiation loads K_t, takes the cost partials from cost_adjoint_feedback_wave, fills the
+//                             action rows of W with K_t C_bar (C_bar = 2 Sigma_t A_t Lambda) and writes gains_bar_t = (cost
+//                             partial) + V_u C_bar^T when it opens step t.  The tile kernels and their launches are shared.
+// Every sum runs in an order fixed by N, E, D and A alone; a point's or candidate's bits do not depend on the batch, on its place in
 // it or on the chunks.  Plain kernels: no atomics, no waits between workgroups.  The workspace (Handle::linbws) is this file's
 // own, laid out by plan_moments_linear_backward (moments_linear_backward_plan.h).
+#include <type_traits>
+
 #include "grad_kernels.h"
 #include "moments_linear_backward_plan.h"
 
@@ -94,6 +103,13 @@ struct LbRollArgs {
     double time0, kappa;
     double mu0[kMaxD];       // read by the init kernel
     double S0[kMaxD * kMaxD];
+};
+
+// The closed-loop kernels' block: the open-loop kernels keep theirs.
+struct LbFbArgs : LbRollArgs {
+    const double* gains;     // (H, A, D) of the chunk's first candidate
+    long long gain_stride;   // doubles between two candidates' gains (0: one gain sequence shared by all)
+    double* gains_bar;       // (rows, H, A, D) of this chunk, or NULL (not written)
 };
 
 template <int EP>
@@ -466,19 +482,216 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_forward_kernel(LbRollAr
     }
 }
 
+// One wavefront per candidate, closed loop: step t -> t + 1 of the recomputed trajectory with the arithmetic of
+// rollout_linear_feedback_step_kernel (the same operations in the same order: the trajectory has the forward entry's bits), the
+// step's M and the D + A state and action rows of V kept for the reverse sweep, and the model inputs of step t + 1.
+__global__ __launch_bounds__(64) void rollout_linear_fb_bwd_forward_kernel(LbFbArgs p) {
+    __shared__ double s_sum[kMaxD][kMaxE + 2];       // sum P k | sum k beta | the Jacobian sums of the state and action inputs
+    __shared__ double s_V[kMaxE][kMaxD];             // V [state or action input][output]
+    __shared__ double s_K[kMaxE][kMaxD];             // K_t [action][state]
+    __shared__ double s_C[kMaxD][kMaxD];             // C = V_s + K_t^T V_u
+    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
+    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t C
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, DA = D + A, NS = DA + 2;
+    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
+    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
+    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
+    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
+    double* keepM = p.stepM + ((size_t)b * H + t) * D;
+    double* keepV = p.stepV + ((size_t)b * H + t) * DA * D;
+    const double* K = p.gains + (size_t)b * (size_t)p.gain_stride + (size_t)t * A * D;
+    for (int idx = tid; idx < D * NS; idx += 64) {
+        const int a = idx / NS, which = idx - a * NS;
+        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
+    }
+    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
+    for (int idx = tid; idx < A * D; idx += 64) s_K[idx / D][idx % D] = K[idx];
+    __syncthreads();
+    for (int idx = tid; idx < DA * D; idx += 64) {
+        const int i = idx / D, a = idx - i * D;
+        const double v = p.ils2[a * E + i] * s_sum[a][2 + i];
+        s_V[i][a] = v;
+        keepV[idx] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // C = V_s + K^T V_u, the actions in order
+        const int i = idx / D, c = idx - i * D;
+        double v = 0.0;
+        for (int u = 0; u < A; ++u) v = fma(s_K[u][i], s_V[D + u][c], v);
+        s_C[i][c] = s_V[i][c] + v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t C
+        const int i = idx / D, c = idx - i * D;
+        double v = 0.0;
+        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_C[k][c], v);
+        s_T[i][c] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
+        const int a = idx / D, c = idx - a * D;
+        if (a > c) continue;
+        double q = 0.0;
+        for (int i = 0; i < D; ++i) q = fma(s_C[i][a], s_T[i][c], q);
+        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
+        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
+        Sg_n[a * D + c] = v;
+        Sg_n[c * D + a] = v;
+    }
+    const bool more = t + 1 < H;
+    double* xq = p.Xq + (size_t)b * E;
+    if (tid < D) {
+        const double v = mu_t[tid] + s_sum[tid][1];
+        keepM[tid] = s_sum[tid][1];
+        mu_n[tid] = v;
+        if (more) xq[tid] = v;
+    }
+    if (more) {
+        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
+        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
+    }
+}
+
+// Closed-loop form of cost_adjoint_wave for a stage t < H: the quadratic cost sees Sigma_z = G Sigma_t G^T with G = [I ; K]
+// (K (A, D) row-major), so besides (mu, Sigma, u) there is a partial wrt K.  With Q = W Sigma_z W (W not assumed symmetric):
+//   Sz_bar = wm W^T + 4 wv (Q^T + (W^T e)(W e)^T),   e_bar = wm (W + W^T) e + 4 wv (Q + Q^T) e
+//   gSig = G^T Sz_bar G,   gK = action rows of (Sz_bar + Sz_bar^T) G Sigma_t,   gmu = e_bar[:D],   gu = e_bar[D:]
+// and the constraint term of cost_adjoint_wave (state marginals only: no partial wrt K).  One wavefront; `tmp` is its scratch,
+// cost_adjoint_feedback_tmp(D, A) doubles.
+__host__ __device__ constexpr int cost_adjoint_feedback_tmp(int D, int A) { return (D + A) * D + 3 * (D + A) * (D + A) + 3 * (D + A); }
+
+__device__ inline void cost_adjoint_feedback_wave(int lane, int D, int A, const double* mu, const double* Sg, const double* act,
+                                                  const double* K, const double* target, const double* Wm, const double* smin,
+                                                  const double* smax, bool use_constraints, double wm, double wv, double* tmp,
+                                                  double* gmu, double* gSig, double* gu, double* gK) {
+    const int n = D + A;
+    double* GS = tmp;            // G Sigma_t  (n x D)
+    double* Sz = GS + n * D;     // Sigma_z  (n x n); then Sz_bar
+    double* WS = Sz + n * n;     // W Sigma_z  (n x n); then Sz_bar G  (n x D)
+    double* Q = WS + n * n;      // W Sigma_z W
+    double* err = Q + n * n;
+    double* We = err + n;
+    double* WTe = We + n;
+    for (int i = lane; i < n; i += 64) err[i] = (i < D ? mu[i] : act[i - D]) - target[i];
+    for (int idx = lane; idx < n * D; idx += 64) {
+        const int i = idx / D, j = idx - i * D;
+        double v;
+        if (i < D) {
+            v = Sg[i * D + j];
+        } else {
+            v = 0.0;
+            for (int k = 0; k < D; ++k) v = fma(K[(i - D) * D + k], Sg[k * D + j], v);
+        }
+        GS[idx] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < n * n; idx += 64) {               // Sigma_z = (G Sigma_t) G^T
+        const int i = idx / n, j = idx - i * n;
+        double v;
+        if (j < D) {
+            v = GS[i * D + j];
+        } else {
+            v = 0.0;
+            for (int k = 0; k < D; ++k) v = fma(GS[i * D + k], K[(j - D) * D + k], v);
+        }
+        Sz[idx] = v;
+    }
+    for (int i = lane; i < n; i += 64) {
+        double a = 0.0, b = 0.0;
+        for (int k = 0; k < n; ++k) { a = fma(Wm[i * n + k], err[k], a); b = fma(Wm[k * n + i], err[k], b); }
+        We[i] = a; WTe[i] = b;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < n * n; idx += 64) {
+        const int i = idx / n, j = idx - i * n;
+        double v = 0.0;
+        for (int k = 0; k < n; ++k) v = fma(Wm[i * n + k], Sz[k * n + j], v);
+        WS[idx] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < n * n; idx += 64) {
+        const int i = idx / n, j = idx - i * n;
+        double v = 0.0;
+        for (int k = 0; k < n; ++k) v = fma(WS[i * n + k], Wm[k * n + j], v);
+        Q[idx] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < n * n; idx += 64) {               // Sz_bar (over Sigma_z)
+        const int i = idx / n, j = idx - i * n;
+        Sz[idx] = wm * Wm[j * n + i] + wv * 4.0 * (Q[j * n + i] + WTe[i] * We[j]);
+    }
+    for (int i = lane; i < n; i += 64) {
+        double v = 0.0;
+        for (int k = 0; k < n; ++k) v = fma(Q[i * n + k] + Q[k * n + i], err[k], v);
+        v = wm * (We[i] + WTe[i]) + wv * 4.0 * v;
+        if (i < D) {
+            if (use_constraints) {
+                const double sq = Sg[i * D + i];
+                const double zmin = (smin[i] - mu[i]) / sq, zmax = (smax[i] - mu[i]) / sq;
+                v += wm * (-exp(-0.5 * zmin * zmin) + exp(-0.5 * zmax * zmax)) * 0.3989422804014327 / sq;
+            }
+            gmu[i] = v;
+        } else {
+            gu[i - D] = v;
+        }
+    }
+    wave_lds_sync();
+    double* SG = WS;                                             // Sz_bar G  (n x D, over W Sigma_z)
+    for (int idx = lane; idx < n * D; idx += 64) {
+        const int i = idx / D, j = idx - i * D;
+        double v = 0.0;
+        for (int u = 0; u < A; ++u) v = fma(Sz[i * n + D + u], K[u * D + j], v);
+        SG[idx] = Sz[i * n + j] + v;
+    }
+    for (int idx = lane; idx < A * D; idx += 64) {               // action rows of (Sz_bar + Sz_bar^T) (G Sigma_t)
+        const int u = idx / D, j = idx - u * D;
+        double v = 0.0;
+        for (int k = 0; k < n; ++k) v = fma(Sz[(D + u) * n + k] + Sz[k * n + D + u], GS[k * D + j], v);
+        gK[idx] = v;
+    }
+    wave_lds_sync();
+    for (int idx = lane; idx < D * D; idx += 64) {               // G^T (Sz_bar G)
+        const int i = idx / D, j = idx - i * D;
+        double v = 0.0;
+        for (int u = 0; u < A; ++u) v = fma(K[u * D + i], SG[(D + u) * D + j], v);
+        v = SG[i * D + j] + v;
+        if (use_constraints && i == j) {
+            const double sq = Sg[i * D + i];                     // the variance as sigma, as cost_adjoint_wave
+            const double zmin = (smin[i] - mu[i]) / sq, zmax = (smax[i] - mu[i]) / sq;
+            const double pmin = exp(-0.5 * zmin * zmin) * 0.3989422804014327, pmax = exp(-0.5 * zmax * zmax) * 0.3989422804014327;
+            v += wm * (-pmin * zmin + pmax * zmax) / sq;
+        }
+        gSig[idx] = v;
+    }
+}
+
 // One wavefront per candidate of the reverse sweep.  t_post >= 0: the reverse tile launch of step t_post is done -- x_bar from its
 // sums, lambda_t = lambda_{t+1} + x_bar[:D] + (cost partial + seed), actions_bar_t = (cost partial) + x_bar[D:D+A]; t_post < 0
 // (first launch): the adjoints start at the terminal index H.  t_pre >= 0: step t_pre is opened -- its cost partials and seeds,
 // A = I + V_s, W = 2 Sigma_t A Lambda, the coefficients and model inputs of its tile launch, Lambda_t = sym(.) + A Lambda A^T;
 // t_pre < 0 (last launch): lambda_0 / Lambda_0 go to mu0_bar / S0_bar.
-__global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollArgs p, int t_post, int t_pre) {
+// FB (compile time; the open-loop instantiation is the kernel it was): the closed loop -- K_t is loaded, the stage's cost partials
+// come from cost_adjoint_feedback_wave (with the one wrt K_t), A = I + C with C = V_s + K_t^T V_u, the action rows of W are
+// K_t C_bar (C_bar = the state rows, 2 Sigma_t A Lambda), and opening step t writes gains_bar_t = (cost partial) + V_u C_bar^T.
+// Static LDS of the FB instantiation at kMaxD = 16, kMaxE = 24: 5520 doubles = 44160 bytes (open loop: 3760 = 30080).
+template <bool FB>
+__global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(std::conditional_t<FB, LbFbArgs, LbRollArgs> p, int t_post,
+                                                                        int t_pre) {
     constexpr int kN = kMaxE;                        // D + A <= E <= kMaxE
+    constexpr int kTmp = FB ? cost_adjoint_feedback_tmp(kMaxD, kN - kMaxD) : 2 * kN * kN + 3 * kN;
+    constexpr int kWR = FB ? kMaxE : kMaxD;          // rows of W that may be non-zero
+    constexpr int kAD = (kMaxE / 2) * (kMaxE - kMaxE / 2);      // A D <= this for D + A <= kMaxE
+    static_assert(kMaxE / 2 <= kMaxD, "bound of A D");
     __shared__ double s_cost[kN + kN * kN + kMaxD * kMaxD + 2 * kMaxD];
-    __shared__ double s_tmp[2 * kN * kN + 3 * kN];
+    __shared__ double s_tmp[kTmp];
     __shared__ double s_lam[kMaxD], s_Lam[kMaxD * kMaxD];
     __shared__ double s_gmu[kMaxD], s_gSig[kMaxD * kMaxD], s_gu[kN];
     __shared__ double s_mu[kMaxD], s_Sg[kMaxD * kMaxD], s_act[kN], s_M[kMaxD];
-    __shared__ double s_A[kMaxD][kMaxD], s_AL[kMaxD][kMaxD], s_W[kMaxD][kMaxD];
+    __shared__ double s_A[kMaxD][kMaxD], s_AL[kMaxD][kMaxD], s_W[kWR][kMaxD];
+    [[maybe_unused]] __shared__ double s_V[FB ? kMaxE : 1][kMaxD];      // FB: the kept rows of V [state or action input][output]
+    [[maybe_unused]] __shared__ double s_K[FB ? kAD : 1];               // FB: K_t (A, D) row-major
+    [[maybe_unused]] __shared__ double s_gK[FB ? kAD : 1];              // FB: the cost partial wrt K_t (A, D)
     const int b = blockIdx.x, lane = threadIdx.x;
     const int D = p.D, E = p.E, A = p.A, H = p.H, DD = D * D, n = D + A, NW = p.NW;
     const size_t Mc = (size_t)p.Mc;
@@ -508,13 +721,28 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollAr
         for (int i = lane; i < DD; i += 64) s_Sg[i] = p.Sig[bt * DD + i];
         if (!terminal)
             for (int i = lane; i < A; i += 64) s_act[i] = p.actions[((size_t)b * H + t) * A + i];
+        if constexpr (FB) {
+            if (!terminal) {
+                const double* K = p.gains + (size_t)b * (size_t)p.gain_stride + (size_t)t * A * D;
+                for (int i = lane; i < A * D; i += 64) s_K[i] = K[i];
+            }
+        }
         wave_lds_sync();
         if (cost_on) {
             double wm, wv;
             seeded_cost_weights(has_cm, has_cm ? sd.cm[bt] : 0.0, has_cv, has_cv ? sd.cv[bt] : 0.0, has_J, jb, p.kappa,
                                 has_J ? p.cv[bt] : 1.0, inv_n, wm, wv);
-            cost_adjoint_wave(lane, D, A, terminal, s_mu, s_Sg, s_act, target, terminal ? WT : Wst, smin, smax,
-                              p.use_constraints != 0, wm, wv, s_tmp, s_gmu, s_gSig, s_gu);
+            bool done = false;
+            if constexpr (FB) {
+                if (!terminal) {
+                    cost_adjoint_feedback_wave(lane, D, A, s_mu, s_Sg, s_act, s_K, target, Wst, smin, smax, p.use_constraints != 0,
+                                               wm, wv, s_tmp, s_gmu, s_gSig, s_gu, s_gK);
+                    done = true;
+                }
+            }
+            if (!done)
+                cost_adjoint_wave(lane, D, A, terminal, s_mu, s_Sg, s_act, target, terminal ? WT : Wst, smin, smax,
+                                  p.use_constraints != 0, wm, wv, s_tmp, s_gmu, s_gSig, s_gu);
             wave_lds_sync();
         }
         for (int i = lane; i < D; i += 64) {
@@ -529,6 +757,10 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollAr
         }
         if (!cost_on || terminal)
             for (int i = lane; i < A; i += 64) s_gu[i] = 0.0;
+        if constexpr (FB) {
+            if (!cost_on)
+                for (int i = lane; i < A * D; i += 64) s_gK[i] = 0.0;
+        }
         wave_lds_sync();
     };
 
@@ -558,11 +790,22 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollAr
     const int t = t_pre;
     stage_adjoint(t);
     const double* keepM = p.stepM + ((size_t)b * H + t) * D;
-    const double* keepV = p.stepV + ((size_t)b * H + t) * DD;
+    const double* keepV = p.stepV + ((size_t)b * H + t) * (FB ? n * D : DD);
     for (int i = lane; i < D; i += 64) s_M[i] = keepM[i];
-    for (int idx = lane; idx < DD; idx += 64) {
-        const int i = idx / D, a = idx - i * D;
-        s_A[i][a] = keepV[idx] + (i == a ? 1.0 : 0.0);
+    if constexpr (FB) {
+        for (int idx = lane; idx < n * D; idx += 64) s_V[idx / D][idx % D] = keepV[idx];
+        wave_lds_sync();
+        for (int idx = lane; idx < DD; idx += 64) {              // A = I + C, C = V_s + K^T V_u as the forward forms it
+            const int i = idx / D, a = idx - i * D;
+            double v = 0.0;
+            for (int u = 0; u < A; ++u) v = fma(s_K[u * D + i], s_V[D + u][a], v);
+            s_A[i][a] = (s_V[i][a] + v) + (i == a ? 1.0 : 0.0);
+        }
+    } else {
+        for (int idx = lane; idx < DD; idx += 64) {
+            const int i = idx / D, a = idx - i * D;
+            s_A[i][a] = keepV[idx] + (i == a ? 1.0 : 0.0);
+        }
     }
     wave_lds_sync();
     for (int idx = lane; idx < DD; idx += 64) {                  // A Lambda
@@ -587,18 +830,37 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollAr
         g_Lam[i * D + j] = v;
         g_Lam[j * D + i] = v;
     }
+    if constexpr (FB) {
+        wave_lds_sync();                                         // the state rows of W are C_bar
+        for (int idx = lane; idx < A * D; idx += 64) {           // the action rows: K C_bar
+            const int u = idx / D, a = idx - u * D;
+            double v = 0.0;
+            for (int i = 0; i < D; ++i) v = fma(s_K[u * D + i], s_W[i][a], v);
+            s_W[D + u][a] = v;
+        }
+        if (p.gains_bar) {                                       // gains_bar_t = (cost partial) + V_u C_bar^T
+            double* gb = p.gains_bar + ((size_t)b * H + t) * A * D;
+            for (int idx = lane; idx < A * D; idx += 64) {
+                const int u = idx / D, i = idx - u * D;
+                double v = 0.0;
+                for (int a = 0; a < D; ++a) v = fma(s_V[D + u][a], s_W[i][a], v);
+                gb[idx] = s_gK[idx] + v;
+            }
+        }
+    }
     wave_lds_sync();
+    const int nW = FB ? n : D;                                   // rows of W that are not zero by construction
     for (int idx = lane; idx < D * NW; idx += 64) {
         const int a = idx / NW, which = idx - a * NW;
         double v;
         if (which == 0) v = s_lam[a];
         else if (which == 1) v = s_Lam[a * D + a];
-        else v = (which - 2 < D) ? s_W[which - 2][a] * p.ils2[a * E + which - 2] : 0.0;
+        else v = (which - 2 < nW) ? s_W[which - 2][a] * p.ils2[a * E + which - 2] : 0.0;
         p.coef[((size_t)a * NW + which) * Mc + b] = v;
     }
     for (int g = lane; g < E; g += 64) {
         double v = 0.0;
-        if (g < D)
+        if (g < nW)
             for (int a = 0; a < D; ++a) v = fma(s_W[g][a] * p.ils2[a * E + g], s_M[a], v);
         p.base[(size_t)b * E + g] = v;
     }
@@ -650,7 +912,7 @@ int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, 
     }
     if (!mb_out && !vb_out) return GPMPC_OK;
     LinearBwdPlan pl;
-    plan_moments_linear_backward(N, D, E, 0, P, 0, h->opt_moments_linear_bwd_chunk, pl);
+    plan_moments_linear_backward(N, D, E, 0, P, 0, h->opt_moments_linear_bwd_chunk, 0, pl);
     int rc = grow(h, h->linbws, pl.total);
     if (rc) return rc;
     double* ws = h->linbws.p;
@@ -682,11 +944,18 @@ int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, 
     return GPMPC_OK;
 }
 
-// a: filled by the entry point (model, cost settings, actions, shape, initial state); sd: the cotangents and initial-state outputs
-int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, double* actions_bar, hipStream_t s) {
+namespace {
+
+// a: filled by the entry point (model, cost settings, actions, shape, initial state); sd: the cotangents and initial-state outputs.
+// gains != NULL: the closed loop (gains (B, H, A, D) when per_candidate, else (H, A, D) shared; gains_bar (B, H, A, D) or NULL) --
+// the same plan with the action rows of V kept, the same init kernel and tile launches, with the forward, cost and reverse
+// kernels exchanged; a chunk of candidates offsets the gain pointer only when the gains are per candidate.
+int rollout_linear_backward_chunks(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, const double* gains, bool per_candidate,
+                                   double* actions_bar, double* gains_bar, hipStream_t s) {
     const int N = a.N, D = a.D, E = a.E, A = a.A, H = a.H, B = a.B;
+    const bool fb = gains != nullptr;
     LinearBwdPlan pl;
-    plan_moments_linear_backward(N, D, E, A, B, H, h->opt_moments_linear_bwd_chunk, pl);
+    plan_moments_linear_backward(N, D, E, A, B, H, h->opt_moments_linear_bwd_chunk, fb ? A : 0, pl);
     int rc = grow(h, h->linbws, pl.total);
     if (rc) return rc;
     double* ws = h->linbws.p;
@@ -694,7 +963,8 @@ int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSe
     p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.beta = h->beta.p; p.iK = h->iK.p;
     p.part = ws + pl.part; p.coef = ws + pl.coef; p.Xq = ws + pl.xq;
     p.N = N; p.E = E; p.D = D; p.nCB = pl.nCB; p.NW = pl.NW; p.Mc = pl.Mc;
-    LbRollArgs q{};
+    LbFbArgs q{};                                     // (the open-loop kernels take its LbRollArgs part)
+    q.gain_stride = per_candidate ? (long long)H * A * D : 0;
     q.part = p.part; q.ils2 = p.ils2; q.var = p.var; q.cost = a.cost;
     q.mu = ws + pl.mu; q.Sig = ws + pl.Sig; q.stepM = ws + pl.stepM; q.stepV = ws + pl.stepV; q.cv = ws + pl.cv;
     q.adj = ws + pl.adj; q.coef = ws + pl.coef; q.base = ws + pl.base; q.Xq = ws + pl.xq;
@@ -707,6 +977,12 @@ int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSe
         const int rows = (int)((B - b0) < pl.chunk ? (B - b0) : pl.chunk);
         const size_t o = (size_t)b0;
         p.rows = rows;
+        q.gains = fb ? gains + o * (size_t)q.gain_stride : nullptr;
+        q.gains_bar = gains_bar ? gains_bar + o * H * A * D : nullptr;
+        auto launch_reverse = [&](int t_post, int t_pre) {
+            if (fb) hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel<true>, dim3(rows), dim3(64), 0, s, q, t_post, t_pre);
+            else hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel<false>, dim3(rows), dim3(64), 0, s, q, t_post, t_pre);
+        };
         q.actions = a.actions + o * H * A;
         q.actions_bar = actions_bar + o * H * A;
         q.sd.mu = sd.mu ? sd.mu + o * T1 * D : nullptr;
@@ -718,14 +994,19 @@ int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSe
         q.sd.S0_bar = sd.S0_bar ? sd.S0_bar + o * D * D : nullptr;
         // the forward, recomputed
         q.t = 0;
-        hipLaunchKernelGGL(rollout_linear_bwd_init_kernel, dim3(rows), dim3(64), 0, s, q);
+        hipLaunchKernelGGL(rollout_linear_bwd_init_kernel, dim3(rows), dim3(64), 0, s, static_cast<const LbRollArgs&>(q));
         for (int t = 0; t < H; ++t) {
             launch_tiles(p, true, false, s);
             q.t = t;
-            hipLaunchKernelGGL(rollout_linear_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, q);
+            if (fb) hipLaunchKernelGGL(rollout_linear_fb_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, q);
+            else hipLaunchKernelGGL(rollout_linear_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, static_cast<const LbRollArgs&>(q));
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());
-        if (sd.J) {                                   // the objective's weights need the cost variances
+        if (sd.J && fb) {                             // the objective's weights need the (closed-loop) cost variances
+            rc = launch_traj_cost_feedback(h, a, rows, q.mu, q.Sig, q.actions, q.gains, q.gain_stride, nullptr, ws + pl.cv, nullptr,
+                                           s);
+            if (rc) return rc;
+        } else if (sd.J) {                            // the objective's weights need the cost variances
             RolloutArgs c = a;
             c.B = rows;
             c.actions = q.actions;
@@ -734,14 +1015,25 @@ int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSe
             if (rc) return rc;
         }
         // the reverse sweep
-        hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel, dim3(rows), dim3(64), 0, s, q, -1, H - 1);
+        launch_reverse(-1, H - 1);
         for (int t = H - 1; t >= 0; --t) {
             launch_tiles(p, true, true, s);
-            hipLaunchKernelGGL(rollout_linear_bwd_reverse_kernel, dim3(rows), dim3(64), 0, s, q, t, t - 1);
+            launch_reverse(t, t - 1);
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());
     }
     return GPMPC_OK;
+}
+
+}  // namespace
+
+int run_rollout_linear_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, double* actions_bar, hipStream_t s) {
+    return rollout_linear_backward_chunks(h, a, sd, nullptr, false, actions_bar, nullptr, s);
+}
+
+int run_rollout_linear_feedback_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, const double* gains,
+                                         bool per_candidate, double* actions_bar, double* gains_bar, hipStream_t s) {
+    return rollout_linear_backward_chunks(h, a, sd, gains, per_candidate, actions_bar, gains_bar, s);
 }
 
 }  // namespace gpmpc_hip

@@ -568,6 +568,59 @@ class HipEngine:
         back = self.rollout_linear_backward(actions, mu0, S0, include_time, time0, J_bar=ones, want_initial=False)
         return {"J": J, "grad": back["actions_bar"]}
 
+    def rollout_linear_feedback_backward(self, actions, gains, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None,
+                                         cost_mu_bar=None, cost_var_bar=None, J_bar=None, want_initial=True, want_gains=True):
+        """Reverse-mode product of `rollout_linear_feedback` (gpmpc_rollout_linear_feedback_backward): its arguments and the
+        cotangents of `rollout_linear_backward` -> dict of device tensors actions_bar (B,H,A), with `want_gains` gains_bar
+        (B,H,A,D), and with `want_initial` mu0_bar (B,D) and S0_bar (B,D,D) per candidate (S0_bar the symmetric part).
+        `gains`: (A, D), (H, A, D) or (B, H, A, D) as in `rollout_linear_feedback`.  gains_bar is per candidate and per step
+        whatever the layout of `gains`: reduce it as the gains were broadcast -- `gains_bar.sum(0)` for a shared (H, A, D)
+        sequence, `gains_bar.sum((0, 1))` for one (A, D) gain.  gains None: `rollout_linear_backward` (no gains_bar).  The
+        forward is recomputed inside the call.  Cost / J seeds need set_cost.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        per_candidate = False
+        if gains is not None:
+            gains = torch.as_tensor(gains, dtype=torch.float64)
+            per_candidate, every_step = feedback_gains_layout(gains.shape, B, H, A, D)
+            if every_step:
+                gains = gains.expand(H, A, D)
+            gains = self._dev(gains)
+        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
+        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
+        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
+        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
+        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
+        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
+        if want_gains and gains is not None:
+            out["gains_bar"] = torch.empty((B, H, A, D), dtype=torch.float64, device=self.device)
+        if want_initial:
+            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
+            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.gpmpc_rollout_linear_feedback_backward(
+            self._h, actions.data_ptr(), ptr(gains), int(per_candidate), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
+            float(time0), ptr(mb), ptr(Sb), ptr(cmb), ptr(cvb), ptr(Jb), out["actions_bar"].data_ptr(), ptr(out.get("gains_bar")),
+            ptr(out.get("mu0_bar")), ptr(out.get("S0_bar")), self._stream()))
+        self._keep_rollout_linear_feedback_backward = (actions, gains, mb, Sb, cmb, cvb, Jb)   # alive until the call has read them
+        return out
+
+    def rollout_linear_feedback_grad(self, actions, gains, mu0, S0, include_time=False, time0=0.0):
+        """Objective of the closed-loop linearised rollout and its analytic gradients: dict(J (B,), grad (B,H,A) = dJ/d(actions),
+        gains_grad (B,H,A,D) = dJ/d(gains), per candidate: see `rollout_linear_feedback_backward`) of device tensors, from
+        `rollout_linear_feedback` followed by `rollout_linear_feedback_backward` with J_bar = 1."""
+        actions = self._dev(actions)
+        B = actions.shape[0]
+        J = torch.empty(B, dtype=torch.float64, device=self.device)
+        self.rollout_linear_feedback(actions, gains, mu0, S0, include_time, time0, trajectories=False, stage_costs=False,
+                                     out={"J": J})
+        ones = torch.ones(B, dtype=torch.float64, device=self.device)
+        back = self.rollout_linear_feedback_backward(actions, gains, mu0, S0, include_time, time0, J_bar=ones, want_initial=False)
+        return {"J": J, "grad": back["actions_bar"], "gains_grad": back.get("gains_bar")}
+
     def objective_grad_host(self, actions, mu0, S0, include_time=False, time0=0.0):
         """ONE action sequence (H, A) on the host -> objective, gradient, trajectory and stage costs on the host
         (gpmpc_objective_grad_host: the sequence travels as a kernel argument, the results through a pinned host buffer,

@@ -259,7 +259,8 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * gpmpc_predict_backward), "predict_cov_chunk_rows" (the same for gpmpc_predict_cov's rows of Xa),"moments_chunk_points" (gpmpc_moments' points per internal
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
- * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward).  Measurement (A/B) switches of single
+ * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
+ * gpmpc_rollout_linear_feedback_backward).  Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);
@@ -420,6 +421,52 @@ int gpmpc_rollout_linear_backward(gpmpc_t* h, const double* actions_dev, const d
                                   const double* Sig_bar_dev, const double* cost_mu_bar_dev, const double* cost_var_bar_dev,
                                   const double* J_bar_dev, double* actions_bar_out_dev, double* mu0_bar_out_dev,
                                   double* S0_bar_out_dev, void* stream);
+
+/*
+ * gpmpc_rollout_linear_feedback_backward: the reverse-mode product (vector-Jacobian product) of gpmpc_rollout_linear_feedback for
+ * B candidates: the gradients of
+ *     sum_t <mu_bar_t, mu_t> + <Sig_bar_t, Sig_t> + cost_mu_bar_t cost_mu_t + cost_var_bar_t cost_var_t  +  J_bar J
+ * (what gpmpc_rollout_linear_feedback writes for the same inputs and the same loaded cost) with respect to each candidate's
+ * actions ubar, its gains K_t and the initial mean and covariance, per candidate.  Inputs as gpmpc_rollout_linear_feedback
+ * (gains_dev (B,H,A,D) when gains_per_candidate != 0, else (H,A,D) shared); cotangents, conventions, NULL rules and errors as
+ * gpmpc_rollout_linear_backward.  Outputs, overwritten (not accumulated into):
+ *   actions_bar_out_dev (B,H,A)  required
+ *   gains_bar_out_dev (B,H,A,D)  or NULL (not written): ALWAYS per candidate, whatever the layout of gains_dev; a shared gain's
+ *                                gradient is the sum over B (the rule of the shared initial state) -- the entry does not reduce
+ *   mu0_bar_out_dev (B,D), S0_bar_out_dev (B,D,D)  or NULL (not written); S0_bar the symmetric part, exactly symmetric
+ * Forward, per candidate and step t (V_s / V_u the state / action rows of step t's V, K_t (A x D)):
+ *   C_t = V_s + K_t^T V_u,   A_t = I + C_t,   Sigma_{t+1} = A_t^T Sigma_t A_t + diag v,   mu_{t+1} = mu_t + M
+ * Reverse sweep t = H-1 .. 0 with the adjoints lambda_{t+1} (D), Lambda_{t+1} (D x D, symmetric):
+ *   C_bar = 2 Sigma_t A_t Lambda_{t+1}                    (D x D)
+ *   W     = [ C_bar ; K_t C_bar ; 0 ]                     (E x D: state rows, action rows, time row)
+ *   x_bar = the step formula of gpmpc_moments_linear_backward with M_bar = lambda_{t+1}, this W, s_a = Lambda_{t+1}[a,a]
+ *   actions_bar_t = (cost partial wrt ubar_t) + x_bar[D:D+A]
+ *   gains_bar_t   = (cost partial wrt K_t) + V_u C_bar^T                                  (A x D)
+ *   lambda_t = lambda_{t+1} + x_bar[:D] + (cost partial and seed wrt mu_t)
+ *   Lambda_t = sym(A_t Lambda_{t+1} A_t^T) + sym(cost partial and seed wrt Sigma_t)       (i <= j, mirrored)
+ * Stage cost partials (t < H), with G = [I ; K_t], Sigma_z = G Sigma_t G^T, e = [mu_t | ubar_t] - target, the loaded W (not
+ * assumed symmetric), Q = W Sigma_z W and the weights wm, wv of gpmpc_rollout_backward (cost_var_t: the closed-loop one):
+ *   Sz_bar = wm W^T + 4 wv (Q^T + (W^T e)(W e)^T),   e_bar = wm (W + W^T) e + 4 wv (Q + Q^T) e
+ *   wrt Sigma_t: G^T Sz_bar G (then symmetrised)     wrt K_t: the action rows of (Sz_bar + Sz_bar^T) G Sigma_t
+ *   wrt mu_t: e_bar[:D]                              wrt ubar_t: e_bar[D:]
+ * The constraint term (state marginals only: no partial wrt K_t), the terminal step (G = I, W_T, no action, no gain) and the clip
+ * (pass-through) are gpmpc_rollout_linear_backward's.
+ * The forward is RECOMPUTED inside the call, with the arithmetic of gpmpc_rollout_linear_feedback (the recomputed trajectory has
+ * its bits), and keeps every step's M and the D + A state and action rows of V, per chunk of candidates.  The tile launches are
+ * gpmpc_rollout_linear_backward's; the closed loop fills the action rows of their weights.  A candidate's results are bitwise the
+ * same alone and at any position of any batch, whatever "moments_linear_backward_chunk_points" is and whether its gains arrive
+ * shared or per candidate; a NULL cotangent and an all-zero one give the same bits; NULL outputs do not change the others' bits.
+ * Every sum runs in an order fixed by N, E, D and A alone; no atomics.  Workspace: gpmpc_rollout_linear_backward's own (within
+ * 16 MB or one 64-row tile's need).  Touches no other workspace and no gpmpc_last_* state.  Asynchronous on `stream`.
+ * gains_dev == NULL with gains_bar_out_dev == NULL: the call IS gpmpc_rollout_linear_backward (the same bits); gains_dev == NULL
+ * with gains_bar_out_dev != NULL: GPMPC_ERR_ARG.  Other errors: those of gpmpc_rollout_linear_backward.
+ */
+int gpmpc_rollout_linear_feedback_backward(gpmpc_t* h, const double* actions_dev, const double* gains_dev, int gains_per_candidate,
+                                           const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time,
+                                           double time0, const double* mu_bar_dev, const double* Sig_bar_dev,
+                                           const double* cost_mu_bar_dev, const double* cost_var_bar_dev, const double* J_bar_dev,
+                                           double* actions_bar_out_dev, double* gains_bar_out_dev, double* mu0_bar_out_dev,
+                                           double* S0_bar_out_dev, void* stream);
 
 /*
  * gpmpc_objective_grad_host  <->  ONE call of compute_mean_lcb_trajectory (gp_mpc_controller.py:229-285) as scipy's L-BFGS-B

@@ -1,5 +1,5 @@
 // Stand-alone host check of plan_moments_linear_backward (csrc/moments_linear_backward_plan.h): walks the chunk loop of
-// run_moments_linear_backward / run_rollout_linear_backward over a grid of shapes and checks that the arrays of a chunk's
+// run_moments_linear_backward / run_rollout_linear_backward / run_rollout_linear_feedback_backward over a grid of shapes and checks that the arrays of a chunk's
 // workspace do not overlap and that every index a kernel of the chunk may form stays inside its array.  Build with a host
 // sanitizer and run on the CPU:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/host_checks/moments_linear_backward_plan_check.cpp -o plan_check && ./plan_check
@@ -17,9 +17,10 @@ static int fails = 0;
         if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++fails; } \
     } while (0)
 
-static void one(int N, int D, int E, int A, long long count, int H, long long opt) {
+// KA: action rows of V kept per step (0: the open loop; A: the closed loop)
+static void one(int N, int D, int E, int A, long long count, int H, long long opt, int KA) {
     LinearBwdPlan p;
-    plan_moments_linear_backward(N, D, E, A, count, H, opt, p);
+    plan_moments_linear_backward(N, D, E, A, count, H, opt, KA, p);
     CHECK(p.nCB >= 1 && (long long)p.nCB * kLinBwdBN >= N && (long long)(p.nCB - 1) * kLinBwdBN < N);
     CHECK(p.NW == E + 2);
     CHECK(p.chunk >= 1 && p.chunk <= count);
@@ -34,11 +35,15 @@ static void one(int N, int D, int E, int A, long long count, int H, long long op
         o += lens[i];
     }
     CHECK(p.total == o);
+    if (KA == 0 && H > 0) {                            // the open loop: the sizes the plan had before it knew of KA
+        const size_t c = (size_t)p.chunk;
+        CHECK(p.n_stepV == c * H * D * D && p.n_adj == c * (2 * (size_t)D + (size_t)D * D + (size_t)A));
+    }
     if (H == 0) CHECK(p.n_xq + p.n_mu + p.n_Sig + p.n_stepM + p.n_stepV + p.n_cv + p.n_adj == 0);
     // within the budget, or one tile's need
     const long long tile = count < kLinBwdBM ? count : kLinBwdBM;
     LinearBwdPlan one_tile;
-    plan_moments_linear_backward(N, D, E, A, tile, H, tile, one_tile);
+    plan_moments_linear_backward(N, D, E, A, tile, H, tile, KA, one_tile);
     if (opt == 0) CHECK(p.total * sizeof(double) <= kLinBwdWsBudget || p.total <= one_tile.total);
     // touch what the kernels of every chunk touch, in a buffer of the planned size (the sanitizer sees an overrun)
     if (p.total > ((size_t)64 << 20) / sizeof(double)) return;
@@ -67,8 +72,9 @@ static void one(int N, int D, int E, int A, long long count, int H, long long op
             ws[p.Sig + (r * (H + 1) + H) * DD + DD - 1] += 1.0;
             CHECK((r * H + (H - 1)) * D + (D - 1) < p.n_stepM);
             ws[p.stepM + (r * H + (H - 1)) * D + (D - 1)] += 1.0;
-            CHECK((r * H + (H - 1)) * DD + DD - 1 < p.n_stepV);
-            ws[p.stepV + (r * H + (H - 1)) * DD + DD - 1] += 1.0;
+            const size_t VS = DD + (size_t)KA * D;                                             // the kept rows of one step's V
+            CHECK((r * H + (H - 1)) * VS + VS - 1 < p.n_stepV);
+            ws[p.stepV + (r * H + (H - 1)) * VS + VS - 1] += 1.0;
             CHECK(r * (H + 1) + H < p.n_cv);
             ws[p.cv + r * (H + 1) + H] += 1.0;
             const size_t AS = 2 * (size_t)D + DD + (size_t)A;
@@ -90,9 +96,13 @@ int main() {
         for (auto& s : DEAs)
             for (long long c : counts)
                 for (long long o : opts) {
-                    one(N, s[0], s[1], 0, c, 0, o);
-                    for (int H : {1, 12, 50}) one(N, s[0], s[1], s[2], c, H, o);
-                    n += 4;
+                    one(N, s[0], s[1], 0, c, 0, o, 0);
+                    for (int H : {1, 12, 50}) {
+                        one(N, s[0], s[1], s[2], c, H, o, 0);
+                        one(N, s[0], s[1], s[2], c, H, o, s[2]);
+                        n += 2;
+                    }
+                    n += 1;
                 }
     std::printf("%d plans checked, %d failures\n", n, fails);
     return fails ? 1 : 0;

@@ -59,6 +59,7 @@ SIGNATURES = {
     "gpmpc_rollout": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear_feedback": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_lqr_gains": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P]),
     "gpmpc_rollout_grad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -74,7 +75,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 def load(path=LIB_PATH):

@@ -105,7 +105,7 @@ class ControllerConfig:
     def __init__(self, len_horizon=15, actions_optimizer_params=None, init_from_previous_actions=True,
                  restarts_optim=1, optimize=True, num_repeat_actions=1,
                  candidate_optimizer=None, cem_candidates=256, cem_iterations=4, cem_elite_fraction=0.1,
-                 lbfgs_candidates=None, shard_over_ranks=False, feedback_gain=None):
+                 lbfgs_candidates=None, shard_over_ranks=False, feedback_gain=None, feedback_lqr_reg=0.0):
         self.len_horizon = len_horizon
         self.actions_optimizer_params = dict(_DEFAULT_OPTIMIZER if actions_optimizer_params is None
                                              else actions_optimizer_params)
@@ -123,8 +123,11 @@ class ControllerConfig:
         self.shard_over_ranks = shard_over_ranks
         # ancillary feedback u = ubar_t + K (x - mu_t) the candidates are planned under (closed-loop covariance and costs,
         # gpmpc_rollout_linear_feedback): an (A, D) or (H, A, D) array in model space, or None (open loop).  Needs
-        # ModelConfig.uncertainty_propagation = "linearized"
+        # ModelConfig.uncertainty_propagation = "linearized".  "lqr": every candidate's own LQR gains, designed on the device along
+        # its nominal trajectory on the reward's quadratic cost (gpmpc_lqr_gains), feedback_lqr_reg >= 0 added to the diagonal of
+        # Huu (certainty-equivalent; the action box is not modelled)
         self.feedback_gain = feedback_gain
+        self.feedback_lqr_reg = feedback_lqr_reg
 
 
 def _broadcast(v, shape):

@@ -153,7 +153,12 @@ class GpMpcController(BaseControllerObject):
         gain = getattr(self.config.controller, "feedback_gain", None)
         if gain is not None:
             self._check_propagation_supported()
-        kw = {} if gain is None else {"feedback_gains": self._feedback_gain_on_device(gain)}      # open loop: the call as ever
+        if gain is None:
+            kw = {}                                                                              # open loop: the call as ever
+        elif isinstance(gain, str):                                                              # "lqr": designed per candidate
+            kw = {"feedback_gains": gain, "lqr_reg": float(getattr(self.config.controller, "feedback_lqr_reg", 0.0))}
+        else:
+            kw = {"feedback_gains": self._feedback_gain_on_device(gain)}
         out = self.transition_model.predict_trajectory_batch(
             acts, obs_mu, obs_var, self.config.controller.len_horizon, self.iter_ctrl,
             trajectories=trajectories, stage_costs=True, **kw)

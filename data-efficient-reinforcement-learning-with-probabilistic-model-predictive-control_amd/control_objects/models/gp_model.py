@@ -401,7 +401,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
 
     # -- a3/a4 -------------------------------------------------------------------------
     def predict_trajectory_batch(self, actions, obs_mu, obs_var, len_horizon=None, current_time_idx=0,
-                                 trajectories=True, stage_costs=True, propagation=None, feedback_gains=None):
+                                 trajectories=True, stage_costs=True, propagation=None, feedback_gains=None, lqr_reg=0.0):
         """actions (B,H,A) -> dict of DEVICE tensors: J (B,), mu (B,H+1,D), Sig (B,H+1,D,D),
         cost_mu / cost_var (B,H+1).  Costs need set_cost() first.  Differentiable like the reference's predict_trajectory
         followed by get_rewards_trajectory: when grad mode is on and actions, obs_mu or obs_var requires grad, mu, Sig and
@@ -415,9 +415,14 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         dict, no autograd (NotImplementedError when grad mode is on and an input requires grad).
         `feedback_gains` (model space; (A, D), (H, A, D) or (B, H, A, D)): the linearised rollout in closed loop under
         u = actions_t + K_t (x - mu_t) (gpmpc_rollout_linear_feedback) -- Sig and the stage costs are the closed-loop ones, mu
-        is unchanged.  Only with "linearized" (ValueError with moment matching), and without autograd like it."""
+        is unchanged.  Only with "linearized" (ValueError with moment matching), and without autograd like it.
+        `feedback_gains="lqr"`: every candidate's own LQR gains, designed on the device along its nominal trajectory on the
+        loaded cost (gpmpc_lqr_gains, `lqr_reg` added to the diagonal of Huu) and handed to the closed-loop rollout without
+        leaving it; the dict then also holds "gains" (B, H, A, D).  Any other string is a ValueError."""
         if self._cost_key is None and stage_costs:
             raise RuntimeError("call set_cost(reward_config) before predicting costs")
+        if isinstance(feedback_gains, str) and feedback_gains != "lqr":
+            raise ValueError(f"feedback_gains must be an array or 'lqr', got {feedback_gains!r}")
         if feedback_gains is not None and self.propagation(propagation) != "linearized":
             raise ValueError("feedback_gains need propagation='linearized': moment matching has no closed-loop rollout")
         if self.propagation(propagation) == "linearized":
@@ -425,6 +430,12 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
             actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
             if len_horizon is not None and actions.shape[1] != len_horizon:
                 raise ValueError("actions.shape[1] != len_horizon")
+            if isinstance(feedback_gains, str):           # "lqr"
+                if self._cost_key is None:
+                    raise RuntimeError("call set_cost(reward_config) before feedback_gains='lqr': the gains are designed on it")
+                return self.engine.rollout_linear_lqr(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(),
+                                                      self.config.include_time_model, float(current_time_idx), trajectories,
+                                                      stage_costs, reg=float(lqr_reg))
             if feedback_gains is not None:
                 gains = feedback_gains if isinstance(feedback_gains, torch.Tensor) else np.asarray(feedback_gains)
                 return self.engine.rollout_linear_feedback(actions, torch.as_tensor(gains, dtype=F64), _t(obs_mu).numpy(),
@@ -467,15 +478,15 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                                                self.config.include_time_model, float(current_time_idx))
 
     def predict_trajectory(self, actions, obs_mu, obs_var, len_horizon, current_time_idx, propagation=None,
-                           feedback_gains=None):
+                           feedback_gains=None, lqr_reg=0.0):
         """Same signature / return shapes as the reference (:60-110): ((H+1,D), (H+1,D,D)) CPU tensors.  Differentiable like
         the reference: when grad mode is on and actions, obs_mu or obs_var requires grad, both outputs carry a grad_fn and
         backward() reaches the inputs through gpmpc_rollout_backward (see predict_trajectory_batch); obs_var's gradient is the
-        symmetric part of the reference's.  `propagation`, `feedback_gains` ((A, D) or (H, A, D)): see
+        symmetric part of the reference's.  `propagation`, `feedback_gains` ((A, D), (H, A, D) or "lqr"), `lqr_reg`: see
         predict_trajectory_batch."""
         out = self.predict_trajectory_batch(_t(actions)[None], obs_mu, obs_var, len_horizon, current_time_idx,
                                             trajectories=True, stage_costs=False, propagation=propagation,
-                                            feedback_gains=feedback_gains)
+                                            feedback_gains=feedback_gains, lqr_reg=lqr_reg)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()
 
     def predict(self, inputs, include_noise=True):

@@ -1,9 +1,11 @@
 // abi.hip -- extern "C" entry points of libgpmpc_hip.so (declared in include/gpmpc.h).
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <dlfcn.h>
 
 #include "gpmpc_internal.h"
+#include "lqr_gains_plan.h"
 
 // ROCTx ranges around the entry points (tracing row): visible in `rocprofv3 --marker-trace` timelines
 // as gpmpc_prepare / gpmpc_rollout / gpmpc_rollout_grad / gpmpc_argmin.  The marker library is looked up at first use
@@ -53,7 +55,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 18; }
+int gpmpc_abi_version(void) { return 19; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -81,7 +83,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->Xf, &h->Yf, &h->fgws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -145,6 +147,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     else if (!strcmp(name, "moments_linear_backward_chunk_points")) {
         if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
         h->opt_moments_linear_bwd_chunk = (int)value;
+    }
+    else if (!strcmp(name, "lqr_gains_chunk_points")) {
+        if (value < 0 || value > (1 << 24)) { h->err = "lqr_gains_chunk_points: 0 (auto) or a number of candidates"; return GPMPC_ERR_ARG; }
+        h->opt_lqr_gains_chunk = (int)value;
     }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
@@ -458,6 +464,25 @@ int gpmpc_rollout_linear_feedback(gpmpc_t* g, const double* actions, const doubl
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
     return run_rollout_linear(H_(g), a, (hipStream_t)stream, gains, gains_per_candidate != 0);
+}
+
+int gpmpc_lqr_gains(gpmpc_t* g, const double* actions, const double* mu0, int B, int H, int A, int include_time, double time0,
+                    double reg, double* gains_out, double* P_out, int* flags_out, void* stream) {
+    Range roctx_range("gpmpc_lqr_gains");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "lqr_gains before prepare / set_factors");
+    if (!actions || !mu0 || !gains_out) return bad(g, "null argument");
+    if (B < 1 || H < 1 || A < 1) return bad(g, "lqr_gains: need B >= 1, H >= 1, A >= 1");
+    if (h->D + A + (include_time ? 1 : 0) != h->E) return bad(g, "D + A (+1 with time) must equal the model's input dim E");
+    if (!(reg >= 0.0) || !std::isfinite(reg)) return bad(g, "lqr_gains: reg must be finite and >= 0");
+    if (A > kLqrMaxA) {
+        h->err = "lqr_gains: A beyond the compiled limit (A <= 8)";
+        return GPMPC_ERR_LIMIT;
+    }
+    if (h->cost_D != h->D || h->cost_A != A) return bad(g, "gpmpc_set_cost not called for this (D, A)");
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_lqr_gains(h, actions, mu0, B, H, A, include_time, time0, reg, gains_out, P_out, flags_out, (hipStream_t)stream);
 }
 
 int gpmpc_rollout_grad(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,

@@ -212,6 +212,7 @@ struct Handle {
     Buf mombws;   // gpmpc_moments_backward: setup results | A_ab^-1 | per-(point, output) sums | per-(point, pair, row tile) partials
     Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
     Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward / gpmpc_rollout_linear_feedback_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
+    Buf lqrws;    // gpmpc_lqr_gains: model inputs | M of the step at hand | every step's V of one chunk of candidates
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -305,6 +306,7 @@ struct Handle {
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_moments_linear_bwd_chunk = 0;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: the same for their chunks
+    int opt_lqr_gains_chunk = 0;     // gpmpc_lqr_gains: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int lds_limit = 160 * 1024;
     int num_cu = 256;
 };
@@ -513,6 +515,11 @@ int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const dou
 // settings of `a`; each output may be NULL
 int launch_traj_cost_feedback(Handle* h, const RolloutArgs& a, int rows, const double* mu, const double* Sig, const double* actions,
                               const double* gains, long long gain_stride, double* cm, double* cv, double* J, hipStream_t s);
+// lqr_gains.hip: the LQR gains (B, H, A, D) of the linearisation along each candidate's nominal trajectory on the loaded quadratic
+// cost (validated by the entry point: model, cost for this (D, A), 1 <= A <= kLqrMaxA, reg >= 0); P_out (B, H + 1, D, D) and
+// flags_out (B) may be NULL
+int run_lqr_gains(Handle* h, const double* actions, const double* mu0_host, int B, int H, int A, int include_time, double time0,
+                  double reg, double* gains_out, double* P_out, int* flags_out, hipStream_t s);
 // moments_backward.hip: gradients of run_moments wrt mu and Sig (symmetric part) for upstream Mb / Sb / Vb (each may be NULL)
 int run_moments_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
                          const double* Vb, double* mb_out, double* vb_out, hipStream_t s);

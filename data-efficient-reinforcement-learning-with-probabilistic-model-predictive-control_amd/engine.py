@@ -470,6 +470,40 @@ class HipEngine:
         self._keep_rollout_linear_feedback = (actions, gains)      # alive until the asynchronous call has read them
         return out
 
+    def lqr_gains(self, actions, mu0, include_time=False, time0=0.0, reg=0.0, want_cost_to_go=False, want_flags=False):
+        """The LQR feedback gains of the linearisation along each candidate's nominal trajectory on the loaded quadratic cost
+        (gpmpc_lqr_gains; needs set_cost): dict of device tensors `gains` (B, H, A, D) -- the sign and layout
+        `rollout_linear_feedback` takes per candidate --, with want_cost_to_go `P` (B, H + 1, D, D), with want_flags `flags` (B,)
+        int32, the number of steps whose factorisation lost a pivot (their gain is zero).  `reg` >= 0 is added to the diagonal
+        of Huu.  Certainty-equivalent; the action box is not modelled.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        out = {"gains": torch.empty((B, H, A, D), dtype=torch.float64, device=self.device)}
+        if want_cost_to_go:
+            out["P"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
+        if want_flags:
+            out["flags"] = torch.empty(B, dtype=torch.int32, device=self.device)
+
+        def ptr(k):
+            return out[k].data_ptr() if k in out else None
+        self._check(self.lib.gpmpc_lqr_gains(self._h, actions.data_ptr(), _hp(mu0), B, H, A, int(bool(include_time)), float(time0),
+                                             float(reg), ptr("gains"), ptr("P"), ptr("flags"), self._stream()))
+        self._keep_lqr_gains = actions           # alive until the asynchronous call has read it
+        return out
+
+    def rollout_linear_lqr(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None,
+                           reg=0.0):
+        """`rollout_linear_feedback` under each candidate's own LQR gains: `lqr_gains`, then the closed-loop rollout with those
+        (B, H, A, D) gains, which never leave the device.  That call's dict plus "gains"; bit for bit the two calls made
+        separately.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        gains = self.lqr_gains(actions, mu0, include_time, time0, reg)["gains"]
+        res = self.rollout_linear_feedback(actions, gains, mu0, S0, include_time, time0, trajectories, stage_costs, out)
+        res["gains"] = gains
+        return res
+
     def rollout_grad(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=False):
         """Objective and analytic gradient: dict(J (B,), grad (B,H,A) = dJ/d(actions), [mu, Sig, cost_mu, cost_var]).
         Raises GpmpcError(GPMPC_ERR_LIMIT) for shapes the gradient kernels do not cover (callers then

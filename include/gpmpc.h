@@ -260,7 +260,8 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
- * gpmpc_rollout_linear_feedback_backward).  Measurement (A/B) switches of single
+ * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto).
+ * Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */
 int gpmpc_set_option(gpmpc_t* h, const char* name, long long value);
@@ -339,6 +340,41 @@ int gpmpc_rollout_linear_feedback(gpmpc_t* h, const double* actions_dev, const d
                                   const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time,
                                   double time0, double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev,
                                   double* cost_var_out_dev, double* J_out_dev, void* stream);
+
+/*
+ * gpmpc_lqr_gains: the feedback gains gpmpc_rollout_linear_feedback takes as given -- per candidate, the finite-horizon LQR gains
+ * of the linearisation along its nominal (mean) trajectory on the loaded quadratic cost, as cautious GP-MPC chooses its ancillary
+ * controller.  Inputs as gpmpc_rollout_linear (actions_dev (B,H,A) = ubar, mu0_host (D), include_time / time0); there is no S0:
+ * NO covariance enters, and no K* iK product runs.
+ * Nominal trajectory: the model input of step t is [mu_t | ubar_t | time0 + t], mu_0 = mu0, mu_{t+1} = mu_t + M, with M and the
+ * mean Jacobian V (E x D, V[e,a] = dM_a / dm_e) of gpmpc_moments_linear at that input: mu_t is bit for bit
+ * gpmpc_rollout_linear's.  The time row of V is ignored.  With V_s / V_u the state / action rows of V,
+ *   A_t = I_D + V_s^T (D x D),   B_t = V_u^T (D x A):   delta x_{t+1} = A_t delta x_t + B_t delta u_t.
+ * Cost: the block loaded by gpmpc_set_cost for this (D, A): W_s = (W + W^T) / 2, Q = W_s[:D,:D], N = W_s[:D,D:], R = W_s[D:,D:],
+ * P_H = (W_T + W_T^T) / 2.  Target, kappa, clipping and the state constraints do not enter: linear terms and the LCB do not
+ * change the optimal deviation gain.  The gain is CERTAINTY-EQUIVALENT: it is designed on the mean dynamics alone, and the
+ * variance term of the LCB is not part of the design.  NOT modelled, as in gpmpc_rollout_linear_feedback: the action box [0, 1]
+ * (the realised action is not clipped).
+ * Riccati sweep, for t = H-1 .. 0:
+ *   F = P_{t+1} A_t,   Huu = R + B_t^T P_{t+1} B_t + reg I (A x A, formed for i <= j and mirrored),   Hux = N^T + B_t^T F (A x D),
+ *   Huu = L L^T (Cholesky),   K_t = -Huu^-1 Hux (A x D),   P_t = Q + A_t^T F + Hux^T K_t (formed for i <= j and mirrored: exactly
+ *   symmetric).
+ * A pivot of the factorisation that is <= 0 or not finite does not abort the call and produces no NaN: that step gets K_t = 0 and
+ * P_t = Q + A_t^T F (for i <= j, mirrored), and the candidate's flag counts such steps (0: a clean sweep).
+ * Outputs: gains_out_dev (B,H,A,D), required -- K_t [action][state] with the sign and layout gpmpc_rollout_linear_feedback expects
+ * for gains_per_candidate != 0 (u = ubar_t + K_t (x - mu_t)); P_out_dev (B,H+1,D,D) the cost-to-go matrices (index H = P_H), or
+ * NULL; flags_out_dev (B) ints, or NULL.  A NULL P_out_dev / flags_out_dev does not change the gains' bits.
+ * Per step one launch that writes the chunk's model inputs and the no-matrix-product form of gpmpc_moments_linear (its kernels and
+ * workspace, unchanged); after the H steps one launch with a wavefront per candidate runs the sweep.  Plain kernels: no atomics, no
+ * waits between workgroups; every sum runs in an order fixed by N, E, D and A alone.  A candidate's gains, P and flag are bitwise
+ * the same alone, at any position of any batch, and whatever "lqr_gains_chunk_points" (and "moments_linear_chunk_points") is.
+ * Workspace of its own (a chunk's model inputs, M and the V of all H steps), within 16 MB or one 64-candidate chunk's need, beside
+ * gpmpc_moments_linear's; no gpmpc_last_* state is touched.  Asynchronous on `stream`.
+ * GPMPC_ERR_ARG: no cached model, NULL actions / mu0 / gains, B < 1, H < 1, A < 1, D + A (+1) != E, reg < 0 or not finite, no
+ * gpmpc_set_cost for this (D, A).  GPMPC_ERR_LIMIT: A > 8.  No output is written on an error.
+ */
+int gpmpc_lqr_gains(gpmpc_t* h, const double* actions_dev, const double* mu0_host, int B, int H, int A, int include_time,
+                    double time0, double reg, double* gains_out_dev, double* P_out_dev, int* flags_out_dev, void* stream);
 
 /*
  * Objective AND analytic gradient: J_out_dev (B), grad_out_dev (B,H,A) = dJ/d(actions) -- what the reference obtains with

@@ -37,6 +37,7 @@ SIGNATURES = {
     "gpmpc_destroy": (C.c_int, [_P]),
     "gpmpc_last_error": (C.c_char_p, [_P]),
     "gpmpc_prepare": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "gpmpc_prepare_sparse": (C.c_int, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _D, _I, _I, _P]),
     "gpmpc_set_factors": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "gpmpc_get_factors": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "gpmpc_read_factors": (C.c_int, [_P, _P, _P, _P]),
@@ -75,7 +76,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 def load(path=LIB_PATH):

@@ -2,6 +2,7 @@
 arithmetic runs in the HIP library (C ABI of include/gpmpc.h):
 
     prepare_inference   -> gpmpc_prepare   (K build, Cholesky, iK, beta; reference :182-191, 400-431)
+                           or gpmpc_prepare_sparse (ModelConfig.num_inducing_points: a sparse GP on inducing inputs)
     predict_trajectory  -> gpmpc_rollout   (H-step moment matching;     reference :60-180)
 
 plus the batched entry points the reference lacks (`predict_trajectory_batch`,
@@ -125,6 +126,14 @@ def _check_trajectory_grad_shape(D, A, include_time):
 
 
 PROPAGATIONS = ("moment_matching", "linearized")
+
+
+def inducing_rows(N, M):
+    """The rows of an N-point memory that serve as the M inducing inputs of the sparse model (ModelConfig.num_inducing_points):
+    round(i (N - 1) / (M - 1)), i = 0..M-1 (M = 1: row 0) -- deterministic, first and last point included, distinct for M <= N."""
+    if M == 1:
+        return [0]
+    return [int(round(i * (N - 1) / (M - 1))) for i in range(M)]
 
 
 def _no_linearized_autograd(what, *tensors):
@@ -322,6 +331,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self.x_mem = None
         self.y_mem = None
         self._cost_key = None
+        self.is_sparse = False          # the cached model is the sparse one of gpmpc_prepare_sparse
 
     last_training_launches = None       # gpmpc_mll calls of the last `train` in this process (lockstep: ~ the longest GP's count)
 
@@ -354,17 +364,38 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         return self.engine.factors()[1].cpu()
 
     # -- a1/a2 -------------------------------------------------------------------------
-    def prepare_inference(self, inputs, state_changes):
+    def prepare_inference(self, inputs, state_changes, inducing_inputs=None):
+        """Cache the model of the memory (inputs (N, E), state_changes (N, D)).  With ModelConfig.num_inducing_points = M and
+        more than M memory points -- or with explicit `inducing_inputs` (M', E), which override the choice below -- the cached
+        model is the sparse GP of gpmpc_prepare_sparse on the inducing inputs: the rows round(i (N - 1) / (M - 1)), i = 0..M-1,
+        of `inputs` (M = 1: row 0), a deterministic spread over the memory in its order.  Otherwise (the option unset, or
+        N <= M) it is the exact GP, as ever.  x_mem / y_mem are the whole memory either way: training and save_state see all
+        of it."""
         self.x_mem = inputs
         self.y_mem = state_changes
-        self.engine.prepare(inputs, state_changes, self.lengthscales, self.variances, self.noises)
+        M = getattr(self.config, "num_inducing_points", None)
+        if inducing_inputs is None and M is not None and len(inputs) > M:
+            inducing_inputs = _t(inputs)[inducing_rows(len(inputs), M)]
+        self.is_sparse = inducing_inputs is not None
+        if self.is_sparse:
+            self.engine.prepare_sparse(inputs, state_changes, inducing_inputs, self.lengthscales, self.variances, self.noises,
+                                       getattr(self.config, "inducing_jitter", 1e-6))
+        else:
+            self.engine.prepare(inputs, state_changes, self.lengthscales, self.variances, self.noises)
 
     def forget(self, indices):
         """Drop the memory points `indices` (strictly ascending rows of the memory of the last prepare_inference) from the
         cached model (gpmpc_forget, O(k N^2)) and from x_mem / y_mem, so that save_state ships the reduced memory to training.
-        A prepare_inference of the reduced memory plus a few appended points is then a border update, not a factorisation."""
+        A prepare_inference of the reduced memory plus a few appended points is then a border update, not a factorisation.
+        A sparse model (ModelConfig.num_inducing_points) has no downdate -- its factors condense all memory points into the
+        inducing ones: GpmpcError(GPMPC_ERR_ARG), with the model and x_mem / y_mem untouched; call prepare_inference on the
+        reduced memory instead (the controller does: a capped memory re-prepares its window)."""
         if self.x_mem is None:
             raise RuntimeError("call prepare_inference(inputs, state_changes) before forget")
+        if getattr(self, "is_sparse", False):
+            from ..._lib import GPMPC_ERR_ARG, GpmpcError
+            raise GpmpcError(GPMPC_ERR_ARG, "forget: the cached model is sparse (ModelConfig.num_inducing_points) and has no "
+                             "downdate; call prepare_inference on the reduced memory")
         idx = np.asarray(indices).reshape(-1)
         self.engine.forget(idx)
         keep = torch.ones(len(self.x_mem), dtype=torch.bool)
@@ -553,7 +584,8 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         return SavedState(inputs=self.x_mem, states_change=self.y_mem,
                           parameters=[m.state_dict() for m in self.models],
                           constraints_hyperparams={k: v for k, v in vars(self.config).items()
-                                                   if k not in ("gp_init", "uncertainty_propagation")})
+                                                   if k not in ("gp_init", "uncertainty_propagation", "num_inducing_points",
+                                                                "inducing_jitter")})
 
     def load_state(self, saved_state):
         for m, p in zip(self.models, saved_state.parameters):

@@ -55,7 +55,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 19; }
+int gpmpc_abi_version(void) { return 20; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -83,7 +83,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -152,6 +152,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
         if (value < 0 || value > (1 << 24)) { h->err = "lqr_gains_chunk_points: 0 (auto) or a number of candidates"; return GPMPC_ERR_ARG; }
         h->opt_lqr_gains_chunk = (int)value;
     }
+    else if (!strcmp(name, "sparse_chunk_points")) {
+        if (value < 0 || value > (1 << 24) || (value & 63)) { h->err = "sparse_chunk_points: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
+        h->opt_sparse_chunk = (int)value;
+    }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
     else if (!strcmp(name, "grad_separable")) h->opt_grad_sep = (int)value;
@@ -194,6 +198,18 @@ int gpmpc_prepare(gpmpc_t* g, const double* X, const double* Y, const double* ls
     if (rc) return rc;
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     return run_prepare(H_(g), X, Y, ls, os, noise, N, D, E, (hipStream_t)stream);
+}
+
+int gpmpc_prepare_sparse(gpmpc_t* g, const double* X, const double* Y, int N, const double* Z, int M, const double* ls,
+                         const double* os, const double* noise, double jitter_rel, int D, int E, void* stream) {
+    Range roctx_range("gpmpc_prepare_sparse");
+    if (!g || !X || !Y || !Z || !ls || !os || !noise) return bad(g, "null argument");
+    if (M < 1) return bad(g, "prepare_sparse: need M >= 1 inducing inputs");
+    if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return bad(g, "prepare_sparse: jitter_rel must be finite and >= 0");
+    int rc = check_dims(g, N, D, E);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_prepare_sparse(H_(g), X, Y, N, Z, M, ls, os, noise, jitter_rel, D, E, (hipStream_t)stream);
 }
 
 int gpmpc_set_factors(gpmpc_t* g, const double* X, const double* iK, const double* beta, const double* ls,

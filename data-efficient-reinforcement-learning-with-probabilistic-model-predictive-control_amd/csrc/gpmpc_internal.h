@@ -229,6 +229,7 @@ struct Handle {
     // gpmpc_forget: the record's ping-pong partners, the downdate's coefficients | a copy of hyp for the full path, removed rows
     Buf Xf, Yf;   // (N, E), (N, D): trade places with Xc / Yc
     Buf fgws;
+    Buf spws;     // gpmpc_prepare_sparse: Yu | R | partial sums of w | w | jitter | Kuf and V of one chunk of points (prepare_sparse_plan.h)
     int* fidx = nullptr;         // device copy of the removed rows when there are more than 8
     size_t fidx_cap = 0;         // ints
     Buf hio;      // gpmpc_objective_grad_host: actions | J | grad | mu | Sig | cost_mu | cost_var of one candidate (device side)
@@ -298,7 +299,8 @@ struct Handle {
     int opt_prepare_overlap = 1;     // 32-wide panel path: the inverse's launches on a side stream beside the factorisation's (0: one stream, A/B)
     int opt_gram_shared = 1;         // large N: K of all GPs by one workgroup per tile, squared differences shared (0: per-GP kernel, A/B)
     int opt_fused_prepare = 1;       // N <= 256: the whole factorisation in one launch (prepare_small.hip); 0: panel path (A/B, tests)
-    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget)
+    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget), 4 sparse (gpmpc_prepare_sparse)
+    int opt_sparse_chunk = 0;        // gpmpc_prepare_sparse: memory points per chunk (0: as many as a 64 MB workspace holds; else a multiple of 64)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
     int opt_predict_bwd_chunk = 0;   // gpmpc_predict_backward: the same for its chunks
     int opt_predict_cov_chunk = 0;   // gpmpc_predict_cov: rows of Xa per chunk (0: as many as a 256 MB workspace holds; tests set a small one)
@@ -488,6 +490,20 @@ int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const
 int grow(Handle* h, Buf& b, size_t need);
 // ... gpmpc_forget: rows idx_host (validated: strictly ascending, in range, 1 <= k < N) leave the cached model
 int run_forget(Handle* h, const int* idx_host, int k, hipStream_t s);
+// ... gpmpc_prepare_sparse: the DTC model of (X, Y) on the inducing inputs Z, left in the state run_set_factors(Z, iK_eff, beta_eff)
+// would leave (validated by the entry point)
+int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const double* Z, int M, const double* ls, const double* os,
+                       const double* noise, double jitter_rel, int D, int E, hipStream_t s);
+// prepare_sparse.hip: the launches of its stream over the memory points and of its tail (h->Xt / ils2 / var hold the packed Z)
+int launch_sparse_jitter(Handle* h, const double* os, double jitter_rel, int D, double* jit, hipStream_t s);
+int launch_sparse_panel(Handle* h, const double* X, int N, int M, int D, int E, int n0, int cn, int Cs, double* kuf, hipStream_t s);
+int launch_sparse_accumulate(Handle* h, const double* v, const double* Y, int M, int D, int n0, int cn, int Cs, double* G,
+                             double* wpart, hipStream_t s);
+int launch_sparse_bmat(Handle* h, const double* G, const double* wpart, const double* noise, int M, int D, double* Bm, double* w,
+                       hipStream_t s);
+int launch_sparse_beta(Handle* h, const double* Yu, const double* Yb, const double* w, const double* noise, int M, int D, double* t1,
+                       double* t2, double* beta, hipStream_t s);
+int launch_sparse_atb_sym(Handle* h, const double* A, const double* B, int M, int D, double* C, bool ident_minus, hipStream_t s);
 // forget.hip: one removal (iK, linv, beta) -> (gram, Tm, zvec); the record (and, with `tables`, X^T and the data range) without the rows
 int launch_forget_step(Handle* h, int n, int j, int D, int ldw, hipStream_t s);
 int launch_forget_pack(Handle* h, const ForgetRows& rm, int n1, int D, int E, double* Xn, double* Yn, bool tables, hipStream_t s);

@@ -14,6 +14,7 @@
 // D[row=(l>>4)+4r][col=l&15]).
 #include "device_common.h"
 #include "prepare_tiled.h"
+#include "prepare_sparse_plan.h"
 
 namespace gpmpc_hip {
 
@@ -1624,6 +1625,72 @@ int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, c
     if (p.path != PreparePath::small_whole && (rc = launch_tail(h, p, Y, N, D, s))) return rc;
     if ((rc = check_info(h, D, s))) return rc;
     commit_state(h, N, D, E);
+    return GPMPC_OK;
+}
+
+// gpmpc_prepare_sparse (kernels and formulas: prepare_sparse.hip).  The two M x M factorisations run through the launchers a full
+// factorisation of M points plans -- the panel chain or the outer panels, which factorise whatever sits in `gram`; the single
+// launch of prepare_small.hip builds its own Gram matrix from (X, Y), so its sizes take the panel chain here.  Buffers: Kuu and
+// later B and S = I - Yb^T Yb in `gram`, Yu and later Yb in `linv` (Yu is kept in the workspace), G in `iK` until B is formed.
+int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const double* Z, int M, const double* ls, const double* os,
+                       const double* noise, double jitter_rel, int D, int E, hipStream_t s) {
+    int rc = ensure_model_buffers(h, M, D, E, true);
+    if (rc) return rc;
+    SparsePlan sp;
+    plan_prepare_sparse(N, M, D, h->opt_sparse_chunk, sp);
+    if ((rc = grow(h, h->spws, sp.total))) return rc;
+    h->ready = false;
+    h->have_state = false;
+    h->last_prepare_mode = 4;
+    PreparePlan p;
+    {
+        const int keep = h->opt_fused_prepare;
+        h->opt_fused_prepare = 0;
+        plan_prepare(*h, M, p);
+        h->opt_fused_prepare = keep;
+    }
+    double* ws = h->spws.p;
+    const size_t MM = (size_t)D * M * M;
+    const size_t NNm = (size_t)M * M;
+    auto factor = [&]() -> int {                                   // gram -> L (lower triangle), linv = L^-1; synchronises
+        GPMPC_HIP_CHECK(h, hipMemsetAsync(h->linv.p, 0, MM * sizeof(double), s));
+        int r = p.path == PreparePath::outer ? factor_outer(h, p, M, D, s) : factor_panel32(h, p, M, D, s);
+        if (r) return r;
+        GPMPC_HIP_CHECK(h, hipGetLastError());
+        return check_info(h, D, s);
+    };
+    if ((rc = pack(h, Z, ls, os, M, D, E, s))) return rc;
+    if ((rc = launch_sparse_jitter(h, os, jitter_rel, D, ws + sp.jit, s))) return rc;
+    if ((rc = launch_gram(h, p, ws + sp.jit, M, D, E, s))) return rc;
+    if ((rc = factor())) return rc;
+    GPMPC_HIP_CHECK(h, hipMemcpyAsync(ws + sp.yu, h->linv.p, MM * sizeof(double), hipMemcpyDeviceToDevice, s));
+    // the stream over the memory points: Kuf, V = Yu Kuf (Yu lower triangular), G += V V^T, w += V y
+    double* G = h->iK.p;
+    GPMPC_HIP_CHECK(h, hipMemsetAsync(G, 0, MM * sizeof(double), s));
+    GPMPC_HIP_CHECK(h, hipMemsetAsync(ws + sp.wpart, 0, (size_t)D * M * kSparseLanes * sizeof(double), s));
+    const int Cs = sp.chunk;
+    const size_t panel = (size_t)M * Cs;
+    for (long long n0 = 0; n0 < N; n0 += Cs) {
+        const int cn = (N - n0 < Cs) ? (int)(N - n0) : Cs;
+        const int cn64 = (cn + 63) / 64 * 64;
+        if ((rc = launch_sparse_panel(h, X, N, M, D, E, (int)n0, cn, Cs, ws + sp.kuf, s))) return rc;
+        hipLaunchKernelGGL(gemm_nn_tiled_kernel, dim3(cn64 / TS, (M + TS - 1) / TS, D), dim3(256), 0, s, ws + sp.yu, M, NNm,
+                           ws + sp.kuf, Cs, panel, ws + sp.v, Cs, panel, M, cn64, M, 1.0, 0, 1);
+        if ((rc = launch_sparse_accumulate(h, ws + sp.v, Y, M, D, (int)n0, cn, Cs, G, ws + sp.wpart, s))) return rc;
+    }
+    if ((rc = launch_sparse_bmat(h, G, ws + sp.wpart, noise, M, D, h->gram.p, ws + sp.w, s))) return rc;
+    if ((rc = factor())) return rc;
+    // tail: beta_eff = Yu^T Yb^T Yb w / n;  S = I - Yb^T Yb;  R = S Yu;  iK_eff = Yu^T R;  T
+    if ((rc = launch_sparse_beta(h, ws + sp.yu, h->linv.p, ws + sp.w, noise, M, D, h->zvec.p, h->kv.p, h->beta.p, s))) return rc;
+    if ((rc = launch_sparse_atb_sym(h, h->linv.p, h->linv.p, M, D, h->gram.p, true, s))) return rc;
+    hipLaunchKernelGGL(gemm_nn_tiled_kernel, dim3((M + TS - 1) / TS, (M + TS - 1) / TS, D), dim3(256), 0, s, h->gram.p, M, NNm,
+                       ws + sp.yu, M, NNm, ws + sp.r, M, NNm, M, M, M, 1.0, 1, 0);
+    if ((rc = launch_sparse_atb_sym(h, ws + sp.yu, ws + sp.r, M, D, h->iK.p, false, s))) return rc;
+    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
+    h->N = M; h->D = D; h->E = E; h->ready = true;
+    h->inc_updates = 0;                                            // no (X, Y) record: a later gpmpc_prepare factorises in full
     return GPMPC_OK;
 }
 

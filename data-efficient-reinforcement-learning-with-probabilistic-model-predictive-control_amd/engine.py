@@ -119,6 +119,31 @@ class HipEngine:
                                            nz.data_ptr(), N, D, E, self._stream()))
         self.N, self.D, self.E = N, D, E
 
+    def prepare_sparse(self, X, Y, Z, lengthscales, outputscales, noises, jitter_rel=1e-6):
+        """A sparse GP (DTC / projected process) of the memory (X (N, E), Y (N, D)) on the inducing inputs Z (M, E)
+        (gpmpc_prepare_sparse): afterwards the engine holds an M-point model -- `factors()` returns iK_eff (D, M, M) and
+        beta_eff (D, M), and predict, moments, the rollouts, their gradients and the searches run on it unchanged at the cost of
+        an M-point memory.  `jitter_rel` times the outputscale goes on the diagonal of k(Z, Z).  There is no (X, Y) record:
+        `forget` raises GpmpcError(GPMPC_ERR_ARG) and the next `prepare` factorises in full.  `last_prepare_mode` is 4.
+        Synchronises the current stream."""
+        X = self._dev(X)
+        N, E = X.shape
+        Y = self._dev(Y)
+        D = Y.shape[1]
+        if Y.shape[0] != N:
+            raise ValueError(f"expected targets of shape ({N}, D), got {tuple(Y.shape)}")
+        Z = self._dev(Z)
+        if Z.dim() != 2 or Z.shape[1] != E:
+            raise ValueError(f"expected inducing inputs of shape (M, {E}), got {tuple(Z.shape)}")
+        M = Z.shape[0]
+        ls = self._dev(lengthscales, (D, E))
+        osc = self._dev(outputscales).reshape(D)
+        nz = self._dev(noises).reshape(D)
+        self._keep = (X, Y, Z, ls, osc, nz)
+        self._check(self.lib.gpmpc_prepare_sparse(self._h, X.data_ptr(), Y.data_ptr(), N, Z.data_ptr(), M, ls.data_ptr(),
+                                                  osc.data_ptr(), nz.data_ptr(), float(jitter_rel), D, E, self._stream()))
+        self.N, self.D, self.E = M, D, E
+
     def mll(self, X, Y, lengthscales, outputscales, noises):
         """Training loss of the D GPs and its gradient (gp_model.py:262-275): dict(loss (D,), d_lengthscale (D,E),
         d_outputscale (D,), d_noise (D,)) as numpy arrays.  Replaces the cached factors of this engine."""
@@ -153,7 +178,8 @@ class HipEngine:
 
     @property
     def last_prepare_mode(self):
-        """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit, 3 = downdate (`forget`)."""
+        """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit, 3 = downdate (`forget`),
+        4 = sparse model (`prepare_sparse`)."""
         return int(self.lib.gpmpc_last_prepare_mode(self._h))
 
     @property

@@ -43,7 +43,8 @@ const char* gpmpc_last_error(const gpmpc_t* h);
  *   X_dev (N,E)  Y_dev (N,D)  lengthscales_dev (D,E)  outputscales_dev (D)  noises_dev (D)
  * Synchronises `stream` (a failed factorisation is reported here: GPMPC_ERR_NOT_PD).  Reuse across control steps (the reference
  * refactorises every step, gp_mpc_controller.py:117): gpmpc_last_prepare_mode = 0 full factorisation, 1 border update (the
- * cached memory plus <= 8 appended points, same hyper-parameters), 2 cache hit, 3 downdate (gpmpc_forget).
+ * cached memory plus <= 8 appended points, same hyper-parameters), 2 cache hit, 3 downdate (gpmpc_forget), 4 sparse model
+ * (gpmpc_prepare_sparse).
  */
 int gpmpc_prepare(gpmpc_t* h, const double* X_dev, const double* Y_dev, const double* lengthscales_dev,
                   const double* outputscales_dev, const double* noises_dev, int N, int D, int E, void* stream);
@@ -67,6 +68,32 @@ int gpmpc_last_prepare_mode(gpmpc_t* h);
  * repeated.  GPMPC_ERR_NOT_PD and GPMPC_ERR_HIP leave no model, as after a failed gpmpc_prepare: prepare again.
  */
 int gpmpc_forget(gpmpc_t* h, const int* idx_host, int k, void* stream);
+
+/*
+ * gpmpc_prepare_sparse: a sparse GP on M inducing inputs Z in place of the exact one on all N memory points (the reference has
+ * no counterpart; PILCO, the method it follows, ships one for the same reason).  DTC / projected-process form (Quinonero-Candela
+ * & Rasmussen 2005, section 5; Seeger et al. 2003): it predicts with the formulas of an exact GP whose memory is Z and whose
+ * factors are iK_eff (D,M,M), beta_eff (D,M), so every other entry point runs on it unchanged at the cost of an M-point memory.
+ *   X_dev (N,E)  Y_dev (N,D)  Z_dev (M,E)  lengthscales_dev (D,E)  outputscales_dev (D)  noises_dev (D)  (as in gpmpc_prepare)
+ * Per output a (sigma2_a, n_a: outputscale and noise), in this order of operations:
+ *   Kuu = k_a(Z, Z) + jitter_rel sigma2_a I,  Lu = chol(Kuu),  Yu = Lu^-1
+ *   V   = Yu k_a(Z, X)                          (M x N: exists one chunk of points at a time)
+ *   B   = I + V V^T / n_a,  w = V y_a,  LB = chol(B),  Yb = LB^-1
+ *   beta_eff = Yu^T Yb^T Yb w / n_a,   iK_eff = Yu^T (I - Yb^T Yb) Yu    (the bracket first; exactly symmetric)
+ * so that the mean is k_a(x, Z) beta_eff and the variance sigma2_a - k_a(x, Z) iK_eff k_a(Z, x), the DTC variance (>= 0 in exact
+ * arithmetic, not clamped).  Each point's column is whitened before the rank update: the textbook form Kuu^-1 - (Kuu + Kuf Kfu /
+ * n)^-1 loses 5 to 9 more digits of the mean at the same sizes.  Nothing of size N x N or M x N is allocated: the
+ * workspace is O(D M^2) plus one chunk of points within 64 MB (option "sparse_chunk_points": 0 auto, else a multiple of 64; every
+ * output bit is the same whatever it is, and every sum runs in an order fixed by N, M, D and E alone).  N < M is legal.
+ * Afterwards the handle is exactly in the state gpmpc_set_factors(Z, iK_eff, beta_eff, ..., N := M) would leave: no (X, Y) record,
+ * so gpmpc_forget answers GPMPC_ERR_ARG and a later gpmpc_prepare is a full factorisation; gpmpc_last_prepare_mode = 4.
+ * Synchronises `stream`.  GPMPC_ERR_ARG, with the cached model untouched: a NULL pointer, N < 1, M < 1, jitter_rel negative or not
+ * finite; GPMPC_ERR_LIMIT: D or E beyond the compiled limits; GPMPC_ERR_NOT_PD: a lost pivot in either Cholesky -- it leaves no
+ * model, as after a failed gpmpc_prepare.
+ */
+int gpmpc_prepare_sparse(gpmpc_t* h, const double* X_dev, const double* Y_dev, int N, const double* Z_dev, int M,
+                         const double* lengthscales_dev, const double* outputscales_dev, const double* noises_dev,
+                         double jitter_rel, int D, int E, void* stream);
 
 /* Training objective: per GP -log p(y_a | X, theta_a) / N and its gradient wrt lengthscales, outputscale and
  * noise -- what gpytorch's ExactMarginalLogLikelihood + autograd give the reference's LBFGS loop (gp_model.py:262-275).
@@ -260,7 +287,8 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
- * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto).
+ * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
+ * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64).
  * Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */

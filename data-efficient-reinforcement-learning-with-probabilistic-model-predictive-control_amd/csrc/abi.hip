@@ -55,7 +55,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 20; }
+int gpmpc_abi_version(void) { return 21; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -768,7 +768,24 @@ int gpmpc_argmin_async(gpmpc_t* g, const double* J, int B, long long first, cons
     if (!g || !J || !out_dev || B < 1 || first < 0 || HA < 0) return bad(g, "bad argument");
     Handle* h = H_(g);
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return launch_argmin_to(h, J, B, first, actions, HA, out_dev, (hipStream_t)stream);
+    return launch_argmin_to(h, J, B, first, actions, HA, out_dev, nullptr, (hipStream_t)stream);
+}
+
+int gpmpc_argmin_export(gpmpc_t* g, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
+                        double* out_host, void* stream) {
+    Range roctx_range("gpmpc_argmin_export");
+    if (!g || !J || !out_dev || !out_host || B < 1 || first < 0 || HA < 0) return bad(g, "bad argument");
+    Handle* h = H_(g);
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    // out_host must be pinned host memory this device can address: the kernel stores the record there itself
+    hipPointerAttribute_t attr;
+    void* dev_view = nullptr;
+    if (hipPointerGetAttributes(&attr, out_host) != hipSuccess || attr.type != hipMemoryTypeHost ||
+        hipHostGetDevicePointer(&dev_view, out_host, 0) != hipSuccess || !dev_view) {
+        (void)hipGetLastError();         // the query's own error must not stay behind as the runtime's last error
+        return bad(g, "out_host must be pinned (page-locked, device-mapped) host memory");
+    }
+    return launch_argmin_to(h, J, B, first, actions, HA, out_dev, static_cast<double*>(dev_view), (hipStream_t)stream);
 }
 
 }  // extern "C"

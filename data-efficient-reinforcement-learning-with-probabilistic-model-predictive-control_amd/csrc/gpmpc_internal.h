@@ -477,7 +477,7 @@ int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t
 int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s,          // grad_wide.hip: 8 < D <= 16
                              const RolloutSeeds* seeds = nullptr);
 int launch_argmin_to(Handle* h, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
-                     hipStream_t s);
+                     double* out_host, hipStream_t s);     // out_host: device address of pinned host memory, or NULL
 // prepare.hip (allow_reuse = false: a full factorisation even where the cached factors could be reused or border-updated)
 void plan_prepare(const Handle& h, int N, PreparePlan& p);
 int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, const double* os,

@@ -46,8 +46,8 @@ __global__ __launch_bounds__(NT) void few_candidate_moments_kernel(const GradArg
         return;
     }
     if (blockIdx.x != 0 || threadIdx.x >= 64) return;
-    traj_cost_body(blockIdx.y, threadIdx.x, p.mu, p.Sig, p.actions, cs.cost, p.D, p.A, p.H, cs.kappa, cs.clip, cs.use_constraints,
-                   cs.cm, cs.cv, cs.J);
+    traj_cost_body<DP>(blockIdx.y, threadIdx.x, p.mu, p.Sig, p.actions, cs.cost, p.D, p.A, p.H, cs.kappa, cs.clip, cs.use_constraints,
+                       cs.cm, cs.cv, cs.J);
 }
 
 // (cs.cost NULL: no stage costs are wanted -- the grid stops before the cost slice)

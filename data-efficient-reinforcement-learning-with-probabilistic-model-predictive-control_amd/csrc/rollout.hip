@@ -25,45 +25,63 @@ __global__ __launch_bounds__(64) void traj_cost_kernel(const double* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
-// Keep-the-best rule of gp_mpc_controller.py:146-148 over a vector (single workgroup).
+// Keep-the-best rule of gp_mpc_controller.py:146-148 over a vector (single workgroup of 64 * ceil(B / 64) threads, 1024 at most).
+// The J[0] of the NaN rule is loaded first, beside the scan's loads; every wavefront folds the per-wave results itself (a second
+// butterfly over the <= 16 entries instead of a serial scan by thread 0 and a second barrier; one wavefront needs no LDS at all),
+// so every thread knows the winner and gathers its sequence at once.  `out_host` (NULL: none) = pinned host memory the device
+// can address: the record goes there too, followed by a system-scope fence -- no separate device-to-host copy.
+__device__ __forceinline__ void keep_better(double& bv, long long& bi, double ov, long long oi) {
+    if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+}
+
 __global__ __launch_bounds__(1024) void argmin_kernel(const double* J, int B, long long first, double* out, int index_as_double,
-                                                     const double* actions, int HA) {
-    __shared__ long long s_best;
+                                                     const double* actions, int HA, double* out_host) {
     __shared__ double s_v[16];
     __shared__ long long s_i[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nt = blockDim.x, nw = nt >> 6;
+    const double j0 = B > 0 ? J[0] : 0.0;
     double bv = INFINITY;
     long long bi = -1;
-    for (int i = tid; i < B; i += 1024) {
+    for (int i = tid; i < B; i += nt) {
         const double v = J[i];
         if (v < bv) { bv = v; bi = i; }          // strided scan keeps the lowest index per thread
     }
     for (int off = 32; off >= 1; off >>= 1) {
         const double ov = __shfl_xor(bv, off, 64);
         const long long oi = __shfl_xor(bi, off, 64);
-        if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+        keep_better(bv, bi, ov, oi);
     }
-    if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; ++w) {
-            const double ov = s_v[w];
-            const long long oi = s_i[w];
-            if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    if (nw > 1) {
+        if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
+        __syncthreads();
+        bv = lane < nw ? s_v[lane] : INFINITY;
+        bi = lane < nw ? s_i[lane] : -1;
+        for (int off = 8; off >= 1; off >>= 1) {
+            const double ov = __shfl_xor(bv, off, 64);
+            const long long oi = __shfl_xor(bi, off, 64);
+            keep_better(bv, bi, ov, oi);
         }
-        if (first == 0 && B > 0 && J[0] != J[0]) { bv = J[0]; bi = 0; }   // NaN in global slot 0 is adopted and stays
-        if (bi < 0) bv = INFINITY;                              // nothing selectable in this shard
-        out[0] = bv;
+        bv = __shfl(bv, 0, 64);                  // (lanes 16.. hold another group's fold)
+        bi = __shfl(bi, 0, 64);
+    }
+    if (first == 0 && B > 0 && j0 != j0) { bv = j0; bi = 0; }   // NaN in global slot 0 is adopted and stays
+    if (bi < 0) bv = INFINITY;                                  // nothing selectable in this shard
+    if (tid == 0) {
         const long long gi = (bi < 0) ? -1 : bi + first;
+        out[0] = bv;
         if (index_as_double) out[1] = (double)gi;
         else reinterpret_cast<long long*>(out)[1] = gi;
-        s_best = bi < 0 ? 0 : bi;
+        if (out_host) { out_host[0] = bv; out_host[1] = (double)gi; }
     }
     if (actions) {                      // append the winner's action sequence to the record
-        __syncthreads();
-        const long long w = s_best;
-        for (int k = tid; k < HA; k += 1024) out[2 + k] = actions[w * HA + k];
+        const long long w = bi < 0 ? 0 : bi;
+        for (int k = tid; k < HA; k += nt) {
+            const double v = actions[w * HA + k];
+            out[2 + k] = v;
+            if (out_host) out_host[2 + k] = v;
+        }
     }
+    if (out_host) __threadfence_system();
 }
 
 // Zeroes an exchange buffer of the cooperative form with WRITE-THROUGH (agent-scope, sc1) stores: every later write to these
@@ -93,9 +111,15 @@ int launch_traj_cost(Handle* h, const RolloutArgs& a, double* cm, double* cv, do
     return GPMPC_OK;
 }
 
+// only the wavefronts B needs (1 .. 16)
+static inline int argmin_threads(int B) {
+    const int w = (B + 63) / 64;
+    return 64 * (w < 1 ? 1 : w > 16 ? 16 : w);
+}
+
 int launch_argmin_to(Handle* h, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
-                     hipStream_t s) {
-    hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(1024), 0, s, J, B, first, out_dev, 1, actions, HA);
+                     double* out_host, hipStream_t s) {
+    hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(argmin_threads(B)), 0, s, J, B, first, out_dev, 1, actions, HA, out_host);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     return GPMPC_OK;
 }
@@ -103,7 +127,8 @@ int launch_argmin_to(Handle* h, const double* J, int B, long long first, const d
 int launch_argmin(Handle* h, const double* J, int B, long long first, hipStream_t s) {
     int rc = grow(h, h->best, 2);
     if (rc) return rc;
-    hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(1024), 0, s, J, B, first, h->best.p, 0, (const double*)nullptr, 0);
+    hipLaunchKernelGGL(argmin_kernel, dim3(1), dim3(argmin_threads(B)), 0, s, J, B, first, h->best.p, 0, (const double*)nullptr, 0,
+                       (double*)nullptr);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     return GPMPC_OK;
 }

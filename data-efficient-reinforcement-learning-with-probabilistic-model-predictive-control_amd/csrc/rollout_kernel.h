@@ -1855,11 +1855,14 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
 // ------------------------------------------------------------------------------------------
 // Stage / terminal costs and the mean-LCB objective of one candidate from the stored trajectory (one wavefront, lanes over the
 // H + 1 time steps): the body of traj_cost_kernel (rollout.hip) and of the cost slice of the few-candidate gradient launch.
-__device__ __forceinline__ void traj_cost_body(int c, int lane, const double* __restrict__ mu, const double* __restrict__ Sig,
-                                                       const double* __restrict__ actions, const double* __restrict__ cost,
-                                                       int D, int A, int H, double kappa, int clip, int use_constraints,
-                                                       double* __restrict__ cm_out, double* __restrict__ cv_out,
-                                                       double* __restrict__ J_out) {
+//
+// traj_cost_generic: any D, A.  Every operand is a global load inside run-time loops (a few hundred dependent L1/L2 round trips
+// per lane): the fallback of the shapes traj_cost_fixed does not cover.
+__device__ __forceinline__ void traj_cost_generic(int c, int lane, const double* __restrict__ mu, const double* __restrict__ Sig,
+                                                          const double* __restrict__ actions, const double* __restrict__ cost,
+                                                          int D, int A, int H, double kappa, int clip, int use_constraints,
+                                                          double* __restrict__ cm_out, double* __restrict__ cv_out,
+                                                          double* __restrict__ J_out) {
     const int DA = D + A;
     const double* target = cost;
     const double* W = cost + DA;
@@ -1915,6 +1918,125 @@ __device__ __forceinline__ void traj_cost_body(int c, int lane, const double* __
     // fixed-order sum over lanes (lane l holds steps l, l + 64, ...)
     jsum = wave_xor_sum(jsum);
     if (lane == 0 && J_out) J_out[c] = jsum / (double)(H + 1);
+}
+
+// The four quadratic terms of one step from registers: Wm is the (N, N) weight (N = D: terminal, N = D + A: stage), e the N
+// errors, S the (D, D) covariance.  The loops are those of traj_cost_generic with n = N, in the same order, so every
+// accumulator sees the same operations and the results keep their bits.
+template <int D, int N>
+__device__ __forceinline__ void stage_cost_terms(const double* S, const double* e, const double* Wm, double& cm_out, double& cv_out) {
+    double cm = 0.0, cv = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) cm = fma(S[i * D + j], Wm[j * N + i], cm);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double ei = e[i];
+#pragma unroll
+        for (int j = 0; j < N; ++j) cm = fma(ei * Wm[i * N + j], e[j], cm);
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            double tij = 0.0, tji = 0.0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                tij = fma(Wm[i * N + k], S[k * D + j], tij);
+                tji = fma(Wm[j * N + k], S[k * D + i], tji);
+            }
+            cv = fma(2.0 * tij, tji, cv);
+            double v1 = 0.0, v2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                v1 = fma(e[k], Wm[k * N + i], v1);
+                v2 = fma(Wm[j * N + k], e[k], v2);
+            }
+            cv = fma(4.0 * v1 * S[i * D + j], v2, cv);
+        }
+    cm_out = cm;
+    cv_out = cv;
+}
+
+// traj_cost_fixed: compile-time D <= 4, A <= 2.  The wave-uniform operands (target, W, W_T, s_min, s_max) and the step's own
+// (Sigma_t, mu_t, a_t) are loaded ONCE, all loads in flight together, and the arithmetic runs from registers: one memory round
+// trip per lane and trip instead of a few hundred.  Same operations in the same order as traj_cost_generic.
+template <int D, int A>
+__device__ __forceinline__ void traj_cost_fixed(int c, int lane, const double* __restrict__ mu, const double* __restrict__ Sig,
+                                                        const double* __restrict__ actions, const double* __restrict__ cost,
+                                                        int H, double kappa, int clip, int use_constraints,
+                                                        double* __restrict__ cm_out, double* __restrict__ cv_out,
+                                                        double* __restrict__ J_out) {
+    constexpr int DA = D + A;
+    double target[DA], W[DA * DA], WT[D * D], smin[D], smax[D];
+#pragma unroll
+    for (int i = 0; i < DA; ++i) target[i] = cost[i];
+#pragma unroll
+    for (int i = 0; i < DA * DA; ++i) W[i] = cost[DA + i];
+#pragma unroll
+    for (int i = 0; i < D * D; ++i) WT[i] = cost[DA + DA * DA + i];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        smin[d] = cost[DA + DA * DA + D * D + d];            // (gpmpc_set_cost always writes both rows: zeros without constraints)
+        smax[d] = cost[DA + DA * DA + D * D + D + d];
+    }
+    double jsum = 0.0;
+    for (int t = lane; t <= H; t += 64) {
+        const bool terminal = (t == H);
+        const double* mp = mu + ((size_t)c * (H + 1) + t) * D;
+        const double* Sp = Sig + ((size_t)c * (H + 1) + t) * D * D;
+        const double* ap = actions + ((size_t)c * H + (terminal ? 0 : t)) * A;
+        double S[D * D], m[D], e[DA];
+#pragma unroll
+        for (int i = 0; i < D * D; ++i) S[i] = Sp[i];
+#pragma unroll
+        for (int i = 0; i < D; ++i) m[i] = mp[i];
+#pragma unroll
+        for (int i = 0; i < A; ++i) e[D + i] = (terminal ? 0.0 : ap[i]) - target[D + i];   // (the terminal step has no action)
+#pragma unroll
+        for (int i = 0; i < D; ++i) e[i] = m[i] - target[i];
+        double cm, cv;
+        if (terminal) stage_cost_terms<D, D>(S, e, WT, cm, cv);
+        else stage_cost_terms<D, DA>(S, e, W, cm, cv);
+        if (use_constraints && !terminal) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const double sg = S[d * D + d];              // the reference passes the VARIANCE as sigma (:63-64)
+                cm += 0.5 * (1.0 + erf((smin[d] - m[d]) / (sg * 1.4142135623730951)))
+                    + (1.0 - 0.5 * (1.0 + erf((smax[d] - m[d]) / (sg * 1.4142135623730951))));
+            }
+        }
+        double ucb = -cm + kappa * sqrt(cv);
+        if (clip) ucb = fmin(ucb, 0.0);
+        jsum -= ucb;
+        if (cm_out) cm_out[(size_t)c * (H + 1) + t] = cm;
+        if (cv_out) cv_out[(size_t)c * (H + 1) + t] = cv;
+    }
+    // fixed-order sum over lanes (lane l holds steps l, l + 64, ...)
+    jsum = wave_xor_sum(jsum);
+    if (lane == 0 && J_out) J_out[c] = jsum / (double)(H + 1);
+}
+
+// ONE body for both callers.  DPAD: 0 = any D (traj_cost_kernel); the padded state dimension of a gradient instantiation
+// (2: D <= 2, 3: D = 3, 4: D = 4) keeps only the register forms that instantiation can meet.
+template <int DPAD = 0>
+__device__ __forceinline__ void traj_cost_body(int c, int lane, const double* __restrict__ mu, const double* __restrict__ Sig,
+                                                       const double* __restrict__ actions, const double* __restrict__ cost,
+                                                       int D, int A, int H, double kappa, int clip, int use_constraints,
+                                                       double* __restrict__ cm_out, double* __restrict__ cv_out,
+                                                       double* __restrict__ J_out) {
+#define GPMPC_COST_FIXED(d, a)                                                                                                    \
+    if constexpr (DPAD == 0 || (DPAD == 2 ? (d) <= 2 : (d) == DPAD)) {                                                            \
+        if (D == (d) && A == (a)) {                                                                                               \
+            traj_cost_fixed<d, a>(c, lane, mu, Sig, actions, cost, H, kappa, clip, use_constraints, cm_out, cv_out, J_out);       \
+            return;                                                                                                               \
+        }                                                                                                                         \
+    }
+    GPMPC_COST_FIXED(1, 1) GPMPC_COST_FIXED(1, 2) GPMPC_COST_FIXED(2, 1) GPMPC_COST_FIXED(2, 2)
+    GPMPC_COST_FIXED(3, 1) GPMPC_COST_FIXED(3, 2) GPMPC_COST_FIXED(4, 1) GPMPC_COST_FIXED(4, 2)
+#undef GPMPC_COST_FIXED
+    traj_cost_generic(c, lane, mu, Sig, actions, cost, D, A, H, kappa, clip, use_constraints, cm_out, cv_out, J_out);
 }
 
 }  // namespace gpmpc_hip

@@ -776,16 +776,29 @@ class HipEngine:
                                              state.data_ptr(), self._stream()))
 
     # -- a8 ----------------------------------------------------------------------------
-    def argmin_async(self, J, first_global_index=0, actions=None, out=None):
+    # sharding.select_best_async looks for this attribute: argmin_async can deliver the record to pinned host memory itself
+    argmin_exports_host = True
+
+    def argmin_async(self, J, first_global_index=0, actions=None, out=None, host_out=None):
         """Device-side keep-the-best, no host synchronisation: returns the device record
-        [best J, global index as double (-1: none), winning action sequence (H*A values, if `actions` given)]."""
+        [best J, global index as double (-1: none), winning action sequence (H*A values, if `actions` given)].
+        `host_out`: a pinned float64 host tensor of the record's length; the kernel stores the record there as well
+        (gpmpc_argmin_export) -- complete once the stream has passed the launch, no copy behind it."""
         J = self._dev(J)
         ha = 0 if actions is None else int(actions[0].numel())
         if out is None:
             out = torch.empty(2 + ha, dtype=torch.float64, device=self.device)
-        self._check(self.lib.gpmpc_argmin_async(self._h, J.data_ptr(), J.numel(), int(first_global_index),
-                                                None if actions is None else actions.data_ptr(), ha,
-                                                out.data_ptr(), self._stream()))
+        if host_out is None:
+            self._check(self.lib.gpmpc_argmin_async(self._h, J.data_ptr(), J.numel(), int(first_global_index),
+                                                    None if actions is None else actions.data_ptr(), ha,
+                                                    out.data_ptr(), self._stream()))
+            return out
+        if (host_out.device.type != "cpu" or host_out.dtype != torch.float64 or not host_out.is_contiguous()
+                or host_out.numel() != 2 + ha or not host_out.is_pinned()):
+            raise ValueError("host_out must be a pinned contiguous float64 host tensor of 2 + H*A elements")
+        self._check(self.lib.gpmpc_argmin_export(self._h, J.data_ptr(), J.numel(), int(first_global_index),
+                                                 None if actions is None else actions.data_ptr(), ha,
+                                                 out.data_ptr(), host_out.data_ptr(), self._stream()))
         return out
 
     def argmin(self, J, first_global_index=0):

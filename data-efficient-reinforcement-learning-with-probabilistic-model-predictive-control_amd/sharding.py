@@ -239,10 +239,21 @@ def select_best_async(engine, J, actions_local, lo, num_candidates, group=None, 
       "host"      = the copy carries this rank's record only and the records are exchanged between the hosts (gloo) when the
                     result is read (PendingBest.result) -- the fallback when no xGMI collective is wanted.
     `host_buffer` / `record`: reusable pinned / device buffers of a previous call with the same shapes.
+    Without an active process group, an engine with `argmin_exports_host` lets the kernel write the record to `host_buffer`
+    directly (no copy is enqueued); engines without that attribute take the copy.
     Returns a PendingBest."""
     n, H, A = actions_local.shape
-    rec = _local_record(engine, J, actions_local, lo, out=record)
     multi = _active(group)
+    if (not multi and n > 0 and actions_local.device.type == "cuda" and getattr(engine, "argmin_exports_host", False)):
+        # one rank, nothing to exchange: the keep-the-best kernel stores the record to the pinned buffer itself -- no copy
+        # launch behind it; the event still marks the point where the host may read
+        if host_buffer is None or host_buffer.numel() != 2 + H * A:
+            host_buffer = torch.empty(2 + H * A, dtype=torch.float64, pin_memory=True)
+        rec = engine.argmin_async(J, first_global_index=lo, actions=actions_local, out=record, host_out=host_buffer)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(rec.device))
+        return PendingBest(host_buffer, ev, 1, H, A, rec)
+    rec = _local_record(engine, J, actions_local, lo, out=record)
     if exchange == "host" and multi:
         world = dist.get_world_size(group)
         xg = host_group(group)

@@ -549,12 +549,18 @@ int gpmpc_objective_grad_host(gpmpc_t* h, const double* actions_host, const doub
  * J_dev[0] (the shard offset when candidates are sharded over GPUs); the returned index is global; nothing selectable: index -1,
  * J = +inf.  gpmpc_argmin synchronises and writes HOST memory; gpmpc_argmin_async does not: it writes the device record
  * out_dev[0] = best J, [1] = (double) global index, [2 .. 2+HA) = the winning sequence when actions_dev (B,HA) is given -- ready
- * to be all-gathered over RCCL as is (the ONE exchange of a sharded control step).
+ * to be all-gathered over RCCL as is (the ONE exchange of a sharded control step).  gpmpc_argmin_export is gpmpc_argmin_async
+ * whose kernel ALSO stores the same record to out_host (2 + HA doubles of PINNED host memory this device can address, e.g.
+ * hipHostMalloc / a pinned torch tensor) and fences at system scope: the single-GPU step needs no device-to-host copy behind it
+ * (gp_mpc_controller.py:146-148 reads the winner on the host).  The record is complete once the stream has passed the call (wait
+ * for an event recorded behind it); any other kind of out_host pointer is GPMPC_ERR_ARG.
  */
 int gpmpc_argmin(gpmpc_t* h, const double* J_dev, int B, long long first_global_index, double* best_J_host,
                  long long* best_idx_host, void* stream);
 int gpmpc_argmin_async(gpmpc_t* h, const double* J_dev, int B, long long first_global_index, const double* actions_dev, int HA,
                        double* out_dev, void* stream);
+int gpmpc_argmin_export(gpmpc_t* h, const double* J_dev, int B, long long first_global_index, const double* actions_dev, int HA,
+                        double* out_dev, double* out_host, void* stream);
 
 /*
  * Candidate optimisation whose loop stays on the device (replaces B sequential scipy restarts, gp_mpc_controller.py:125-141, by a

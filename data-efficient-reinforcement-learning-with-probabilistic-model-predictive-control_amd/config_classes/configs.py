@@ -152,18 +152,24 @@ def _with_time_column(ls, ls_time, num_models, num_inputs):
 
 
 UNCERTAINTY_PROPAGATIONS = ("moment_matching", "linearized")
+INDUCING_SELECTIONS = ("strided", "greedy")
 
 
 class ModelConfig:
     def __init__(self, gp_init=None, init_lengthscale_time=100, min_std_noise=1e-3, max_std_noise=3e-1,
                  min_outputscale=1e-5, max_outputscale=0.95, min_lengthscale=4e-3, max_lengthscale=25.0,
                  min_lengthscale_time=10, max_lengthscale_time=10000, include_time_model=False,
-                 uncertainty_propagation="moment_matching", num_inducing_points=None, inducing_jitter=1e-6):
+                 uncertainty_propagation="moment_matching", num_inducing_points=None, inducing_jitter=1e-6,
+                 inducing_selection="strided"):
         """num_inducing_points: None (the exact GP on the whole memory), or M >= 1 -- once the memory holds more than M points
         the model predicts with a sparse GP (DTC / projected process, gpmpc_prepare_sparse) on M inducing inputs, the rows
         round(i (N - 1) / (M - 1)), i = 0..M-1, of the N-point memory (M = 1: row 0): every prediction, rollout and gradient
         then costs what an M-point memory costs while all N points shape the model.  Training stays the exact marginal
         likelihood on the whole memory.  inducing_jitter: times the outputscale, added to the diagonal of k(Z, Z).
+        inducing_selection: which M memory points those are -- "strided" (the rows above: they ignore the data and the kernel)
+        or "greedy" (gpmpc_select_inducing, chosen afresh on the device at every prepare_inference: each pick is the point
+        the inducing set so far explains worst under the current hyper-parameters, so a memory clustered round the setpoint
+        keeps its few exploratory points).
         uncertainty_propagation: how an uncertain state goes through the GP -- "moment_matching" (the reference's exact
         moment matching, gp_model.py:112-180) or "linearized" (first-order Taylor propagation at the input mean,
         gpmpc_moments_linear / gpmpc_rollout_linear: no D^2 pair pass, but a different approximation)."""
@@ -177,6 +183,9 @@ class ModelConfig:
         if not (float(inducing_jitter) >= 0.0 and float(inducing_jitter) < float("inf")):
             raise ValueError(f"ModelConfig.inducing_jitter={inducing_jitter!r}: a finite number >= 0")
         self.inducing_jitter = float(inducing_jitter)
+        if inducing_selection not in INDUCING_SELECTIONS:
+            raise ValueError(f"ModelConfig.inducing_selection must be one of {INDUCING_SELECTIONS}, got {inducing_selection!r}")
+        self.inducing_selection = inducing_selection
         if gp_init is None:
             gp_init = {"noise_covar.noise": [1e-4] * 3, "base_kernel.lengthscale": [[0.75] * 4] * 3,
                        "outputscale": [5e-2] * 3}

@@ -332,6 +332,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self.y_mem = None
         self._cost_key = None
         self.is_sparse = False          # the cached model is the sparse one of gpmpc_prepare_sparse
+        self.inducing_idx = None        # rows of the memory its inducing inputs are: a list (strided), a device tensor (greedy), or None
 
     last_training_launches = None       # gpmpc_mll calls of the last `train` in this process (lockstep: ~ the longest GP's count)
 
@@ -368,14 +369,24 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         """Cache the model of the memory (inputs (N, E), state_changes (N, D)).  With ModelConfig.num_inducing_points = M and
         more than M memory points -- or with explicit `inducing_inputs` (M', E), which override the choice below -- the cached
         model is the sparse GP of gpmpc_prepare_sparse on the inducing inputs: the rows round(i (N - 1) / (M - 1)), i = 0..M-1,
-        of `inputs` (M = 1: row 0), a deterministic spread over the memory in its order.  Otherwise (the option unset, or
-        N <= M) it is the exact GP, as ever.  x_mem / y_mem are the whole memory either way: training and save_state see all
-        of it."""
+        of `inputs` (M = 1: row 0), a deterministic spread over the memory in its order -- or, with
+        ModelConfig.inducing_selection = "greedy", the M rows gpmpc_select_inducing picks under the current hyper-parameters,
+        chosen afresh at every call (nothing is cached that training or a memory change could make stale) and handed to
+        gpmpc_prepare_sparse on the device.  Otherwise (the option unset, or N <= M) it is the exact GP, as ever.
+        `inducing_idx` records the chosen rows: a list (strided), an int32 device tensor (greedy), None otherwise.  x_mem /
+        y_mem are the whole memory either way: training and save_state see all of it."""
         self.x_mem = inputs
         self.y_mem = state_changes
+        self.inducing_idx = None
         M = getattr(self.config, "num_inducing_points", None)
         if inducing_inputs is None and M is not None and len(inputs) > M:
-            inducing_inputs = _t(inputs)[inducing_rows(len(inputs), M)]
+            if getattr(self.config, "inducing_selection", "strided") == "greedy":
+                sel = self.engine.select_inducing(inputs, M, self.lengthscales, self.variances,
+                                                  getattr(self.config, "inducing_jitter", 1e-6))
+                self.inducing_idx, inducing_inputs = sel["idx"], sel["Z"]
+            else:
+                self.inducing_idx = inducing_rows(len(inputs), M)
+                inducing_inputs = _t(inputs)[self.inducing_idx]
         self.is_sparse = inducing_inputs is not None
         if self.is_sparse:
             self.engine.prepare_sparse(inputs, state_changes, inducing_inputs, self.lengthscales, self.variances, self.noises,
@@ -585,7 +596,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                           parameters=[m.state_dict() for m in self.models],
                           constraints_hyperparams={k: v for k, v in vars(self.config).items()
                                                    if k not in ("gp_init", "uncertainty_propagation", "num_inducing_points",
-                                                                "inducing_jitter")})
+                                                                "inducing_jitter", "inducing_selection")})
 
     def load_state(self, saved_state):
         for m, p in zip(self.models, saved_state.parameters):

@@ -55,7 +55,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 21; }
+int gpmpc_abi_version(void) { return 22; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -83,7 +83,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->selws};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -156,6 +156,10 @@ int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
         if (value < 0 || value > (1 << 24) || (value & 63)) { h->err = "sparse_chunk_points: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
         h->opt_sparse_chunk = (int)value;
     }
+    else if (!strcmp(name, "select_inducing_max_mb")) {
+        if (value < 1) { h->err = "select_inducing_max_mb: a number of MiB >= 1"; return GPMPC_ERR_ARG; }
+        h->opt_select_max_mb = value;
+    }
     else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
     else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
     else if (!strcmp(name, "grad_separable")) h->opt_grad_sep = (int)value;
@@ -210,6 +214,19 @@ int gpmpc_prepare_sparse(gpmpc_t* g, const double* X, const double* Y, int N, co
     if (rc) return rc;
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
     return run_prepare_sparse(H_(g), X, Y, N, Z, M, ls, os, noise, jitter_rel, D, E, (hipStream_t)stream);
+}
+
+int gpmpc_select_inducing(gpmpc_t* g, const double* X, int N, int M, const double* ls, const double* os, double jitter_rel, int D,
+                          int E, int* idx_out, double* Z_out, double* trace_out, void* stream) {
+    Range roctx_range("gpmpc_select_inducing");
+    if (!g || !X || !ls || !os || !idx_out) return bad(g, "null argument");
+    if (N < 1) return bad(g, "select_inducing: need N >= 1 memory points");
+    if (M < 1 || M > N) return bad(g, "select_inducing: need 1 <= M <= N inducing inputs");
+    if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return bad(g, "select_inducing: jitter_rel must be finite and >= 0");
+    int rc = check_dims(g, N, D, E);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_select_inducing(H_(g), X, N, M, ls, os, jitter_rel, D, E, idx_out, Z_out, trace_out, (hipStream_t)stream);
 }
 
 int gpmpc_set_factors(gpmpc_t* g, const double* X, const double* iK, const double* beta, const double* ls,

@@ -230,6 +230,7 @@ struct Handle {
     Buf Xf, Yf;   // (N, E), (N, D): trade places with Xc / Yc
     Buf fgws;
     Buf spws;     // gpmpc_prepare_sparse: Yu | R | partial sums of w | w | jitter | Kuf and V of one chunk of points (prepare_sparse_plan.h)
+    Buf selws;    // gpmpc_select_inducing: partial factors L | d | tile traces | tile records | picks | flags (select_inducing_plan.h)
     int* fidx = nullptr;         // device copy of the removed rows when there are more than 8
     size_t fidx_cap = 0;         // ints
     Buf hio;      // gpmpc_objective_grad_host: actions | J | grad | mu | Sig | cost_mu | cost_var of one candidate (device side)
@@ -301,6 +302,7 @@ struct Handle {
     int opt_fused_prepare = 1;       // N <= 256: the whole factorisation in one launch (prepare_small.hip); 0: panel path (A/B, tests)
     int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget), 4 sparse (gpmpc_prepare_sparse)
     int opt_sparse_chunk = 0;        // gpmpc_prepare_sparse: memory points per chunk (0: as many as a 64 MB workspace holds; else a multiple of 64)
+    long long opt_select_max_mb = 0; // gpmpc_select_inducing: cap on its workspace in MiB (0: 4096)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
     int opt_predict_bwd_chunk = 0;   // gpmpc_predict_backward: the same for its chunks
     int opt_predict_cov_chunk = 0;   // gpmpc_predict_cov: rows of Xa per chunk (0: as many as a 256 MB workspace holds; tests set a small one)
@@ -504,6 +506,10 @@ int launch_sparse_bmat(Handle* h, const double* G, const double* wpart, const do
 int launch_sparse_beta(Handle* h, const double* Yu, const double* Yb, const double* w, const double* noise, int M, int D, double* t1,
                        double* t2, double* beta, hipStream_t s);
 int launch_sparse_atb_sym(Handle* h, const double* A, const double* B, int M, int D, double* C, bool ident_minus, hipStream_t s);
+// select_inducing.hip: greedy variance selection of M of the N points X as inducing inputs (validated by the entry point; Z_out and
+// trace_out may be NULL); asynchronous on s, the cached model is neither read nor written
+int run_select_inducing(Handle* h, const double* X, int N, int M, const double* ls, const double* os, double jitter_rel, int D, int E,
+                        int* idx_out, double* Z_out, double* trace_out, hipStream_t s);
 // forget.hip: one removal (iK, linv, beta) -> (gram, Tm, zvec); the record (and, with `tables`, X^T and the data range) without the rows
 int launch_forget_step(Handle* h, int n, int j, int D, int ldw, hipStream_t s);
 int launch_forget_pack(Handle* h, const ForgetRows& rm, int n1, int D, int E, double* Xn, double* Yn, bool tables, hipStream_t s);

@@ -144,6 +144,34 @@ class HipEngine:
                                                   osc.data_ptr(), nz.data_ptr(), float(jitter_rel), D, E, self._stream()))
         self.N, self.D, self.E = M, D, E
 
+    def select_inducing(self, X, M, lengthscales, outputscales, jitter_rel=1e-6):
+        """Choose M of the memory points X (N, E) as inducing inputs for `prepare_sparse` by greedy variance selection
+        (gpmpc_select_inducing: a pivoted partial Cholesky of the D kernel matrices in lockstep, each step picking the point the
+        inducing set so far explains worst).  Returns DEVICE tensors {"idx": int32 (M,) the picks, distinct, idx[0] == 0;
+        "Z": (M, E) = X[idx] bit for bit; "trace": (M,) sum_a tr(K_a - Q_a) / outputscale_a after each pick}.  The choice depends
+        on the inputs and the kernel alone (no targets, no noise); outputs whose residual at a pick is not above `jitter_rel`
+        times their outputscale skip that step.  The cached model is neither needed nor touched, `last_prepare_mode` stays, and
+        nothing synchronises: the results are ordered on the current stream."""
+        X = self._dev(X)
+        if X.dim() != 2:
+            raise ValueError(f"expected inputs of shape (N, E), got {tuple(X.shape)}")
+        N, E = X.shape
+        ls = self._dev(lengthscales)
+        if ls.dim() != 2 or ls.shape[1] != E:
+            raise ValueError(f"expected lengthscales of shape (D, {E}), got {tuple(ls.shape)}")
+        D = ls.shape[0]
+        osc = self._dev(outputscales).reshape(-1)
+        if osc.numel() != D:
+            raise ValueError(f"expected {D} outputscales, got {osc.numel()}")
+        M = int(M)
+        idx = torch.empty(max(M, 0), dtype=torch.int32, device=self.device)
+        Z = torch.empty((max(M, 0), E), dtype=torch.float64, device=self.device)
+        trace = torch.empty(max(M, 0), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_select_inducing(self._h, X.data_ptr(), N, M, ls.data_ptr(), osc.data_ptr(), float(jitter_rel),
+                                                   D, E, idx.data_ptr(), Z.data_ptr(), trace.data_ptr(), self._stream()))
+        self._keep_select = (X, ls, osc)               # inputs of launches that may still be in flight
+        return {"idx": idx, "Z": Z, "trace": trace}
+
     def mll(self, X, Y, lengthscales, outputscales, noises):
         """Training loss of the D GPs and its gradient (gp_model.py:262-275): dict(loss (D,), d_lengthscale (D,E),
         d_outputscale (D,), d_noise (D,)) as numpy arrays.  Replaces the cached factors of this engine."""

@@ -95,6 +95,37 @@ int gpmpc_prepare_sparse(gpmpc_t* h, const double* X_dev, const double* Y_dev, i
                          const double* lengthscales_dev, const double* outputscales_dev, const double* noises_dev,
                          double jitter_rel, int D, int E, void* stream);
 
+/*
+ * gpmpc_select_inducing: chooses the M inducing inputs of gpmpc_prepare_sparse among the N memory points on the device (the
+ * reference has no counterpart).  Greedy variance selection (Burt et al. 2019; Fine & Scheinberg 2001): a pivoted partial Cholesky
+ * of the D kernel matrices K_a = k_a(X, X), k_a(x, x') = sigma2_a exp(-1/2 sum_e ((x_e - x'_e) / l_ae)^2), run in lockstep over
+ * the outputs because gpmpc_prepare_sparse takes one Z for all of them.  There is no Y and no noise: the choice depends on the
+ * inputs and the kernel alone.
+ *   X_dev (N,E)  lengthscales_dev (D,E)  outputscales_dev (D)
+ *   idx_out_dev (M) int, required: the picks, distinct;  Z_out_dev (M,E) or NULL: row m = X[p_m], bit for bit;
+ *   trace_out_dev (M) or NULL: trace[m] = sum_i s(i) over all N points after step m's update = sum_a tr(K_a - Q_a) / sigma2_a of
+ *   the first m + 1 picks (the trace term of the Titsias bound: it tells a caller when more points stop paying)
+ * State: d_a(i) = sigma2_a for every point, L_a (M x N) = 0.  At step m = 0 .. M-1:
+ *   score   s(i) = sum_a max(d_a(i), 0) / sigma2_a, a ascending
+ *   pick    p_m = the point of largest score among the points not yet picked; the lowest index wins a tie, a score that is not
+ *           finite ranks below every finite one (step 0: every score is exactly D, so p_0 = 0 always)
+ *   update  per output a, if d_a(p) > jitter_rel sigma2_a:
+ *             c(i) = (k_a(x_i, x_p) - sum_{j<m} L_a[j,i] L_a[j,p]) / sqrt(d_a(p)), j ascending;  L_a[m,i] = c(i);  d_a(i) -= c(i)^2
+ *           otherwise (the pivot floor gpmpc_prepare_sparse puts on the diagonal of k(Z, Z)) row m of L_a stays zero and d_a is
+ *           unchanged: no NaN and no abort.
+ * One plain launch per step (a workgroup per 64-point tile, a wavefront per output) and one to write the outputs: the partial
+ * trace of a tile is summed in a fixed tree, the tiles in ascending order; every sum runs in an order fixed by N, M, D and E alone,
+ * no atomics, no waits between workgroups: two calls give the same bits, and a NULL output changes no bit of the others.  No
+ * cached model is needed and none is touched; gpmpc_last_* is not written; the workspace is the call's own: D M N doubles of L plus
+ * O(D N + M N / 64), capped at 4 GiB (option "select_inducing_max_mb").  Asynchronous on `stream`, no host synchronisation inside.
+ * Errors are reported before anything is launched, the outputs untouched.  GPMPC_ERR_ARG: NULL X / lengthscales / outputscales /
+ * idx_out, N < 1, M < 1, M > N, jitter_rel negative or not finite; GPMPC_ERR_LIMIT: D or E beyond the compiled limits, or a
+ * workspace beyond the cap (gpmpc_last_error has the size).
+ */
+int gpmpc_select_inducing(gpmpc_t* h, const double* X_dev, int N, int M, const double* lengthscales_dev,
+                          const double* outputscales_dev, double jitter_rel, int D, int E,
+                          int* idx_out_dev, double* Z_out_dev, double* trace_out_dev, void* stream);
+
 /* Training objective: per GP -log p(y_a | X, theta_a) / N and its gradient wrt lengthscales, outputscale and
  * noise -- what gpytorch's ExactMarginalLogLikelihood + autograd give the reference's LBFGS loop (gp_model.py:262-275).
  * out_host (D, E + 3) = [loss | d/d lengthscale (E) | d/d outputscale | d/d noise]; synchronous; REPLACES the cached factors. */
@@ -288,7 +319,8 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
  * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
- * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64).
+ * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64),
+ * "select_inducing_max_mb" (cap on the workspace of gpmpc_select_inducing in MiB, >= 1; 4096 unless set).
  * Measurement (A/B) switches of single
  * kernels are listed with their measurements in csrc/gpmpc_internal.h (struct Handle, opt_*).  Unknown names: GPMPC_ERR_ARG.
  */

@@ -160,7 +160,7 @@ class ModelConfig:
                  min_outputscale=1e-5, max_outputscale=0.95, min_lengthscale=4e-3, max_lengthscale=25.0,
                  min_lengthscale_time=10, max_lengthscale_time=10000, include_time_model=False,
                  uncertainty_propagation="moment_matching", num_inducing_points=None, inducing_jitter=1e-6,
-                 inducing_selection="strided"):
+                 inducing_selection="strided", inducing_refresh_every=None):
         """num_inducing_points: None (the exact GP on the whole memory), or M >= 1 -- once the memory holds more than M points
         the model predicts with a sparse GP (DTC / projected process, gpmpc_prepare_sparse) on M inducing inputs, the rows
         round(i (N - 1) / (M - 1)), i = 0..M-1, of the N-point memory (M = 1: row 0): every prediction, rollout and gradient
@@ -170,6 +170,11 @@ class ModelConfig:
         or "greedy" (gpmpc_select_inducing, chosen afresh on the device at every prepare_inference: each pick is the point
         the inducing set so far explains worst under the current hyper-parameters, so a memory clustered round the setpoint
         keeps its few exploratory points).
+        inducing_refresh_every: None (every prepare_inference rebuilds the sparse model: select or stride, then
+        gpmpc_prepare_sparse), or R >= 1 -- a prepare_inference whose memory is the previous one followed by k new rows, under
+        unchanged hyper-parameters, appends them to the cached sparse model in O(k M^2) (gpmpc_sparse_append: same inducing
+        inputs) as long as no more than R rows have been appended since the last rebuild; the rebuild then chooses the
+        inducing inputs afresh.  Rounding does not limit R; the age of the inducing inputs does.
         uncertainty_propagation: how an uncertain state goes through the GP -- "moment_matching" (the reference's exact
         moment matching, gp_model.py:112-180) or "linearized" (first-order Taylor propagation at the input mean,
         gpmpc_moments_linear / gpmpc_rollout_linear: no D^2 pair pass, but a different approximation)."""
@@ -186,6 +191,11 @@ class ModelConfig:
         if inducing_selection not in INDUCING_SELECTIONS:
             raise ValueError(f"ModelConfig.inducing_selection must be one of {INDUCING_SELECTIONS}, got {inducing_selection!r}")
         self.inducing_selection = inducing_selection
+        if inducing_refresh_every is not None and (isinstance(inducing_refresh_every, bool)
+                                                   or int(inducing_refresh_every) != inducing_refresh_every
+                                                   or int(inducing_refresh_every) < 1):
+            raise ValueError(f"ModelConfig.inducing_refresh_every={inducing_refresh_every!r}: None or a positive number of rows")
+        self.inducing_refresh_every = None if inducing_refresh_every is None else int(inducing_refresh_every)
         if gp_init is None:
             gp_init = {"noise_covar.noise": [1e-4] * 3, "base_kernel.lengthscale": [[0.75] * 4] * 3,
                        "outputscale": [5e-2] * 3}

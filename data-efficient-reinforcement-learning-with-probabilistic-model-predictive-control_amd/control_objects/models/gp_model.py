@@ -333,6 +333,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self._cost_key = None
         self.is_sparse = False          # the cached model is the sparse one of gpmpc_prepare_sparse
         self.inducing_idx = None        # rows of the memory its inducing inputs are: a list (strided), a device tensor (greedy), or None
+        self._sparse_record = None      # ModelConfig.inducing_refresh_every: hyper-parameters of the last sparse prepare, rows appended since
 
     last_training_launches = None       # gpmpc_mll calls of the last `train` in this process (lockstep: ~ the longest GP's count)
 
@@ -374,7 +375,15 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         chosen afresh at every call (nothing is cached that training or a memory change could make stale) and handed to
         gpmpc_prepare_sparse on the device.  Otherwise (the option unset, or N <= M) it is the exact GP, as ever.
         `inducing_idx` records the chosen rows: a list (strided), an int32 device tensor (greedy), None otherwise.  x_mem /
-        y_mem are the whole memory either way: training and save_state see all of it."""
+        y_mem are the whole memory either way: training and save_state see all of it.
+        With ModelConfig.inducing_refresh_every = R the sparse model the config chose is not rebuilt when the memory only grew:
+        if `inputs` / `state_changes` are the previous memory followed by k >= 1 rows (compared by value), the hyper-parameters
+        are those of the last sparse prepare and no more than R rows have been appended since it, the k rows go through
+        gpmpc_sparse_append (O(k M^2), same inducing inputs, `inducing_idx` kept); with k = 0 no call is made at all.  Anything
+        else -- and an engine that answers the append with GPMPC_ERR_ARG -- rebuilds as above and starts the count again."""
+        if inducing_inputs is None and self._try_sparse_append(inputs, state_changes):
+            return
+        self._sparse_record = None
         self.x_mem = inputs
         self.y_mem = state_changes
         self.inducing_idx = None
@@ -391,8 +400,43 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         if self.is_sparse:
             self.engine.prepare_sparse(inputs, state_changes, inducing_inputs, self.lengthscales, self.variances, self.noises,
                                        getattr(self.config, "inducing_jitter", 1e-6))
+            if self.inducing_idx is not None and getattr(self.config, "inducing_refresh_every", None) is not None:
+                self._sparse_record = {"hyp": self._hyper_parameters(), "appended": 0}
         else:
             self.engine.prepare(inputs, state_changes, self.lengthscales, self.variances, self.noises)
+
+    def _hyper_parameters(self):
+        return tuple(t.detach().clone() for t in (self.lengthscales, self.variances, self.noises))
+
+    def _try_sparse_append(self, inputs, state_changes):
+        """The append policy of ModelConfig.inducing_refresh_every (see prepare_inference): True when the cached sparse model
+        already is, or by gpmpc_sparse_append has become, the model of this memory."""
+        rec = getattr(self, "_sparse_record", None)
+        R = getattr(self.config, "inducing_refresh_every", None)
+        if rec is None or R is None or not self.is_sparse or self.x_mem is None:
+            return False
+        if not all(torch.equal(a, b) for a, b in zip(rec["hyp"], self._hyper_parameters())):
+            return False
+        x_new, y_new, x_old, y_old = _t(inputs), _t(state_changes), _t(self.x_mem), _t(self.y_mem)
+        n_prev, k = len(x_old), len(x_new) - len(x_old)
+        if k < 0 or len(y_new) != len(x_new) or x_new.shape[1:] != x_old.shape[1:] or y_new.shape[1:] != y_old.shape[1:]:
+            return False
+        if not (torch.equal(x_new[:n_prev].cpu(), x_old.cpu()) and torch.equal(y_new[:n_prev].cpu(), y_old.cpu())):
+            return False
+        if k > 0:
+            if rec["appended"] + k > R:
+                return False
+            from ..._lib import GPMPC_ERR_ARG, GpmpcError
+            try:
+                self.engine.sparse_append(inputs[n_prev:], state_changes[n_prev:])
+            except GpmpcError as e:
+                if e.code != GPMPC_ERR_ARG:
+                    raise
+                return False                     # the engine holds no record (any more): rebuild
+            rec["appended"] += k
+        self.x_mem = inputs
+        self.y_mem = state_changes
+        return True
 
     def forget(self, indices):
         """Drop the memory points `indices` (strictly ascending rows of the memory of the last prepare_inference) from the
@@ -596,7 +640,8 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                           parameters=[m.state_dict() for m in self.models],
                           constraints_hyperparams={k: v for k, v in vars(self.config).items()
                                                    if k not in ("gp_init", "uncertainty_propagation", "num_inducing_points",
-                                                                "inducing_jitter", "inducing_selection")})
+                                                                "inducing_jitter", "inducing_selection",
+                                                                "inducing_refresh_every")})
 
     def load_state(self, saved_state):
         for m, p in zip(self.models, saved_state.parameters):

@@ -15,6 +15,7 @@
 #include "device_common.h"
 #include "prepare_tiled.h"
 #include "prepare_sparse_plan.h"
+#include "sparse_append_plan.h"
 
 namespace gpmpc_hip {
 
@@ -1137,6 +1138,7 @@ int run_set_factors(Handle* h, const double* X, const double* iK, const double* 
     GPMPC_HIP_CHECK(h, hipGetLastError());
     h->N = N; h->D = D; h->E = E; h->ready = true;
     h->have_state = false;                      // no (X, Y, hyper-parameters) record for these factors
+    h->sp_have = false;                         // ... and none of a sparse model
     return GPMPC_OK;
 }
 
@@ -1605,6 +1607,7 @@ static void commit_state(Handle* h, int N, int D, int E) {
 int run_prepare(Handle* h, const double* X, const double* Y, const double* ls, const double* os,
                 const double* noise, int N, int D, int E, hipStream_t s, bool allow_reuse) {
     h->last_prepare_mode = 0;
+    h->sp_have = false;                                            // the record of a sparse model ends here
     int rc = allow_reuse ? try_incremental(h, X, Y, ls, os, noise, N, D, E, s) : 0;
     if (rc != 0) return rc < 0 ? rc : GPMPC_OK;
     if ((rc = ensure_model_buffers(h, N, D, E, true))) return rc;
@@ -1638,7 +1641,11 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     if (rc) return rc;
     SparsePlan sp;
     plan_prepare_sparse(N, M, D, h->opt_sparse_chunk, sp);
+    h->sp_have = false;
     if ((rc = grow(h, h->spws, sp.total))) return rc;
+    SparseAppendPlan ap;
+    plan_sparse_append(M, D, ap);
+    if ((rc = grow(h, h->sprec, ap.total))) return rc;
     h->ready = false;
     h->have_state = false;
     h->last_prepare_mode = 4;
@@ -1680,6 +1687,11 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     }
     if ((rc = launch_sparse_bmat(h, G, ws + sp.wpart, noise, M, D, h->gram.p, ws + sp.w, s))) return rc;
     if ((rc = factor())) return rc;
+    // the record gpmpc_sparse_append continues from: Yb, w and the noises in buffers of their own (Yu stays at ws + sp.yu, which
+    // nothing but this function writes)
+    GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->sprec.p + ap.yb, h->linv.p, MM * sizeof(double), hipMemcpyDeviceToDevice, s));
+    GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->sprec.p + ap.w, ws + sp.w, (size_t)D * M * sizeof(double), hipMemcpyDeviceToDevice, s));
+    GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->sprec.p + ap.noise, noise, (size_t)D * sizeof(double), hipMemcpyDeviceToDevice, s));
     // tail: beta_eff = Yu^T Yb^T Yb w / n;  S = I - Yb^T Yb;  R = S Yu;  iK_eff = Yu^T R;  T
     if ((rc = launch_sparse_beta(h, ws + sp.yu, h->linv.p, ws + sp.w, noise, M, D, h->zvec.p, h->kv.p, h->beta.p, s))) return rc;
     if ((rc = launch_sparse_atb_sym(h, h->linv.p, h->linv.p, M, D, h->gram.p, true, s))) return rc;
@@ -1691,6 +1703,8 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
     h->N = M; h->D = D; h->E = E; h->ready = true;
     h->inc_updates = 0;                                            // no (X, Y) record: a later gpmpc_prepare factorises in full
+    h->sp_have = true;
+    h->sp_yu = sp.yu;
     return GPMPC_OK;
 }
 
@@ -1775,6 +1789,30 @@ int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const
     GPMPC_HIP_CHECK(h, hipGetLastError());
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(out_host, out, nout * sizeof(double), hipMemcpyDeviceToHost, s));
     GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
+    return GPMPC_OK;
+}
+
+// gpmpc_sparse_append (kernels and formulas: sparse_append.hip): per point the two launches of launch_sparse_append_point, then
+// once per call beta_eff by the three triangular products of the tail above and the T table.  No host synchronisation.  From the
+// first launch on a HIP error leaves no model and no record.
+int run_sparse_append(Handle* h, const double* Xn, const double* Yn, int k, hipStream_t s) {
+    const int M = h->N, D = h->D, E = h->E;
+    SparseAppendPlan ap;
+    plan_sparse_append(M, D, ap);
+    int rc;
+    if ((rc = check_sparse_append(h, ap))) return rc;
+    h->ready = false;
+    h->sp_have = false;
+    const double* Yu = h->spws.p + h->sp_yu;
+    double* rec = h->sprec.p;
+    for (int q = 0; q < k; ++q)
+        if ((rc = launch_sparse_append_point(h, ap, Yu, rec, Xn + (size_t)q * E, Yn + (size_t)q * D, M, D, E, s))) return rc;
+    if ((rc = launch_sparse_beta(h, Yu, rec + ap.yb, rec + ap.w, rec + ap.noise, M, D, rec + ap.t1, rec + ap.t2, h->beta.p, s))) return rc;
+    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    h->ready = true;
+    h->sp_have = true;
+    h->last_prepare_mode = 5;
     return GPMPC_OK;
 }
 

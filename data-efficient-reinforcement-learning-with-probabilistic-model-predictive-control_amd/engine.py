@@ -144,6 +144,22 @@ class HipEngine:
                                                   osc.data_ptr(), nz.data_ptr(), float(jitter_rel), D, E, self._stream()))
         self.N, self.D, self.E = M, D, E
 
+    def sparse_append(self, X_new, Y_new):
+        """Append the memory points (X_new (k, E), Y_new (k, D)) to the sparse model of the last `prepare_sparse`
+        (gpmpc_sparse_append): same inducing inputs, hyper-parameters and jitter, O(k M^2) per output, nothing of size N touched.
+        Afterwards the engine is in the state `prepare_sparse` would leave for the old memory followed by these rows, up to
+        rounding; calls chain.  `last_prepare_mode` is 5.  Nothing synchronises: the update is ordered on the current stream.
+        An engine without the record of a `prepare_sparse` (after `prepare`, `set_factors`, `mll`), k = 0 or other shapes than the
+        model's: GpmpcError(GPMPC_ERR_ARG), the cached model untouched."""
+        X = self._dev(X_new)
+        Y = self._dev(Y_new)
+        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError(f"expected inputs (k, E) and targets (k, D), got {tuple(X.shape)} and {tuple(Y.shape)}")
+        k, E = X.shape
+        D = Y.shape[1]
+        self._check(self.lib.gpmpc_sparse_append(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
+        self._keep_append = (X, Y)                     # inputs of launches that may still be in flight
+
     def select_inducing(self, X, M, lengthscales, outputscales, jitter_rel=1e-6):
         """Choose M of the memory points X (N, E) as inducing inputs for `prepare_sparse` by greedy variance selection
         (gpmpc_select_inducing: a pivoted partial Cholesky of the D kernel matrices in lockstep, each step picking the point the
@@ -207,7 +223,7 @@ class HipEngine:
     @property
     def last_prepare_mode(self):
         """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit, 3 = downdate (`forget`),
-        4 = sparse model (`prepare_sparse`)."""
+        4 = sparse model (`prepare_sparse`), 5 = points appended to a sparse model (`sparse_append`)."""
         return int(self.lib.gpmpc_last_prepare_mode(self._h))
 
     @property

@@ -47,7 +47,7 @@ struct LqrRiccatiArgs {
 };
 
 // The model inputs of step t: the state entries advance by the mean of the step before (the operation of
-// rollout_linear_step_kernel: the same bits), the action and time entries are set.
+// rollout_linear_step_kernel, moments_linear_kernels.h: the same bits), the action and time entries are set.
 __global__ __launch_bounds__(256) void lqr_inputs_kernel(LqrInputArgs p) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)p.rows * p.E) return;

@@ -9,54 +9,30 @@
 // sum_j c x_j - m sum_j c cancels digits with a time input.
 //
 // Structure ("Linearised propagation"):
-//   moments_linear_tile_kernel    one workgroup per (64 rows, 256-column block of iK_a, output a): P = K*_a iK_a by the k loop of
-//                                 predict.hip (K* tile built on the fly, iK tile staged in LDS, the next one loaded under the MFMAs;
-//                                 predict.hip and predict_cov.hip keep their own copies, so that their code is unchanged).  The
-//                                 epilogue walks the block in four slices of 64 columns: every lane forms k for its 16 rows x 1
-//                                 column, adds P k to its row sums and stages beta k in LDS; then each thread owns one row and the
-//                                 inputs e = w + 4 q and walks the slice's columns in order.  Per row it leaves the block's partial
-//                                 sums  sum_j P_mj k_mj | sum_j k_mj beta_j | E sums beta_j k_mj (x_je - m_e).  Without S the k
-//                                 loop is compiled out.
+//   lin_tile_kernel<EP, KLOOP, false>   (moments_linear_kernels.h, shared with the gradients) one workgroup per (64 rows, 256-column
+//                                 block of iK_a, output a): per row it leaves the block's partial sums
+//                                 sum_j P_mj k_mj | sum_j k_mj beta_j | E sums beta_j k_mj (x_je - m_e),  P = K*_a iK_a.  Without S
+//                                 the k loop that forms P is compiled out.
 //   moments_linear_finish_kernel  one wavefront per point: adds the column blocks in block order, scales the Jacobian, forms
 //                                 Sigma V and V^T (Sigma V) for a <= b and mirrors.
-//   rollout_linear_init_kernel /  the rollout is batch-major: per horizon step one tile launch over all candidates of the chunk,
-//   rollout_linear_step_kernel    then one wavefront per candidate adds the blocks, advances (mu, Sigma) in the stored trajectory
+//   rollout_linear_init_kernel /  (moments_linear_kernels.h) the rollout is batch-major: per horizon step one tile launch over all
+//   rollout_linear_step_kernel<FB>   candidates of the chunk, then one wavefront per candidate adds the blocks, advances (mu, Sigma)
+//                                 in the stored trajectory
 //                                   mu' = mu + M,  T = Sigma V_s,  Sigma' = Sigma + (V_s^T Sigma V_s + diag v) + T + T^T
 //                                 (V_s: the state rows of V) and writes the next step's model inputs [mu' | action | time0 + t + 1].
-//   rollout_linear_feedback_step_kernel /   the closed-loop rollout (gpmpc_rollout_linear_feedback): the same init kernel and tile
-//   traj_cost_feedback_kernel     launches; the step uses C = V_s + K_t^T V_u in place of V_s, the cost kernel the state-action
-//                                 covariance [I ; K_t] Sigma_t [I ; K_t]^T in place of block_diag(Sigma_t, 0).
+//   closed loop (FB) /            gpmpc_rollout_linear_feedback: the same init kernel and tile launches; the step's FB instantiation
+//   traj_cost_feedback_kernel     uses C = V_s + K_t^T V_u in place of V_s, the cost kernel the state-action covariance
+//                                 [I ; K_t] Sigma_t [I ; K_t]^T in place of block_diag(Sigma_t, 0).
 // Every sum runs in an order fixed by N, E and D alone (k steps, lanes, waves, slices, column blocks): a point's bits do not depend
 // on the batch size, on its place in the batch, on its neighbours or on the chunks.  Plain kernels: no atomics, no waits between
 // workgroups.  The workspace (Handle::linws) is this file's own, sized by plan_moments_linear (moments_linear_plan.h); a chunk of
 // candidates runs its whole horizon.  There is no fused-horizon form: with few candidates a 64-row tile is mostly padding and
 // every step costs two launches.
-#include "device_common.h"
-#include "moments_linear_plan.h"
+#include "moments_linear_kernels.h"
 
 namespace gpmpc_hip {
 
 namespace {
-
-constexpr int kBM = kLinBM;              // rows per workgroup
-constexpr int kBN = kLinBN;              // columns of iK per workgroup (64 per wave)
-constexpr int kBK = 16;                  // memory points per k step
-constexpr int kAPitch = kBM + 16;        // LDS row pitch (doubles) of the K* tile, stored [k][row]: rows 32 banks apart
-constexpr int kBPitch = kBN + 16;        // ... and of the iK tile [k][column]
-constexpr int kSlice = 64;               // columns of beta k staged in LDS at a time (16 per wave)
-constexpr int kCkPitch = kBM + 2;        // LDS pitch (doubles) of s_ck [column][row]: 32 lanes of a write hit distinct banks
-
-struct LinTileArgs {
-    const double* Xq;        // (rows, E) input means of this chunk
-    const double* Xt;        // (E, N)
-    const double* ils2;      // (D, E)
-    const double* var;       // (D)
-    const double* beta;      // (D, N)
-    const double* iK;        // (D, N, N)
-    double* part;            // (D, nCB, NW, Mc): sum_j P k | sum_j k beta | E sums beta k (x_j - m)
-    int rows, N, E, D, nCB, NW;
-    long long Mc;
-};
 
 struct LinFinishArgs {
     const double* part;
@@ -69,208 +45,6 @@ struct LinFinishArgs {
     int rows, E, D, nCB, NW;
     long long Mc;
 };
-
-struct LinStepArgs {
-    const double* part;
-    const double* ils2;      // (D, E)
-    const double* var;       // (D)
-    const double* actions;   // (rows, H, A) of this chunk
-    double* mu;              // (rows, H + 1, D) of this chunk
-    double* Sig;             // (rows, H + 1, D, D) of this chunk
-    double* Xq;              // (Mc, E) model inputs of the next tile launch
-    int rows, E, D, A, H, nCB, NW, t, include_time;
-    long long Mc;
-    double time0;
-    double mu0[kMaxD];       // read by the init kernel
-    double S0[kMaxD * kMaxD];
-};
-
-template <int EP>
-__device__ inline double kstar(const double* xq, const double (&xi)[EP], const double (&il)[EP], double sig2) {
-    double s = 0.0;
-#pragma unroll
-    for (int e = 0; e < EP; ++e) {
-        const double d = xq[e] - xi[e];
-        s = fma(d * d, il[e], s);
-    }
-    return sig2 * exp(-0.5 * s);
-}
-
-// P = K*_a iK_a for the workgroup's 64 rows and 256 columns (acc: the f64 MFMA C/D layout, see the epilogue).  The k loop of
-// predict_tile_kernel: the same operations in the same order.
-template <int EP>
-__device__ inline void kstar_ik_product(const double* Xt, const double* iKa, int N, int E, int j0, const double (&il)[EP],
-                                        double sig2, const double (&s_xq)[kBM][EP + 1], double (&s_A)[kBK][kAPitch],
-                                        double (&s_B)[kBK][kBPitch], d4 (&acc)[4][4]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // staging map: K* element (row gr + 16 q, point gi); iK elements (row bk, columns bc + 16 q)
-    const int gi = tid & 15, gr = tid >> 4;
-    const int bk = tid >> 4, bc = tid & 15;
-    const int nk = (N + kBK - 1) / kBK;
-    double breg[16];
-    auto load_b = [&](int i0) {
-        const int i = i0 + bk;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int j = j0 + bc + 16 * q;
-            breg[q] = (i < N && j < N) ? iKa[(size_t)i * N + j] : 0.0;
-        }
-    };
-    load_b(0);
-    for (int ks = 0; ks < nk; ++ks) {
-        const int i0 = ks * kBK;
-        __syncthreads();                         // the previous step's MFMAs have read s_A / s_B
-#pragma unroll
-        for (int q = 0; q < 16; ++q) s_B[bk][bc + 16 * q] = breg[q];
-        {
-            const int i = i0 + gi;
-            double xi[EP];
-#pragma unroll
-            for (int e = 0; e < EP; ++e) xi[e] = (e < E && i < N) ? Xt[(size_t)e * N + i] : 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = gr + 16 * q;
-                s_A[gi][r] = (i < N) ? kstar<EP>(s_xq[r], xi, il, sig2) : 0.0;
-            }
-        }
-        __syncthreads();
-        if (ks + 1 < nk) load_b(i0 + kBK);       // next iK tile in flight under the MFMAs
-#pragma unroll
-        for (int s = 0; s < kBK / 4; ++s) {
-            const int k = 4 * s + (lane >> 4);
-            double av[4], bv[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) av[rt] = s_A[k][16 * rt + (lane & 15)];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) bv[ct] = s_B[k][64 * w + 16 * ct + (lane & 15)];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
-        }
-    }
-}
-
-// Grid and k loop of predict_tile_kernel.  s_ck reuses the k loop's s_A / s_B.  The mean and Jacobian sums are the same
-// operations in both instantiations: they keep their bits when S is not asked for.
-template <int EP, bool VAR>
-__global__ __launch_bounds__(256) void moments_linear_tile_kernel(LinTileArgs p) {
-    constexpr int kLoop = kBK * kAPitch + kBK * kBPitch;
-    constexpr int kMem = (VAR && kLoop > kSlice * kCkPitch) ? kLoop : kSlice * kCkPitch;
-    constexpr int kQ = EP / 4;                       // inputs per thread in the contraction
-    __shared__ double s_xq[kBM][EP + 1];
-    __shared__ double s_xj[kSlice][EP + 1];
-    __shared__ double s_red[4][kBM];
-    __shared__ double s_mem[kMem];
-    double (*s_ck)[kCkPitch] = reinterpret_cast<double (*)[kCkPitch]>(s_mem);
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m0 = blockIdx.x * kBM;                 // first row of the tile (within the chunk)
-    const int cb = blockIdx.y, j0 = cb * kBN;
-    const int a = blockIdx.z;
-    const int N = p.N, E = p.E;
-    const double sig2 = p.var[a];
-    double il[EP];
-#pragma unroll
-    for (int e = 0; e < EP; ++e) il[e] = (e < E) ? p.ils2[a * E + e] : 0.0;
-    for (int idx = tid; idx < kBM * EP; idx += 256) {
-        const int r = idx / EP, e = idx - r * EP;
-        s_xq[r][e] = (e < E && m0 + r < p.rows) ? p.Xq[(size_t)(m0 + r) * E + e] : 0.0;
-    }
-    __syncthreads();
-
-    d4 acc[4][4];
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (VAR) {
-        auto& s_A = *reinterpret_cast<double (*)[kBK][kAPitch]>(s_mem);
-        auto& s_B = *reinterpret_cast<double (*)[kBK][kBPitch]>(s_mem + kBK * kAPitch);
-        kstar_ik_product<EP>(p.Xt, p.iK + (size_t)a * N * N, N, E, j0, il, sig2, s_xq, s_A, s_B, acc);
-    }
-
-    // epilogue: f64 C/D layout -- acc[rt][ct][r] = P[16 rt + (lane >> 4) + 4 r][64 w + 16 ct + (lane & 15)]
-    double rd[4][4];
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rd[rt][r] = 0.0;
-    // contraction state: row `crow`, inputs e = w + 4 q; wave 0 also sums beta k itself (the mean)
-    const int crow = tid & 63;
-    double xo[kQ], g[kQ], mn = 0.0;
-#pragma unroll
-    for (int q = 0; q < kQ; ++q) {
-        xo[q] = s_xq[crow][w + 4 * q];
-        g[q] = 0.0;
-    }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-        __syncthreads();                             // the k loop's MFMAs / the previous slice's contraction are done
-        const int c = 16 * w + (lane & 15);          // this lane's column within the slice
-        const int j = j0 + 64 * w + 16 * ct + (lane & 15);
-        double xj[EP];
-#pragma unroll
-        for (int e = 0; e < EP; ++e) xj[e] = (e < E && j < N) ? p.Xt[(size_t)e * N + j] : 0.0;
-        if ((lane >> 4) == 0) {
-#pragma unroll
-            for (int e = 0; e < EP; ++e) s_xj[c][e] = xj[e];
-        }
-        const double bj = (j < N) ? p.beta[(size_t)a * N + j] : 0.0;
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rt + (lane >> 4) + 4 * r;
-                double ck = 0.0;                     // columns past N contribute nothing (P there is 0 as well)
-                if (j < N) {
-                    const double k = kstar<EP>(s_xq[row], xj, il, sig2);
-                    if constexpr (VAR) rd[rt][r] = fma(acc[rt][ct][r], k, rd[rt][r]);
-                    ck = bj * k;
-                }
-                s_ck[c][row] = ck;
-            }
-        __syncthreads();
-#pragma unroll 4
-        for (int cs = 0; cs < kSlice; ++cs) {
-            const double ck = s_ck[cs][crow];
-            if (w == 0) mn += ck;
-#pragma unroll
-            for (int q = 0; q < kQ; ++q) g[q] = fma(ck, s_xj[cs][w + 4 * q] - xo[q], g[q]);
-        }
-    }
-    const size_t rstride = (size_t)p.Mc;
-    double* dst = p.part + ((size_t)a * p.nCB + cb) * p.NW * rstride;      // [which][row]
-    if (m0 + crow < p.rows) {
-        if (w == 0) dst[rstride + m0 + crow] = mn;
-#pragma unroll
-        for (int q = 0; q < kQ; ++q)
-            if (w + 4 * q < E) dst[(size_t)(2 + w + 4 * q) * rstride + m0 + crow] = g[q];
-    }
-    if constexpr (VAR) {
-        // sum_j P k: the 16 lanes of a row (lane & 15), then the 4 waves in order
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int off = 8; off >= 1; off >>= 1) rd[rt][r] += __shfl_xor(rd[rt][r], off, 64);
-                if ((lane & 15) == 0) s_red[w][16 * rt + (lane >> 4) + 4 * r] = rd[rt][r];
-            }
-        __syncthreads();
-        if (tid < kBM && m0 + tid < p.rows)
-            dst[m0 + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
-    }
-}
-
-// sum over the column blocks, in block order, of partial sum `which` of (output a, row)
-__device__ inline double block_sum(const double* part, int a, int which, size_t row, int nCB, int NW, size_t Mc) {
-    const double* src = part + ((size_t)a * nCB * NW + which) * Mc + row;
-    double s = 0.0;
-    for (int cb = 0; cb < nCB; ++cb) s += src[(size_t)cb * NW * Mc];
-    return s;
-}
 
 // One wavefront per point.
 __global__ __launch_bounds__(64) void moments_linear_finish_kernel(LinFinishArgs p) {
@@ -314,158 +88,6 @@ __global__ __launch_bounds__(64) void moments_linear_finish_kernel(LinFinishArgs
         if (a == b) q += p.var[a] - s_sum[a][0];                 // not clamped
         S[a * D + b] = q;
         S[b * D + a] = q;
-    }
-}
-
-// Index 0 of the stored trajectory and the model inputs of step 0.
-__global__ __launch_bounds__(64) void rollout_linear_init_kernel(LinStepArgs p) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H;
-    double* mu = p.mu + (size_t)b * (H + 1) * D;
-    double* Sg = p.Sig + (size_t)b * (H + 1) * D * D;
-    double* xq = p.Xq + (size_t)b * E;
-    for (int idx = tid; idx < D * D; idx += 64) Sg[idx] = p.S0[idx];
-    if (tid < D) {
-        mu[tid] = p.mu0[tid];
-        xq[tid] = p.mu0[tid];
-    }
-    if (tid < A) xq[D + tid] = p.actions[(size_t)b * H * A + tid];
-    if (p.include_time && tid == 0) xq[E - 1] = p.time0;
-}
-
-// One wavefront per candidate: step t -> t + 1 of the stored trajectory, and the model inputs of step t + 1.
-__global__ __launch_bounds__(64) void rollout_linear_step_kernel(LinStepArgs p) {
-    __shared__ double s_sum[kMaxD][kMaxD + 2];       // sum P k | sum k beta | the Jacobian sums of the state inputs
-    __shared__ double s_V[kMaxD][kMaxD];             // V_s [state input][output]
-    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
-    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t V_s
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, NS = D + 2;
-    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
-    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
-    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
-    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
-    for (int idx = tid; idx < D * NS; idx += 64) {
-        const int a = idx / NS, which = idx - a * NS;
-        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
-    }
-    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {
-        const int i = idx / D, a = idx - i * D;
-        s_V[i][a] = p.ils2[a * E + i] * s_sum[a][2 + i];
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t V_s
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_V[k][c], v);
-        s_T[i][c] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
-        const int a = idx / D, c = idx - a * D;
-        if (a > c) continue;
-        double q = 0.0;
-        for (int i = 0; i < D; ++i) q = fma(s_V[i][a], s_T[i][c], q);
-        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
-        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
-        Sg_n[a * D + c] = v;
-        Sg_n[c * D + a] = v;
-    }
-    const bool more = t + 1 < H;
-    double* xq = p.Xq + (size_t)b * E;
-    if (tid < D) {
-        const double v = mu_t[tid] + s_sum[tid][1];
-        mu_n[tid] = v;
-        if (more) xq[tid] = v;
-    }
-    if (more) {
-        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
-        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Closed-loop form (gpmpc_rollout_linear_feedback): the policy u = ubar_t + K_t (x - mu_t) makes the model input's covariance
-// G Sigma_t G^T with G = [I ; K_t ; 0], so the step's D x D Jacobian is C = G^T V = V_s + K_t^T V_u (V_u: the action rows of V).
-struct LinFbStepArgs {
-    const double* part;
-    const double* ils2;      // (D, E)
-    const double* var;       // (D)
-    const double* actions;   // (rows, H, A) of this chunk
-    const double* gains;     // (H, A, D) of the chunk's first candidate
-    long long gain_stride;   // doubles between two candidates' gains (0: one gain sequence shared by all)
-    double* mu;              // (rows, H + 1, D) of this chunk
-    double* Sig;             // (rows, H + 1, D, D) of this chunk
-    double* Xq;              // (Mc, E) model inputs of the next tile launch
-    int rows, E, D, A, H, nCB, NW, t, include_time;
-    long long Mc;
-    double time0;
-};
-
-// One wavefront per candidate: rollout_linear_step_kernel with C in place of V_s.  The mean takes the same operations as there
-// (its bits do not depend on the gains).
-__global__ __launch_bounds__(64) void rollout_linear_feedback_step_kernel(LinFbStepArgs p) {
-    __shared__ double s_sum[kMaxD][kMaxE + 2];       // sum P k | sum k beta | the Jacobian sums of the state and action inputs
-    __shared__ double s_V[kMaxE][kMaxD];             // V [state or action input][output]
-    __shared__ double s_K[kMaxE][kMaxD];             // K_t [action][state]
-    __shared__ double s_C[kMaxD][kMaxD];             // C = V_s + K_t^T V_u
-    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
-    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t C
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, DA = D + A, NS = DA + 2;
-    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
-    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
-    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
-    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
-    const double* K = p.gains + (size_t)b * (size_t)p.gain_stride + (size_t)t * A * D;
-    for (int idx = tid; idx < D * NS; idx += 64) {
-        const int a = idx / NS, which = idx - a * NS;
-        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
-    }
-    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
-    for (int idx = tid; idx < A * D; idx += 64) s_K[idx / D][idx % D] = K[idx];
-    __syncthreads();
-    for (int idx = tid; idx < DA * D; idx += 64) {
-        const int i = idx / D, a = idx - i * D;
-        s_V[i][a] = p.ils2[a * E + i] * s_sum[a][2 + i];
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // C = V_s + K^T V_u, the actions in order
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int u = 0; u < A; ++u) v = fma(s_K[u][i], s_V[D + u][c], v);
-        s_C[i][c] = s_V[i][c] + v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t C
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_C[k][c], v);
-        s_T[i][c] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
-        const int a = idx / D, c = idx - a * D;
-        if (a > c) continue;
-        double q = 0.0;
-        for (int i = 0; i < D; ++i) q = fma(s_C[i][a], s_T[i][c], q);
-        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
-        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
-        Sg_n[a * D + c] = v;
-        Sg_n[c * D + a] = v;
-    }
-    const bool more = t + 1 < H;
-    double* xq = p.Xq + (size_t)b * E;
-    if (tid < D) {
-        const double v = mu_t[tid] + s_sum[tid][1];
-        mu_n[tid] = v;
-        if (more) xq[tid] = v;
-    }
-    if (more) {
-        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
-        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
     }
 }
 
@@ -565,20 +187,6 @@ __global__ __launch_bounds__(64) void traj_cost_feedback_kernel(const double* __
     if (lane == 0 && J_out) J_out[c] = jsum / (double)(H + 1);
 }
 
-template <int EP>
-void launch_lin_tiles_ep(const LinTileArgs& p, bool var, hipStream_t s) {
-    const dim3 grid((p.rows + kBM - 1) / kBM, p.nCB, p.D);
-    if (var) hipLaunchKernelGGL((moments_linear_tile_kernel<EP, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((moments_linear_tile_kernel<EP, false>), grid, dim3(256), 0, s, p);
-}
-
-void launch_lin_tiles(const LinTileArgs& p, bool var, hipStream_t s) {
-    if (p.E <= 4) launch_lin_tiles_ep<4>(p, var, s);
-    else if (p.E <= 8) launch_lin_tiles_ep<8>(p, var, s);
-    else if (p.E <= 16) launch_lin_tiles_ep<16>(p, var, s);
-    else launch_lin_tiles_ep<24>(p, var, s);
-}
-
 }  // namespace
 
 int launch_traj_cost_feedback(Handle* h, const RolloutArgs& a, int rows, const double* mu, const double* Sig, const double* actions,
@@ -615,7 +223,7 @@ int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, do
         const int rows = (int)((P - m0) < pl.chunk ? (P - m0) : pl.chunk);
         p.rows = rows;
         p.Xq = mu + (size_t)m0 * E;
-        launch_lin_tiles(p, S_out != nullptr, s);
+        launch_lin_tiles<false>(p, S_out != nullptr, s);
         f.rows = rows;
         f.Sig = Sig ? Sig + (size_t)m0 * E * E : nullptr;
         f.M_out = M_out ? M_out + (size_t)m0 * D : nullptr;
@@ -629,8 +237,8 @@ int run_moments_linear(Handle* h, const double* mu, const double* Sig, int P, do
 
 // a: filled by the entry point (model, cost settings, actions, shape, initial state, outputs -- each output may be NULL).
 // gains != NULL: the closed-loop rollout under u = ubar_t + K_t (x - mu_t), gains (B, H, A, D) when per_candidate, else (H, A, D)
-// shared by all candidates -- the same plan, workspace, init kernel and tile launches with the step and cost kernels exchanged; a
-// chunk of candidates offsets the gain pointer only when the gains are per candidate.
+// shared by all candidates -- the same plan, workspace, init kernel and tile launches with the step kernel's FB form and the
+// closed-loop cost kernel; a chunk of candidates offsets the gain pointer only when the gains are per candidate.
 int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const double* gains, bool per_candidate) {
     const int N = a.N, D = a.D, E = a.E, A = a.A, H = a.H, B = a.B;
     const bool own_traj = !a.mu_out || !a.Sig_out;
@@ -653,34 +261,28 @@ int run_rollout_linear(Handle* h, const RolloutArgs& a, hipStream_t s, const dou
     q.include_time = a.include_time; q.time0 = a.time0;
     for (int d = 0; d < D; ++d) q.mu0[d] = a.mu0[d];
     for (int d = 0; d < D * D; ++d) q.S0[d] = a.S0[d];
-    LinFbStepArgs f{};
-    f.part = p.part; f.ils2 = p.ils2; f.var = p.var;
-    f.Xq = q.Xq;
-    f.E = E; f.D = D; f.A = A; f.H = H; f.nCB = pl.nCB; f.NW = pl.NW; f.Mc = pl.Mc;
-    f.include_time = a.include_time; f.time0 = a.time0;
-    f.gain_stride = per_candidate ? (long long)H * A * D : 0;
+    q.gain_stride = per_candidate ? (long long)H * A * D : 0;
     for (long long b0 = 0; b0 < B; b0 += pl.chunk) {
         const int rows = (int)((B - b0) < pl.chunk ? (B - b0) : pl.chunk);
-        p.rows = rows; q.rows = rows; f.rows = rows;
+        p.rows = rows;
         q.actions = a.actions + (size_t)b0 * H * A;
+        q.gains = gains ? gains + (size_t)b0 * (size_t)q.gain_stride : nullptr;
         q.mu = a.mu_out ? a.mu_out + (size_t)b0 * (H + 1) * D : own_mu;
         q.Sig = a.Sig_out ? a.Sig_out + (size_t)b0 * (H + 1) * D * D : own_Sig;
         q.t = 0;
-        f.actions = q.actions; f.mu = q.mu; f.Sig = q.Sig;
-        f.gains = gains ? gains + (size_t)b0 * (size_t)f.gain_stride : nullptr;
         hipLaunchKernelGGL(rollout_linear_init_kernel, dim3(rows), dim3(64), 0, s, q);
         for (int t = 0; t < H; ++t) {
-            launch_lin_tiles(p, true, s);
-            q.t = t; f.t = t;
-            if (gains) hipLaunchKernelGGL(rollout_linear_feedback_step_kernel, dim3(rows), dim3(64), 0, s, f);
-            else hipLaunchKernelGGL(rollout_linear_step_kernel, dim3(rows), dim3(64), 0, s, q);
+            launch_lin_tiles<false>(p, true, s);
+            q.t = t;
+            if (gains) hipLaunchKernelGGL(rollout_linear_step_kernel<true>, dim3(rows), dim3(64), 0, s, q);
+            else hipLaunchKernelGGL(rollout_linear_step_kernel<false>, dim3(rows), dim3(64), 0, s, q);
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());
         if (costs && gains) {                         // closed-loop stage costs + objective of the chunk's stored trajectory
             double* cm = a.cm_out ? a.cm_out + (size_t)b0 * (H + 1) : nullptr;
             double* cv = a.cv_out ? a.cv_out + (size_t)b0 * (H + 1) : nullptr;
             double* J = a.J_out ? a.J_out + b0 : nullptr;
-            rc = launch_traj_cost_feedback(h, a, rows, f.mu, f.Sig, f.actions, f.gains, f.gain_stride, cm, cv, J, s);
+            rc = launch_traj_cost_feedback(h, a, rows, q.mu, q.Sig, q.actions, q.gains, q.gain_stride, cm, cv, J, s);
             if (rc) return rc;
         } else if (costs) {                           // stage costs + objective of the chunk's stored trajectory
             RolloutArgs c = a;

@@ -8,27 +8,27 @@
 // from dM_a/dm_g = V[g,a], dV[e,a]/dm_g = sum_j beta k r_e r_g - delta_eg M_a / l_ae^2, dv_a/dm_g = -2 sum_j q_aj k_aj r_ajg.
 //
 // Structure ("Gradients of the linearised propagation"):
-//   lin_bwd_tile_kernel       the forward's tile kernel in this file's own copy (moments_linear.hip, predict.hip and
-//                             predict_cov.hip are unchanged): one workgroup per (64 rows, 256-column block of iK_a, output a), the
-//                             k loop P = K*_a iK_a on v_mfma_f64_16x16x4_f64, compiled out where no variance term is needed.  Forward
-//                             form: the block's partial sums  sum_j P k | sum_j k beta | E sums beta k (x_j - m).  Reverse form:
-//                             every lane forms k and c for its 16 rows x 1 column from the row's coefficients
-//                             M_bar_a | s_a | W[e,a] / l_ae^2 (staged in LDS) and P, stages c k in LDS, and the contraction of the
-//                             forward leaves the E sums  sum_j c k (x_jg - m_g).
+//   lin_tile_kernel           (moments_linear_kernels.h, shared with the forward) one workgroup per (64 rows, 256-column block of
+//                             iK_a, output a), the k loop P = K*_a iK_a on v_mfma_f64_16x16x4_f64, compiled out where no variance
+//                             term is needed.  Forward form: the block's partial sums  sum_j P k | sum_j k beta | E sums
+//                             beta k (x_j - m).  Reverse form: every lane forms k and c for its 16 rows x 1 column from the row's
+//                             coefficients M_bar_a | s_a | W[e,a] / l_ae^2 (staged in LDS) and P, stages c k in LDS, and the
+//                             contraction of the forward leaves the E sums  sum_j c k (x_jg - m_g).
 //   lin_bwd_point_kernel      one wavefront per point, between the two tile launches: adds the forward sums in block order, forms
 //                             V, var_bar, W, the coefficients and  sum_a W[g,a] M_a / l_ag^2.
 //   lin_bwd_finish_kernel     one wavefront per point: adds the reverse sums in block order, scales, subtracts.
-//   rollout_linear_bwd_*      the trajectory: per chunk of candidates the forward is recomputed batch-major (one tile launch + one
-//                             wavefront per candidate and step, as gpmpc_rollout_linear) and KEEPS every step's M and the state
-//                             rows of V beside the trajectory; the cost variances come from the trajectory cost kernel.  Reverse
+//   rollout_linear_bwd_*      the trajectory: per chunk of candidates the forward is recomputed batch-major by the forward's own
+//                             kernels (rollout_linear_init_kernel, then one tile launch + rollout_linear_step_kernel per step,
+//                             moments_linear_kernels.h), which KEEP every step's M and the state rows of V (keepM / keepV)
+//                             beside the trajectory; the cost variances come from the trajectory cost kernel.  Reverse
 //                             sweep t = H-1 .. 0 with A_t = I + V_s (Sigma_{t+1} = A_t^T Sigma_t A_t + diag v): one wavefront per
 //                             candidate closes step t + 1 (x_bar from the tile sums -> lambda, actions_bar) and opens step t (cost
 //                             partials by cost_adjoint_wave, W = 2 Sigma_t A_t Lambda on the state rows, the coefficients,
 //                             Lambda_t = sym(seeds) + A_t Lambda A_t^T, the model inputs), then one reverse tile launch over the
 //                             chunk: H + 1 small launches and H tile launches.
 //   closed loop (FB)          u = ubar_t + K_t (x - mu_t): C_t = V_s + K_t^T V_u takes the place of V_s (A_t = I + C_t).  The forward
-//                             is recomputed by rollout_linear_fb_bwd_forward_kernel (the arithmetic of
-//                             rollout_linear_feedback_step_kernel) and keeps the D + A state and action rows of V; the cost
+//                             is recomputed by rollout_linear_step_kernel<true>, the closed-loop forward's own step, and keeps
+//                             the D + A state and action rows of V; the cost
 //                             variances come from the closed-loop cost kernel (launch_traj_cost_feedback).  The reverse kernel's
 //                             FB instantiation loads K_t, takes the cost partials from cost_adjoint_feedback_wave, fills the
 //                             action rows of W with K_t C_bar (C_bar = 2 Sigma_t A_t Lambda) and writes gains_bar_t = (cost
@@ -36,35 +36,13 @@
 // Every sum runs in an order fixed by N, E, D and A alone; a point's or candidate's bits do not depend on the batch, on its place in
 // it or on the chunks.  Plain kernels: no atomics, no waits between workgroups.  The workspace (Handle::linbws) is this file's
 // own, laid out by plan_moments_linear_backward (moments_linear_backward_plan.h).
-#include <type_traits>
-
 #include "grad_kernels.h"
 #include "moments_linear_backward_plan.h"
+#include "moments_linear_kernels.h"
 
 namespace gpmpc_hip {
 
 namespace {
-
-constexpr int kBM = kLinBwdBM;           // rows per workgroup
-constexpr int kBN = kLinBwdBN;           // columns of iK per workgroup (64 per wave)
-constexpr int kBK = 16;                  // memory points per k step
-constexpr int kAPitch = kBM + 16;        // LDS row pitch (doubles) of the K* tile, stored [k][row]: rows 32 banks apart
-constexpr int kBPitch = kBN + 16;        // ... and of the iK tile [k][column]
-constexpr int kSlice = 64;               // columns of c k staged in LDS at a time (16 per wave)
-constexpr int kCkPitch = kBM + 2;        // LDS pitch (doubles) of s_ck [column][row]
-
-struct LbTileArgs {
-    const double* Xq;        // (rows, E) input means of this chunk
-    const double* Xt;        // (E, N)
-    const double* ils2;      // (D, E)
-    const double* var;       // (D)
-    const double* beta;      // (D, N)
-    const double* iK;        // (D, N, N)
-    const double* coef;      // (D, NW, Mc) reverse form: M_bar_a | s_a | E weights W[e,a] / l_ae^2
-    double* part;            // (D, nCB, NW, Mc) forward: sum_j P k | sum_j k beta | E sums; reverse: - | - | E sums
-    int rows, N, E, D, nCB, NW;
-    long long Mc;
-};
 
 struct LbPointArgs {
     const double* part;
@@ -81,244 +59,19 @@ struct LbPointArgs {
     long long Mc;
 };
 
-struct LbRollArgs {
-    const double* part;
-    const double* ils2;      // (D, E)
-    const double* var;       // (D)
+// The reverse kernel's block: the recomputed forward's (mu / Sig: the recomputed trajectory; keepM / keepV set) and the sweep's own.
+struct LbRollArgs : LinStepArgs {
     const double* cost;      // target | W | W_T | smin | smax
-    const double* actions;   // (rows, H, A) of this chunk
-    double* mu;              // (rows, H + 1, D) recomputed trajectory of this chunk
-    double* Sig;             // (rows, H + 1, D, D)
-    double* stepM;           // (rows, H, D)
-    double* stepV;           // (rows, H, D, D) state rows of V [state input][output]
     const double* cv;        // (rows, H + 1) cost variances (read with an objective seed only)
     double* adj;             // (rows, 2 D + D D + A): lambda | Lambda | cost partials of the open step wrt mu and the action
     double* coef;            // (D, NW, Mc)
     double* base;            // (rows, E)
-    double* Xq;              // (Mc, E) model inputs of the next tile launch
     SweepSeeds sd;           // this chunk's cotangents (each NULL = 0) and initial-state outputs (each NULL = not written)
     double* actions_bar;     // (rows, H, A) of this chunk
-    int E, D, A, H, nCB, NW, t, include_time, use_constraints;
-    long long Mc;
-    double time0, kappa;
-    double mu0[kMaxD];       // read by the init kernel
-    double S0[kMaxD * kMaxD];
+    double* gains_bar;       // closed loop: (rows, H, A, D) of this chunk, or NULL (not written)
+    int use_constraints;
+    double kappa;
 };
-
-// The closed-loop kernels' block: the open-loop kernels keep theirs.
-struct LbFbArgs : LbRollArgs {
-    const double* gains;     // (H, A, D) of the chunk's first candidate
-    long long gain_stride;   // doubles between two candidates' gains (0: one gain sequence shared by all)
-    double* gains_bar;       // (rows, H, A, D) of this chunk, or NULL (not written)
-};
-
-template <int EP>
-__device__ inline double kstar(const double* xq, const double (&xi)[EP], const double (&il)[EP], double sig2) {
-    double s = 0.0;
-#pragma unroll
-    for (int e = 0; e < EP; ++e) {
-        const double d = xq[e] - xi[e];
-        s = fma(d * d, il[e], s);
-    }
-    return sig2 * exp(-0.5 * s);
-}
-
-// P = K*_a iK_a for the workgroup's 64 rows and 256 columns (acc: the f64 MFMA C/D layout, see the epilogue).  The k loop of
-// moments_linear_tile_kernel / predict_tile_kernel: the same operations in the same order.
-template <int EP>
-__device__ inline void kstar_ik_product(const double* Xt, const double* iKa, int N, int E, int j0, const double (&il)[EP],
-                                        double sig2, const double (&s_xq)[kBM][EP + 1], double (&s_A)[kBK][kAPitch],
-                                        double (&s_B)[kBK][kBPitch], d4 (&acc)[4][4]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // staging map: K* element (row gr + 16 q, point gi); iK elements (row bk, columns bc + 16 q)
-    const int gi = tid & 15, gr = tid >> 4;
-    const int bk = tid >> 4, bc = tid & 15;
-    const int nk = (N + kBK - 1) / kBK;
-    double breg[16];
-    auto load_b = [&](int i0) {
-        const int i = i0 + bk;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int j = j0 + bc + 16 * q;
-            breg[q] = (i < N && j < N) ? iKa[(size_t)i * N + j] : 0.0;
-        }
-    };
-    load_b(0);
-    for (int ks = 0; ks < nk; ++ks) {
-        const int i0 = ks * kBK;
-        __syncthreads();                         // the previous step's MFMAs have read s_A / s_B
-#pragma unroll
-        for (int q = 0; q < 16; ++q) s_B[bk][bc + 16 * q] = breg[q];
-        {
-            const int i = i0 + gi;
-            double xi[EP];
-#pragma unroll
-            for (int e = 0; e < EP; ++e) xi[e] = (e < E && i < N) ? Xt[(size_t)e * N + i] : 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = gr + 16 * q;
-                s_A[gi][r] = (i < N) ? kstar<EP>(s_xq[r], xi, il, sig2) : 0.0;
-            }
-        }
-        __syncthreads();
-        if (ks + 1 < nk) load_b(i0 + kBK);       // next iK tile in flight under the MFMAs
-#pragma unroll
-        for (int s = 0; s < kBK / 4; ++s) {
-            const int k = 4 * s + (lane >> 4);
-            double av[4], bv[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) av[rt] = s_A[k][16 * rt + (lane & 15)];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) bv[ct] = s_B[k][64 * w + 16 * ct + (lane & 15)];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[rt], bv[ct], acc[rt][ct], 0, 0, 0);
-        }
-    }
-}
-
-// KLOOP: P = K* iK is formed (forward: the variance sum is wanted; reverse: s_a may be non-zero).  BWD: the reverse form.
-template <int EP, bool KLOOP, bool BWD>
-__global__ __launch_bounds__(256) void lin_bwd_tile_kernel(LbTileArgs p) {
-    constexpr int kLoop = kBK * kAPitch + kBK * kBPitch;
-    constexpr int kMem = (KLOOP && kLoop > kSlice * kCkPitch) ? kLoop : kSlice * kCkPitch;
-    constexpr int kQ = EP / 4;                       // inputs per thread in the contraction
-    constexpr int kCfRows = BWD ? kBM : 1;
-    __shared__ double s_xq[kBM][EP + 1];
-    __shared__ double s_xj[kSlice][EP + 1];
-    __shared__ double s_cf[kCfRows][EP + 3];         // reverse form: M_bar_a | s_a | W[e,a] / l_ae^2 of the tile's rows
-    __shared__ double s_red[4][kBM];
-    __shared__ double s_mem[kMem];
-    double (*s_ck)[kCkPitch] = reinterpret_cast<double (*)[kCkPitch]>(s_mem);
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m0 = blockIdx.x * kBM;                 // first row of the tile (within the chunk)
-    const int cb = blockIdx.y, j0 = cb * kBN;
-    const int a = blockIdx.z;
-    const int N = p.N, E = p.E;
-    const double sig2 = p.var[a];
-    double il[EP];
-#pragma unroll
-    for (int e = 0; e < EP; ++e) il[e] = (e < E) ? p.ils2[a * E + e] : 0.0;
-    for (int idx = tid; idx < kBM * EP; idx += 256) {
-        const int r = idx / EP, e = idx - r * EP;
-        s_xq[r][e] = (e < E && m0 + r < p.rows) ? p.Xq[(size_t)(m0 + r) * E + e] : 0.0;
-    }
-    if constexpr (BWD) {
-        for (int idx = tid; idx < kBM * (EP + 2); idx += 256) {
-            const int c = idx / kBM, r = idx - c * kBM;
-            s_cf[r][c] = (c < E + 2 && m0 + r < p.rows) ? p.coef[((size_t)a * p.NW + c) * (size_t)p.Mc + m0 + r] : 0.0;
-        }
-    }
-    __syncthreads();
-
-    d4 acc[4][4];
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = d4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (KLOOP) {
-        auto& s_A = *reinterpret_cast<double (*)[kBK][kAPitch]>(s_mem);
-        auto& s_B = *reinterpret_cast<double (*)[kBK][kBPitch]>(s_mem + kBK * kAPitch);
-        kstar_ik_product<EP>(p.Xt, p.iK + (size_t)a * N * N, N, E, j0, il, sig2, s_xq, s_A, s_B, acc);
-    }
-
-    // epilogue: f64 C/D layout -- acc[rt][ct][r] = P[16 rt + (lane >> 4) + 4 r][64 w + 16 ct + (lane & 15)]
-    [[maybe_unused]] double rd[4][4];
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) rd[rt][r] = 0.0;
-    // contraction state: row `crow`, inputs e = w + 4 q; forward form: wave 0 also sums beta k itself (the mean)
-    const int crow = tid & 63;
-    double xo[kQ], g[kQ];
-    [[maybe_unused]] double mn = 0.0;
-#pragma unroll
-    for (int q = 0; q < kQ; ++q) {
-        xo[q] = s_xq[crow][w + 4 * q];
-        g[q] = 0.0;
-    }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-        __syncthreads();                             // the k loop's MFMAs / the previous slice's contraction are done
-        const int c = 16 * w + (lane & 15);          // this lane's column within the slice
-        const int j = j0 + 64 * w + 16 * ct + (lane & 15);
-        double xj[EP];
-#pragma unroll
-        for (int e = 0; e < EP; ++e) xj[e] = (e < E && j < N) ? p.Xt[(size_t)e * N + j] : 0.0;
-        if ((lane >> 4) == 0) {
-#pragma unroll
-            for (int e = 0; e < EP; ++e) s_xj[c][e] = xj[e];
-        }
-        const double bj = (j < N) ? p.beta[(size_t)a * N + j] : 0.0;
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * rt + (lane >> 4) + 4 * r;
-                double ck = 0.0;                     // columns past N contribute nothing (P there is 0 as well)
-                if (j < N) {
-                    const double k = kstar<EP>(s_xq[row], xj, il, sig2);
-                    if constexpr (BWD) {
-                        double u = 0.0;              // sum_e W[e,a] r_aje
-#pragma unroll
-                        for (int e = 0; e < EP; ++e) u = fma(s_cf[row][2 + e], xj[e] - s_xq[row][e], u);
-                        double cc = bj * (s_cf[row][0] + u);
-                        if constexpr (KLOOP) cc = fma(-2.0 * s_cf[row][1], acc[rt][ct][r], cc);
-                        ck = cc * k;
-                    } else {
-                        if constexpr (KLOOP) rd[rt][r] = fma(acc[rt][ct][r], k, rd[rt][r]);
-                        ck = bj * k;
-                    }
-                }
-                s_ck[c][row] = ck;
-            }
-        __syncthreads();
-#pragma unroll 4
-        for (int cs = 0; cs < kSlice; ++cs) {
-            const double ck = s_ck[cs][crow];
-            if constexpr (!BWD) {
-                if (w == 0) mn += ck;
-            }
-#pragma unroll
-            for (int q = 0; q < kQ; ++q) g[q] = fma(ck, s_xj[cs][w + 4 * q] - xo[q], g[q]);
-        }
-    }
-    const size_t rstride = (size_t)p.Mc;
-    double* dst = p.part + ((size_t)a * p.nCB + cb) * p.NW * rstride;      // [which][row]
-    if (m0 + crow < p.rows) {
-        if constexpr (!BWD) {
-            if (w == 0) dst[rstride + m0 + crow] = mn;
-        }
-#pragma unroll
-        for (int q = 0; q < kQ; ++q)
-            if (w + 4 * q < E) dst[(size_t)(2 + w + 4 * q) * rstride + m0 + crow] = g[q];
-    }
-    if constexpr (KLOOP && !BWD) {
-        // sum_j P k: the 16 lanes of a row (lane & 15), then the 4 waves in order
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                for (int off = 8; off >= 1; off >>= 1) rd[rt][r] += __shfl_xor(rd[rt][r], off, 64);
-                if ((lane & 15) == 0) s_red[w][16 * rt + (lane >> 4) + 4 * r] = rd[rt][r];
-            }
-        __syncthreads();
-        if (tid < kBM && m0 + tid < p.rows)
-            dst[m0 + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
-    }
-}
-
-// sum over the column blocks, in block order, of partial sum `which` of (output a, row)
-__device__ inline double block_sum(const double* part, int a, int which, size_t row, int nCB, int NW, size_t Mc) {
-    const double* src = part + ((size_t)a * nCB * NW + which) * Mc + row;
-    double s = 0.0;
-    for (int cb = 0; cb < nCB; ++cb) s += src[(size_t)cb * NW * Mc];
-    return s;
-}
 
 // One wavefront per point, after the forward-form tile launch (no k loop: M and the Jacobian sums only).
 __global__ __launch_bounds__(64) void lin_bwd_point_kernel(LbPointArgs p) {
@@ -407,152 +160,6 @@ __global__ __launch_bounds__(64) void lin_bwd_finish_kernel(LbPointArgs p) {
 }
 
 // ---- the trajectory ------------------------------------------------------------------------------------------------------------
-// Index 0 of the recomputed trajectory and the model inputs of step 0 (rollout_linear_init_kernel).
-__global__ __launch_bounds__(64) void rollout_linear_bwd_init_kernel(LbRollArgs p) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H;
-    double* mu = p.mu + (size_t)b * (H + 1) * D;
-    double* Sg = p.Sig + (size_t)b * (H + 1) * D * D;
-    double* xq = p.Xq + (size_t)b * E;
-    for (int idx = tid; idx < D * D; idx += 64) Sg[idx] = p.S0[idx];
-    if (tid < D) {
-        mu[tid] = p.mu0[tid];
-        xq[tid] = p.mu0[tid];
-    }
-    if (tid < A) xq[D + tid] = p.actions[(size_t)b * H * A + tid];
-    if (p.include_time && tid == 0) xq[E - 1] = p.time0;
-}
-
-// One wavefront per candidate: step t -> t + 1 of the recomputed trajectory (the arithmetic of rollout_linear_step_kernel), the
-// step's M and V_s kept for the reverse sweep, and the model inputs of step t + 1.
-__global__ __launch_bounds__(64) void rollout_linear_bwd_forward_kernel(LbRollArgs p) {
-    __shared__ double s_sum[kMaxD][kMaxD + 2];       // sum P k | sum k beta | the Jacobian sums of the state inputs
-    __shared__ double s_V[kMaxD][kMaxD];             // V_s [state input][output]
-    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
-    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t V_s
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, NS = D + 2;
-    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
-    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
-    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
-    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
-    double* keepM = p.stepM + ((size_t)b * H + t) * D;
-    double* keepV = p.stepV + ((size_t)b * H + t) * D * D;
-    for (int idx = tid; idx < D * NS; idx += 64) {
-        const int a = idx / NS, which = idx - a * NS;
-        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
-    }
-    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {
-        const int i = idx / D, a = idx - i * D;
-        const double v = p.ils2[a * E + i] * s_sum[a][2 + i];
-        s_V[i][a] = v;
-        keepV[idx] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t V_s
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_V[k][c], v);
-        s_T[i][c] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
-        const int a = idx / D, c = idx - a * D;
-        if (a > c) continue;
-        double q = 0.0;
-        for (int i = 0; i < D; ++i) q = fma(s_V[i][a], s_T[i][c], q);
-        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
-        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
-        Sg_n[a * D + c] = v;
-        Sg_n[c * D + a] = v;
-    }
-    const bool more = t + 1 < H;
-    double* xq = p.Xq + (size_t)b * E;
-    if (tid < D) {
-        const double v = mu_t[tid] + s_sum[tid][1];
-        keepM[tid] = s_sum[tid][1];
-        mu_n[tid] = v;
-        if (more) xq[tid] = v;
-    }
-    if (more) {
-        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
-        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
-    }
-}
-
-// One wavefront per candidate, closed loop: step t -> t + 1 of the recomputed trajectory with the arithmetic of
-// rollout_linear_feedback_step_kernel (the same operations in the same order: the trajectory has the forward entry's bits), the
-// step's M and the D + A state and action rows of V kept for the reverse sweep, and the model inputs of step t + 1.
-__global__ __launch_bounds__(64) void rollout_linear_fb_bwd_forward_kernel(LbFbArgs p) {
-    __shared__ double s_sum[kMaxD][kMaxE + 2];       // sum P k | sum k beta | the Jacobian sums of the state and action inputs
-    __shared__ double s_V[kMaxE][kMaxD];             // V [state or action input][output]
-    __shared__ double s_K[kMaxE][kMaxD];             // K_t [action][state]
-    __shared__ double s_C[kMaxD][kMaxD];             // C = V_s + K_t^T V_u
-    __shared__ double s_S[kMaxD][kMaxD];             // Sigma_t
-    __shared__ double s_T[kMaxD][kMaxD];             // Sigma_t C
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int D = p.D, E = p.E, A = p.A, H = p.H, t = p.t, DA = D + A, NS = DA + 2;
-    const double* mu_t = p.mu + ((size_t)b * (H + 1) + t) * D;
-    const double* Sg_t = p.Sig + ((size_t)b * (H + 1) + t) * D * D;
-    double* mu_n = p.mu + ((size_t)b * (H + 1) + t + 1) * D;
-    double* Sg_n = p.Sig + ((size_t)b * (H + 1) + t + 1) * D * D;
-    double* keepM = p.stepM + ((size_t)b * H + t) * D;
-    double* keepV = p.stepV + ((size_t)b * H + t) * DA * D;
-    const double* K = p.gains + (size_t)b * (size_t)p.gain_stride + (size_t)t * A * D;
-    for (int idx = tid; idx < D * NS; idx += 64) {
-        const int a = idx / NS, which = idx - a * NS;
-        s_sum[a][which] = block_sum(p.part, a, which, (size_t)b, p.nCB, p.NW, (size_t)p.Mc);
-    }
-    for (int idx = tid; idx < D * D; idx += 64) s_S[idx / D][idx % D] = Sg_t[idx];
-    for (int idx = tid; idx < A * D; idx += 64) s_K[idx / D][idx % D] = K[idx];
-    __syncthreads();
-    for (int idx = tid; idx < DA * D; idx += 64) {
-        const int i = idx / D, a = idx - i * D;
-        const double v = p.ils2[a * E + i] * s_sum[a][2 + i];
-        s_V[i][a] = v;
-        keepV[idx] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // C = V_s + K^T V_u, the actions in order
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int u = 0; u < A; ++u) v = fma(s_K[u][i], s_V[D + u][c], v);
-        s_C[i][c] = s_V[i][c] + v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // T = Sigma_t C
-        const int i = idx / D, c = idx - i * D;
-        double v = 0.0;
-        for (int k = 0; k < D; ++k) v = fma(s_S[i][k], s_C[k][c], v);
-        s_T[i][c] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += 64) {                // a <= c, mirrored: exactly symmetric
-        const int a = idx / D, c = idx - a * D;
-        if (a > c) continue;
-        double q = 0.0;
-        for (int i = 0; i < D; ++i) q = fma(s_C[i][a], s_T[i][c], q);
-        if (a == c) q += p.var[a] - s_sum[a][0];                 // not clamped
-        const double v = (s_S[a][c] + q) + (s_T[a][c] + s_T[c][a]);
-        Sg_n[a * D + c] = v;
-        Sg_n[c * D + a] = v;
-    }
-    const bool more = t + 1 < H;
-    double* xq = p.Xq + (size_t)b * E;
-    if (tid < D) {
-        const double v = mu_t[tid] + s_sum[tid][1];
-        keepM[tid] = s_sum[tid][1];
-        mu_n[tid] = v;
-        if (more) xq[tid] = v;
-    }
-    if (more) {
-        if (tid < A) xq[D + tid] = p.actions[((size_t)b * H + t + 1) * A + tid];
-        if (p.include_time && tid == 0) xq[E - 1] = p.time0 + (double)(t + 1);
-    }
-}
-
 // Closed-loop form of cost_adjoint_wave for a stage t < H: the quadratic cost sees Sigma_z = G Sigma_t G^T with G = [I ; K]
 // (K (A, D) row-major), so besides (mu, Sigma, u) there is a partial wrt K.  With Q = W Sigma_z W (W not assumed symmetric):
 //   Sz_bar = wm W^T + 4 wv (Q^T + (W^T e)(W e)^T),   e_bar = wm (W + W^T) e + 4 wv (Q + Q^T) e
@@ -671,13 +278,12 @@ __device__ inline void cost_adjoint_feedback_wave(int lane, int D, int A, const 
 // (first launch): the adjoints start at the terminal index H.  t_pre >= 0: step t_pre is opened -- its cost partials and seeds,
 // A = I + V_s, W = 2 Sigma_t A Lambda, the coefficients and model inputs of its tile launch, Lambda_t = sym(.) + A Lambda A^T;
 // t_pre < 0 (last launch): lambda_0 / Lambda_0 go to mu0_bar / S0_bar.
-// FB (compile time; the open-loop instantiation is the kernel it was): the closed loop -- K_t is loaded, the stage's cost partials
+// FB (compile time): the closed loop -- K_t is loaded, the stage's cost partials
 // come from cost_adjoint_feedback_wave (with the one wrt K_t), A = I + C with C = V_s + K_t^T V_u, the action rows of W are
 // K_t C_bar (C_bar = the state rows, 2 Sigma_t A Lambda), and opening step t writes gains_bar_t = (cost partial) + V_u C_bar^T.
 // Static LDS of the FB instantiation at kMaxD = 16, kMaxE = 24: 5520 doubles = 44160 bytes (open loop: 3760 = 30080).
 template <bool FB>
-__global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(std::conditional_t<FB, LbFbArgs, LbRollArgs> p, int t_post,
-                                                                        int t_pre) {
+__global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(LbRollArgs p, int t_post, int t_pre) {
     constexpr int kN = kMaxE;                        // D + A <= E <= kMaxE
     constexpr int kTmp = FB ? cost_adjoint_feedback_tmp(kMaxD, kN - kMaxD) : 2 * kN * kN + 3 * kN;
     constexpr int kWR = FB ? kMaxE : kMaxD;          // rows of W that may be non-zero
@@ -789,8 +395,8 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(std::con
     }
     const int t = t_pre;
     stage_adjoint(t);
-    const double* keepM = p.stepM + ((size_t)b * H + t) * D;
-    const double* keepV = p.stepV + ((size_t)b * H + t) * (FB ? n * D : DD);
+    const double* keepM = p.keepM + ((size_t)b * H + t) * D;
+    const double* keepV = p.keepV + ((size_t)b * H + t) * (FB ? n * D : DD);
     for (int i = lane; i < D; i += 64) s_M[i] = keepM[i];
     if constexpr (FB) {
         for (int idx = lane; idx < n * D; idx += 64) s_V[idx / D][idx % D] = keepV[idx];
@@ -877,25 +483,6 @@ __global__ __launch_bounds__(64) void rollout_linear_bwd_reverse_kernel(std::con
     if (p.include_time && lane == 0) xq[E - 1] = p.time0 + (double)t;
 }
 
-template <int EP>
-void launch_tiles_ep(const LbTileArgs& p, bool kloop, bool bwd, hipStream_t s) {
-    const dim3 grid((p.rows + kBM - 1) / kBM, p.nCB, p.D);
-    if (bwd) {
-        if (kloop) hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, true, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, false, true>), grid, dim3(256), 0, s, p);
-    } else {
-        if (kloop) hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, true, false>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((lin_bwd_tile_kernel<EP, false, false>), grid, dim3(256), 0, s, p);
-    }
-}
-
-void launch_tiles(const LbTileArgs& p, bool kloop, bool bwd, hipStream_t s) {
-    if (p.E <= 4) launch_tiles_ep<4>(p, kloop, bwd, s);
-    else if (p.E <= 8) launch_tiles_ep<8>(p, kloop, bwd, s);
-    else if (p.E <= 16) launch_tiles_ep<16>(p, kloop, bwd, s);
-    else launch_tiles_ep<24>(p, kloop, bwd, s);
-}
-
 }  // namespace
 
 int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, int P, const double* Mb, const double* Sb,
@@ -916,7 +503,7 @@ int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, 
     int rc = grow(h, h->linbws, pl.total);
     if (rc) return rc;
     double* ws = h->linbws.p;
-    LbTileArgs p{};
+    LinTileArgs p{};
     p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.beta = h->beta.p; p.iK = h->iK.p;
     p.part = ws + pl.part; p.coef = ws + pl.coef;
     p.N = N; p.E = E; p.D = D; p.nCB = pl.nCB; p.NW = pl.NW; p.Mc = pl.Mc;
@@ -927,7 +514,7 @@ int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, 
         const int rows = (int)((P - m0) < pl.chunk ? (P - m0) : pl.chunk);
         p.rows = rows;
         p.Xq = mu + (size_t)m0 * E;
-        launch_tiles(p, false, false, s);            // M and the Jacobian sums: no matrix product
+        launch_lin_tiles<false>(p, false, s);        // M and the Jacobian sums: no matrix product
         f.Sig = Sig ? Sig + (size_t)m0 * E * E : nullptr;
         f.Mb = Mb ? Mb + (size_t)m0 * D : nullptr;
         f.Sb = Sb ? Sb + (size_t)m0 * D * D : nullptr;
@@ -936,7 +523,7 @@ int run_moments_linear_backward(Handle* h, const double* mu, const double* Sig, 
         f.mu_bar = mb_out ? mb_out + (size_t)m0 * E : nullptr;
         hipLaunchKernelGGL(lin_bwd_point_kernel, dim3(rows), dim3(64), 0, s, f);
         if (mb_out) {
-            launch_tiles(p, Sb != nullptr, true, s);
+            launch_lin_tiles<true>(p, Sb != nullptr, s);
             hipLaunchKernelGGL(lin_bwd_finish_kernel, dim3(rows), dim3(64), 0, s, f);
         }
     }
@@ -948,8 +535,8 @@ namespace {
 
 // a: filled by the entry point (model, cost settings, actions, shape, initial state); sd: the cotangents and initial-state outputs.
 // gains != NULL: the closed loop (gains (B, H, A, D) when per_candidate, else (H, A, D) shared; gains_bar (B, H, A, D) or NULL) --
-// the same plan with the action rows of V kept, the same init kernel and tile launches, with the forward, cost and reverse
-// kernels exchanged; a chunk of candidates offsets the gain pointer only when the gains are per candidate.
+// the same plan with the action rows of V kept, the same init kernel and tile launches, with the FB forms of the step and reverse
+// kernels and the closed-loop cost kernel; a chunk of candidates offsets the gain pointer only when the gains are per candidate.
 int rollout_linear_backward_chunks(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, const double* gains, bool per_candidate,
                                    double* actions_bar, double* gains_bar, hipStream_t s) {
     const int N = a.N, D = a.D, E = a.E, A = a.A, H = a.H, B = a.B;
@@ -959,14 +546,15 @@ int rollout_linear_backward_chunks(Handle* h, const RolloutArgs& a, const Rollou
     int rc = grow(h, h->linbws, pl.total);
     if (rc) return rc;
     double* ws = h->linbws.p;
-    LbTileArgs p{};
+    LinTileArgs p{};
     p.Xt = h->Xt.p; p.ils2 = h->ils2.p; p.var = h->var.p; p.beta = h->beta.p; p.iK = h->iK.p;
     p.part = ws + pl.part; p.coef = ws + pl.coef; p.Xq = ws + pl.xq;
     p.N = N; p.E = E; p.D = D; p.nCB = pl.nCB; p.NW = pl.NW; p.Mc = pl.Mc;
-    LbFbArgs q{};                                     // (the open-loop kernels take its LbRollArgs part)
+    LbRollArgs q{};
+    const LinStepArgs& fq = q;                        // the forward's kernels take its LinStepArgs part
     q.gain_stride = per_candidate ? (long long)H * A * D : 0;
     q.part = p.part; q.ils2 = p.ils2; q.var = p.var; q.cost = a.cost;
-    q.mu = ws + pl.mu; q.Sig = ws + pl.Sig; q.stepM = ws + pl.stepM; q.stepV = ws + pl.stepV; q.cv = ws + pl.cv;
+    q.mu = ws + pl.mu; q.Sig = ws + pl.Sig; q.keepM = ws + pl.stepM; q.keepV = ws + pl.stepV; q.cv = ws + pl.cv;
     q.adj = ws + pl.adj; q.coef = ws + pl.coef; q.base = ws + pl.base; q.Xq = ws + pl.xq;
     q.E = E; q.D = D; q.A = A; q.H = H; q.nCB = pl.nCB; q.NW = pl.NW; q.Mc = pl.Mc;
     q.include_time = a.include_time; q.time0 = a.time0; q.kappa = a.kappa; q.use_constraints = a.use_constraints;
@@ -994,12 +582,12 @@ int rollout_linear_backward_chunks(Handle* h, const RolloutArgs& a, const Rollou
         q.sd.S0_bar = sd.S0_bar ? sd.S0_bar + o * D * D : nullptr;
         // the forward, recomputed
         q.t = 0;
-        hipLaunchKernelGGL(rollout_linear_bwd_init_kernel, dim3(rows), dim3(64), 0, s, static_cast<const LbRollArgs&>(q));
+        hipLaunchKernelGGL(rollout_linear_init_kernel, dim3(rows), dim3(64), 0, s, fq);
         for (int t = 0; t < H; ++t) {
-            launch_tiles(p, true, false, s);
+            launch_lin_tiles<false>(p, true, s);
             q.t = t;
-            if (fb) hipLaunchKernelGGL(rollout_linear_fb_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, q);
-            else hipLaunchKernelGGL(rollout_linear_bwd_forward_kernel, dim3(rows), dim3(64), 0, s, static_cast<const LbRollArgs&>(q));
+            if (fb) hipLaunchKernelGGL(rollout_linear_step_kernel<true>, dim3(rows), dim3(64), 0, s, fq);
+            else hipLaunchKernelGGL(rollout_linear_step_kernel<false>, dim3(rows), dim3(64), 0, s, fq);
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());
         if (sd.J && fb) {                             // the objective's weights need the (closed-loop) cost variances
@@ -1017,7 +605,7 @@ int rollout_linear_backward_chunks(Handle* h, const RolloutArgs& a, const Rollou
         // the reverse sweep
         launch_reverse(-1, H - 1);
         for (int t = H - 1; t >= 0; --t) {
-            launch_tiles(p, true, true, s);
+            launch_lin_tiles<true>(p, true, s);
             launch_reverse(t, t - 1);
         }
         GPMPC_HIP_CHECK(h, hipGetLastError());

@@ -5,10 +5,12 @@
 #pragma once
 #include <cstddef>
 
+#include "moments_linear_plan.h"
+
 namespace gpmpc_hip {
 
-constexpr int kLinBwdBM = 64;                              // query rows per workgroup of the tile kernel
-constexpr int kLinBwdBN = 256;                             // columns of iK per workgroup
+constexpr int kLinBwdBM = kLinBM;                          // the forward's tile (one tile kernel serves both): query rows per workgroup
+constexpr int kLinBwdBN = kLinBN;                          // ... and columns of iK per workgroup
 constexpr size_t kLinBwdWsBudget = (size_t)16 << 20;       // bytes of workspace per chunk (or one 64-row tile's need if that is more)
 
 struct LinearBwdPlan {

@@ -27,7 +27,8 @@ __device__ inline void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, un
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
 
-// Philox4x32-10: two uniform doubles in (0, 1) from (counter, key)
+// Philox4x32-10: two uniform doubles in (0, 1] from (counter, key).  x = 2^53 - 1 gives exactly 1.0 ((double)x + 0.5 rounds to
+// 2^53), which is harmless: log(1) = 0 and 1.0 lies inside the box; x = 0 gives 2^-54, so the logarithm is always finite.
 __device__ inline void philox_uniform2(unsigned long long seed, unsigned a, unsigned b, unsigned c, double& u0, double& u1) {
     unsigned c0 = a, c1 = b, c2 = c, c3 = 0x9E3779B9u;
     unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);

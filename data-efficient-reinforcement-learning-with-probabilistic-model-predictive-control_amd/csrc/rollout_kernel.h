@@ -444,31 +444,66 @@ __device__ inline double item_exp(const double* rec, int nrows, const double (&w
     return acc;
 }
 
+// The T rows of one two-column item, addressed the scalar way: the T tables of all outputs are ONE buffer resource (SGPRs), the
+// lane keeps a single 32-bit byte offset for the whole item -- (output a, first row i0 of the lane's chunk, column j): everything
+// that differs between lanes -- and the row inside the chunk is the instruction's scalar offset, advanced on the scalar ALU.
+// (As `Tp[(size_t)u * N]` with a per-lane 64-bit Tp every trip formed its addresses with three 64-bit vector adds, and every
+// item's set-up multiplied them out in 64 bits.)  Every read lies inside the allocation (see item_taylor2 on the rows read
+// ahead); the resource's bound is a net under that, not something the loops rely on.  The fused-horizon kernel keeps the row
+// records of a pair in LDS, so N is a few thousand at most and the tables stay far below the 4 GB a 32-bit offset spans.
+struct TRows {
+    __amdgpu_buffer_rsrc_t rs;      // the whole Tm allocation, (D, N + kTPad, N) doubles
+    unsigned voff;                  // byte offset of T_a[i0][j] in it (per lane)
+    unsigned row_bytes;             // N * 8
+};
+__device__ inline TRows make_t_rows(const double* Tm, int D, int N, int a, int i0, int j) {
+    TRows t;
+    t.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(Tm), 0, D * (N + kTPad) * N * 8, 0x00020000);
+    t.voff = (unsigned)(((a * (N + kTPad) + i0) * N + j) * 8);
+    t.row_bytes = (unsigned)N * 8u;
+    return t;
+}
+// columns j, j + 1 of the row `soff` bytes (wave-uniform) behind the lane's first: one 16-byte read (8-byte aligned for odd N)
+__device__ inline void t_row_pair(const TRows& t, unsigned soff, double& x0, double& x1) {
+    const lds_d2 v = __builtin_bit_cast(lds_d2, __builtin_amdgcn_raw_buffer_load_b128(t.rs, t.voff, soff, 0));
+    x0 = v.x; x1 = v.y;
+}
+
 // Two columns per lane (j, j + 1): the row operands (ev_i, g_i) are LDS broadcasts whose return bandwidth, not the
 // VALU, bounds the one-column loop at small D (32 bytes per lane and row for 12 FMAs); serving two columns per read
 // halves that traffic.  Two rows x two columns in flight = the same four independent chains as the one-column loop.
-// U = rows per trip = depth of the T prefetch.  With the tables in L2 (configs 1-3) two rows ahead are enough and the
-// shorter trip is 2 % faster; at config 4 (N = 1000, D = 4) the loads come from the Infinity Cache and four rows ahead gain
+// U = rows per trip = T rows requested together.  With the tables in L2 (configs 1-3) two rows are enough and the
+// shorter trip is 2 % faster; at config 4 (N = 1000, D = 4) the loads come from the Infinity Cache and four rows per trip gain
 // 5 % (115.2 -> 109.2 ms); eight rows spill and lose.
+// The prefetch (U = 2): the diagonal loop runs its trips in PAIRS over two register sets -- the T rows of trip i + 1 are requested before
+// the arithmetic of trip i and consumed one trip later, behind a counted wait (vmcnt(U), not 0).  What keeps it in the compiled
+// loop: the reads are buffer builtins, which the optimiser's load forwarding does not look through (written as plain loads with a
+// `t <- next` rotation, the rotation was folded into loads at the top of the trip that used them: one exposed L2 round trip per
+// trip), and the two sets are written out, so no register copy stands where the rotation was.  A pair also advances the record
+// pointer once, its second trip reading at immediate offsets.
+// Rows read ahead and never used: at most U rows behind the item's last trip, i.e. row index < i0 + nrows + U <= N + 3 + U of
+// output a -- inside the kTPad (72) zero rows that follow every output's table, the last output's included.  (U = 4, DP >= 4:
+// no read-ahead, see below; the last row read is i0 + nrows - 1 <= N + 2.)
 template <int DP, int K, int U, class REC = RowRecAligned<DP>>
 __device__ inline void item_taylor2(const double* rec, int nrows, const double (&w0)[DP], const double (&w1)[DP], bool diag,
-                                    const double* Tp, int N, double& acc0, double& acc1) {
+                                    const TRows& t, double& acc0, double& acc1) {
     constexpr int RS = REC::RS;
+    static_assert(3 + U < kTPad, "the rows read ahead must stay in the zero rows behind a table");
     acc0 = 0.0;
     acc1 = 0.0;
     if (diag) {
-        double t0[U], t1[U];
+        unsigned so = 0;            // scalar byte offset of the next trip to request
+        auto request = [&](double (&x0)[U], double (&x1)[U]) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) { t0[u] = Tp[(size_t)u * N]; t1[u] = Tp[(size_t)u * N + 1]; }
-        for (int it = 0; it < nrows; it += U) {
-            double n0[U], n1[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) { n0[u] = Tp[(size_t)(U + u) * N]; n1[u] = Tp[(size_t)(U + u) * N + 1]; }
+            for (int u = 0; u < U; ++u) t_row_pair(t, so + (unsigned)u * t.row_bytes, x0[u], x1[u]);
+            so += (unsigned)U * t.row_bytes;
+        };
+        auto trip = [&](const double* rc, const double (&x0)[U], const double (&x1)[U]) {
             double c0[U], c1[U], ev[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 double r[RS];
-                REC::template load<(REC::EA > REC::G ? REC::EA + 1 : REC::G + DP)>(rec + u * RS, r);
+                REC::template load<(REC::EA > REC::G ? REC::EA + 1 : REC::G + DP)>(rc + u * RS, r);
                 double a = r[REC::G] * w0[0], b = r[REC::G] * w1[0];
 #pragma unroll
                 for (int d = 1; d < DP; ++d) { a = fma(r[REC::G + d], w0[d], a); b = fma(r[REC::G + d], w1[d], b); }
@@ -477,13 +512,30 @@ __device__ inline void item_taylor2(const double* rec, int nrows, const double (
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                acc0 = fma(taylor_exp<K>(c0[u]) * ev[u], t0[u], acc0);
-                acc1 = fma(taylor_exp<K>(c1[u]) * ev[u], t1[u], acc1);
+                acc0 = fma(taylor_exp<K>(c0[u]) * ev[u], x0[u], acc0);
+                acc1 = fma(taylor_exp<K>(c1[u]) * ev[u], x1[u], acc1);
             }
+        };
+        if constexpr (U == 2) {
+            double p0[U], p1[U], q0[U], q1[U];
+            request(p0, p1);
+            for (int it = 0; it < nrows; it += 2 * U) {         // (nrows is a multiple of 4: every pair is whole)
+                request(q0, q1);                                // trip it + U: in flight during trip it
+                trip(rec, p0, p1);
+                request(p0, p1);                                // trip it + 2 U
+                trip(rec + U * RS, q0, q1);
+                rec += 2 * U * RS;
+            }
+        } else {
+            // four rows per trip (DP >= 4): a second set of 16 registers is not there -- the 1024-thread workgroups of these
+            // widths live at the 128-register limit -- so a trip requests its own rows at its top
+            for (int it = 0; it < nrows; it += U) {
+                double p0[U], p1[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) { t0[u] = n0[u]; t1[u] = n1[u]; }
-            rec += U * RS;
-            Tp += (size_t)U * N;
+                for (int u = 0; u < U; ++u) t_row_pair(t, (unsigned)(it + u) * t.row_bytes, p0[u], p1[u]);
+                trip(rec, p0, p1);
+                rec += U * RS;
+            }
         }
     } else {
         for (int it = 0; it < nrows; it += U) {
@@ -510,11 +562,13 @@ __device__ inline void item_taylor2(const double* rec, int nrows, const double (
 
 template <int DP, class REC = RowRecAligned<DP>>
 __device__ inline void item_exp2(const double* rec, int nrows, const double (&w0)[DP], const double (&w1)[DP], double kb0,
-                                 double kb1, bool diag, const double* Tp, int N, const double* tab, double& acc0, double& acc1) {
+                                 double kb1, bool diag, const TRows& t, const double* tab, double& acc0, double& acc1) {
     constexpr int RS = REC::RS;
     constexpr int U = 2;
     acc0 = 0.0;
     acc1 = 0.0;
+    // (no read-ahead here: a trip's T rows are requested at its top and first used behind the exponentials, ~100 instructions on)
+    unsigned so = 0;
     for (int it = 0; it < nrows; it += U) {
         double a0[U], a1[U], wt0[U], wt1[U];
 #pragma unroll
@@ -525,8 +579,8 @@ __device__ inline void item_exp2(const double* rec, int nrows, const double (&w0
 #pragma unroll
             for (int d = 0; d < DP; ++d) { x = fma(r[REC::G + d], w0[d], x); y = fma(r[REC::G + d], w1[d], y); }
             a0[u] = x; a1[u] = y;
-            wt0[u] = diag ? Tp[(size_t)u * N] : r[REC::RA];
-            wt1[u] = diag ? Tp[(size_t)u * N + 1] : r[REC::RA];
+            if (diag) t_row_pair(t, so + (unsigned)u * t.row_bytes, wt0[u], wt1[u]);
+            else { wt0[u] = r[REC::RA]; wt1[u] = r[REC::RA]; }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -534,7 +588,7 @@ __device__ inline void item_exp2(const double* rec, int nrows, const double (&w0
             acc1 = fma(fast_exp(a1[u], tab), wt1[u], acc1);
         }
         rec += U * RS;
-        Tp += (size_t)U * N;
+        so += (unsigned)U * t.row_bytes;
     }
 }
 
@@ -706,8 +760,15 @@ __device__ __attribute__((noinline)) void sep3_item(int band, int lane, int N, i
 // stores {tag | low word}, {tag | high word} per value: each half is single-copy atomic, a reader accepts a value when both tags
 // are this step's -- no fences, MI355X_MICROARCH.md "handoff-1to1").  Every value is formed by the same instruction sequence as in
 // the plain kernel and summed in the same order: the trajectory is bit-identical to the one-workgroup result.
+// Four wavefronts per SIMD (<= 128 registers) is what a 1024-thread workgroup needs anyway; the narrower workgroups of DP = 2 and of
+// the plain DP = 3 form rely on it too (two 512-thread or four 256-thread workgroups per CU) and sat just below 128 by themselves
+// until the read-ahead's second register set: the bound keeps them there (no scratch: profiles/item_loop_resource_usage_new.txt).
+// The wider ones (DP >= 4, the cooperative DP = 3 form) never fitted and keep their free allocation.
+template <int DP, bool CL>
+constexpr int rollout_min_waves() { return (DP == 2 || (DP == 3 && !CL)) ? 4 : 1; }
+
 template <int DP, int NT, int DX, bool C2, bool TILED = false, bool CL = false>
-__global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
+__global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_kernel(const RolloutArgs p) {
     static_assert(!TILED || (DP <= 4 && NT >= 256), "the batch-major path is built for D <= 4");
     static_assert(!CL || (!TILED && DP <= 4 && NT >= 256), "the cooperative form is built for D <= 4");
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1661,8 +1722,9 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
                     const int sle = CL ? (Kraw >> 8) - 1 : gq;
                     const double kbj = a_kb[sle * N + j];
                     const double* rec = a_rows + ((size_t)sle * NR + i0) * RS;
-                    const double* Tp = p.Tm + ((size_t)a * (N + kTPad) + i0) * N + j;
+                    [[maybe_unused]] const double* Tp = p.Tm + ((size_t)a * (N + kTPad) + i0) * N + j;     // (one-column loops)
                     if constexpr (C2) {
+                        const TRows trows = make_t_rows(p.Tm, D, N, a, i0, j);
                         // second column: always read (jl is a valid column) and masked by a factor -- four `valid1 ? load : 0`
                         // became four exec-mask branches with a wait each in every item's set-up
                         double w1[DP];
@@ -1672,22 +1734,22 @@ __global__ __launch_bounds__(NT) void rollout_kernel(const RolloutArgs p) {
                         const double kb1 = a_kb[sle * N + jl] * m1;
                         double acc0, acc1;
                         if (K == 0) {
-                            item_exp2<DP>(rec, nrows, w, w1, kbj, kb1, diag, Tp, N, c_exptab, acc0, acc1);
+                            item_exp2<DP>(rec, nrows, w, w1, kbj, kb1, diag, trows, c_exptab, acc0, acc1);
                             acc = acc0 * (diag ? 2.0 : p.beta[b * N + j]) + (valid1 ? acc1 * (diag ? 2.0 : p.beta[b * N + j + 1]) : 0.0);
                         } else {
-                            // rows per trip = depth of the T prefetch (see item_taylor2): 4 from DP = 4 up.  One
+                            // rows per trip (see item_taylor2): 4 from DP = 4 up, 2 with the T read-ahead below that.  One
                             // instantiation per degree: a second one (choice by N) cost config 2 2.7 % through the larger kernel.
                             constexpr int TU = DP >= 4 ? 4 : 2;       // (the cooperative form measured the same with 2, 4, 8: its items are bound by their set-up)
-                            if (K <= 2) item_taylor2<DP, 2, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 3) item_taylor2<DP, 3, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 4) item_taylor2<DP, 4, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 5) item_taylor2<DP, 5, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 6) item_taylor2<DP, 6, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 7) item_taylor2<DP, 7, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K == 8) item_taylor2<DP, 8, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K <= 10) item_taylor2<DP, 10, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else if (K <= 12) item_taylor2<DP, 12, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
-                            else item_taylor2<DP, 14, TU>(rec, nrows, w, w1, diag, Tp, N, acc0, acc1);
+                            if (K <= 2) item_taylor2<DP, 2, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 3) item_taylor2<DP, 3, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 4) item_taylor2<DP, 4, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 5) item_taylor2<DP, 5, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 6) item_taylor2<DP, 6, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 7) item_taylor2<DP, 7, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K == 8) item_taylor2<DP, 8, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K <= 10) item_taylor2<DP, 10, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else if (K <= 12) item_taylor2<DP, 12, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
+                            else item_taylor2<DP, 14, TU>(rec, nrows, w, w1, diag, trows, acc0, acc1);
                             acc = fma(acc0, kbj, acc1 * kb1) * (diag ? 2.0 : 1.0);
                         }
                     } else if (K == 0) {

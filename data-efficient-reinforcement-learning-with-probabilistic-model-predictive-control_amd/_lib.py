@@ -39,6 +39,7 @@ SIGNATURES = {
     "gpmpc_prepare": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "gpmpc_prepare_sparse": (C.c_int, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _D, _I, _I, _P]),
     "gpmpc_sparse_append": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    "gpmpc_sparse_forget": (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "gpmpc_select_inducing": (C.c_int, [_P, _P, _I, _I, _P, _P, _D, _I, _I, _P, _P, _P, _P]),
     "gpmpc_set_factors": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "gpmpc_get_factors": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
@@ -79,7 +80,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 
 def load(path=LIB_PATH):

@@ -160,7 +160,7 @@ class ModelConfig:
                  min_outputscale=1e-5, max_outputscale=0.95, min_lengthscale=4e-3, max_lengthscale=25.0,
                  min_lengthscale_time=10, max_lengthscale_time=10000, include_time_model=False,
                  uncertainty_propagation="moment_matching", num_inducing_points=None, inducing_jitter=1e-6,
-                 inducing_selection="strided", inducing_refresh_every=None):
+                 inducing_selection="strided", inducing_refresh_every=None, inducing_forget=False):
         """num_inducing_points: None (the exact GP on the whole memory), or M >= 1 -- once the memory holds more than M points
         the model predicts with a sparse GP (DTC / projected process, gpmpc_prepare_sparse) on M inducing inputs, the rows
         round(i (N - 1) / (M - 1)), i = 0..M-1, of the N-point memory (M = 1: row 0): every prediction, rollout and gradient
@@ -175,6 +175,13 @@ class ModelConfig:
         unchanged hyper-parameters, appends them to the cached sparse model in O(k M^2) (gpmpc_sparse_append: same inducing
         inputs) as long as no more than R rows have been appended since the last rebuild; the rebuild then chooses the
         inducing inputs afresh.  Rounding does not limit R; the age of the inducing inputs does.
+        inducing_forget: False (`forget` is refused on a sparse model, and the evictions of a capped memory rebuild it every
+        step), or True -- together with inducing_refresh_every = R, `forget` removes the rows from the cached sparse model in
+        O(k M^2) (gpmpc_sparse_forget: same inducing inputs, the rows' values leave by the append's recurrence with the
+        opposite sign), so a sliding-window step (MemoryConfig.max_points_model) is forget + append in place of a rebuild from
+        all N points.  Removed rows count toward R together with appended ones: R is then "rows changed since the last
+        rebuild".  Here rounding does limit R: a removal subtracts, and loses digits when most of the data behind an
+        inducing input has left.
         uncertainty_propagation: how an uncertain state goes through the GP -- "moment_matching" (the reference's exact
         moment matching, gp_model.py:112-180) or "linearized" (first-order Taylor propagation at the input mean,
         gpmpc_moments_linear / gpmpc_rollout_linear: no D^2 pair pass, but a different approximation)."""
@@ -196,6 +203,9 @@ class ModelConfig:
                                                    or int(inducing_refresh_every) < 1):
             raise ValueError(f"ModelConfig.inducing_refresh_every={inducing_refresh_every!r}: None or a positive number of rows")
         self.inducing_refresh_every = None if inducing_refresh_every is None else int(inducing_refresh_every)
+        if not isinstance(inducing_forget, bool):
+            raise ValueError(f"ModelConfig.inducing_forget={inducing_forget!r}: True or False")
+        self.inducing_forget = inducing_forget
         if gp_init is None:
             gp_init = {"noise_covar.noise": [1e-4] * 3, "base_kernel.lengthscale": [[0.75] * 4] * 3,
                        "outputscale": [5e-2] * 3}

@@ -136,6 +136,20 @@ def inducing_rows(N, M):
     return [int(round(i * (N - 1) / (M - 1))) for i in range(M)]
 
 
+def _renumber_inducing(inducing_idx, gone):
+    """`inducing_idx` (a list, or an int32 device tensor) after the ascending memory rows `gone` have left: every entry moves down
+    by the number of departed rows below it; an entry whose own row has left -- or had left before -- is -1."""
+    if isinstance(inducing_idx, torch.Tensor):
+        gone_t = torch.as_tensor(np.asarray(gone), dtype=torch.long, device=inducing_idx.device)
+        old = inducing_idx.to(torch.long)
+        new = torch.where(torch.isin(old, gone_t) | (old < 0), torch.full_like(old, -1), old - torch.searchsorted(gone_t, old))
+        return new.to(inducing_idx.dtype)
+    gone = np.asarray(gone, dtype=np.int64)
+    old = np.asarray(inducing_idx, dtype=np.int64)
+    new = np.where(np.isin(old, gone) | (old < 0), -1, old - np.searchsorted(gone, old))
+    return [int(v) for v in new]
+
+
 def _no_linearized_autograd(what, *tensors):
     """The linearised propagation has no backward kernels: refuse rather than return tensors without a grad_fn."""
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
@@ -333,7 +347,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self._cost_key = None
         self.is_sparse = False          # the cached model is the sparse one of gpmpc_prepare_sparse
         self.inducing_idx = None        # rows of the memory its inducing inputs are: a list (strided), a device tensor (greedy), or None
-        self._sparse_record = None      # ModelConfig.inducing_refresh_every: hyper-parameters of the last sparse prepare, rows appended since
+        self._sparse_record = None      # ModelConfig.inducing_refresh_every: hyper-parameters of the last sparse prepare, rows changed since
 
     last_training_launches = None       # gpmpc_mll calls of the last `train` in this process (lockstep: ~ the longest GP's count)
 
@@ -378,9 +392,9 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         y_mem are the whole memory either way: training and save_state see all of it.
         With ModelConfig.inducing_refresh_every = R the sparse model the config chose is not rebuilt when the memory only grew:
         if `inputs` / `state_changes` are the previous memory followed by k >= 1 rows (compared by value), the hyper-parameters
-        are those of the last sparse prepare and no more than R rows have been appended since it, the k rows go through
-        gpmpc_sparse_append (O(k M^2), same inducing inputs, `inducing_idx` kept); with k = 0 no call is made at all.  Anything
-        else -- and an engine that answers the append with GPMPC_ERR_ARG -- rebuilds as above and starts the count again."""
+        are those of the last sparse prepare and no more than R rows have been appended (or, with inducing_forget, forgotten)
+        since it, the k rows go through gpmpc_sparse_append (O(k M^2), same inducing inputs, `inducing_idx` kept); with k = 0 no
+        call is made at all.  Anything else -- and an engine that answers the append with GPMPC_ERR_ARG -- rebuilds as above and starts the count again."""
         if inducing_inputs is None and self._try_sparse_append(inputs, state_changes):
             return
         self._sparse_record = None
@@ -401,7 +415,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
             self.engine.prepare_sparse(inputs, state_changes, inducing_inputs, self.lengthscales, self.variances, self.noises,
                                        getattr(self.config, "inducing_jitter", 1e-6))
             if self.inducing_idx is not None and getattr(self.config, "inducing_refresh_every", None) is not None:
-                self._sparse_record = {"hyp": self._hyper_parameters(), "appended": 0}
+                self._sparse_record = {"hyp": self._hyper_parameters(), "changed": 0}
         else:
             self.engine.prepare(inputs, state_changes, self.lengthscales, self.variances, self.noises)
 
@@ -424,7 +438,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         if not (torch.equal(x_new[:n_prev].cpu(), x_old.cpu()) and torch.equal(y_new[:n_prev].cpu(), y_old.cpu())):
             return False
         if k > 0:
-            if rec["appended"] + k > R:
+            if rec["changed"] + k > R:
                 return False
             from ..._lib import GPMPC_ERR_ARG, GpmpcError
             try:
@@ -433,7 +447,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                 if e.code != GPMPC_ERR_ARG:
                     raise
                 return False                     # the engine holds no record (any more): rebuild
-            rec["appended"] += k
+            rec["changed"] += k
         self.x_mem = inputs
         self.y_mem = state_changes
         return True
@@ -444,19 +458,66 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         A prepare_inference of the reduced memory plus a few appended points is then a border update, not a factorisation.
         A sparse model (ModelConfig.num_inducing_points) has no downdate -- its factors condense all memory points into the
         inducing ones: GpmpcError(GPMPC_ERR_ARG), with the model and x_mem / y_mem untouched; call prepare_inference on the
-        reduced memory instead (the controller does: a capped memory re-prepares its window)."""
+        reduced memory instead (the controller does: a capped memory re-prepares its window).
+        With ModelConfig.inducing_forget = True and inducing_refresh_every = R the sparse model the config chose does have one:
+        under the hyper-parameters of its last rebuild, fewer rows than the memory holds leave it through gpmpc_sparse_forget
+        (O(k M^2), by their values, same inducing inputs) as long as no more than R rows have been appended or forgotten since
+        that rebuild -- past R no call is made and GpmpcError(GPMPC_ERR_ARG) is raised as above, so that the caller's
+        prepare_inference rebuilds: that is the refresh.  `inducing_idx` keeps its kind and is renumbered to the reduced memory,
+        with -1 for an inducing input whose memory row has left (the input itself stays).  Where the engine loses a pivot
+        (GPMPC_ERR_NOT_PD: it then holds no model) the rows leave x_mem / y_mem all the same and the model of the reduced memory is
+        rebuilt by prepare_inference: the caller sees a successful forget.  An engine without a record re-raises its
+        GPMPC_ERR_ARG with the memory untouched."""
         if self.x_mem is None:
             raise RuntimeError("call prepare_inference(inputs, state_changes) before forget")
         if getattr(self, "is_sparse", False):
-            from ..._lib import GPMPC_ERR_ARG, GpmpcError
-            raise GpmpcError(GPMPC_ERR_ARG, "forget: the cached model is sparse (ModelConfig.num_inducing_points) and has no "
-                             "downdate; call prepare_inference on the reduced memory")
+            return self._sparse_forget(indices)
         idx = np.asarray(indices).reshape(-1)
         self.engine.forget(idx)
         keep = torch.ones(len(self.x_mem), dtype=torch.bool)
         keep[torch.as_tensor(idx, dtype=torch.long)] = False
         self.x_mem = _t(self.x_mem)[keep]
         self.y_mem = _t(self.y_mem)[keep]
+
+    def _sparse_forget(self, indices):
+        """`forget` on a sparse model: the policy of ModelConfig.inducing_forget (see forget)."""
+        from ..._lib import GPMPC_ERR_ARG, GPMPC_ERR_NOT_PD, GpmpcError
+        rec = getattr(self, "_sparse_record", None)
+        R = getattr(self.config, "inducing_refresh_every", None)
+        if not getattr(self.config, "inducing_forget", False) or R is None or rec is None:
+            raise GpmpcError(GPMPC_ERR_ARG, "forget: the cached model is sparse (ModelConfig.num_inducing_points) and has no "
+                             "downdate; call prepare_inference on the reduced memory")
+        idx = np.asarray(indices).reshape(-1)
+        n, k = len(self.x_mem), int(idx.size)
+        if k and not np.issubdtype(idx.dtype, np.integer):
+            raise TypeError("forget: indices must be integers")
+        if k < 1 or k >= n or idx[0] < 0 or idx[-1] >= n or np.any(np.diff(idx) <= 0):
+            raise GpmpcError(GPMPC_ERR_ARG, "forget: need 1 <= k < N strictly ascending rows in [0, N)")
+        if not all(torch.equal(a, b) for a, b in zip(rec["hyp"], self._hyper_parameters())):
+            raise GpmpcError(GPMPC_ERR_ARG, "forget: the hyper-parameters changed since the sparse model was built; call "
+                             "prepare_inference on the reduced memory")
+        if rec["changed"] + k > R:
+            raise GpmpcError(GPMPC_ERR_ARG, f"forget: more than inducing_refresh_every = {R} rows changed since the sparse model "
+                             "was built; call prepare_inference on the reduced memory")
+        x_mem, y_mem = _t(self.x_mem), _t(self.y_mem)
+        rows = torch.as_tensor(idx, dtype=torch.long)
+        keep = torch.ones(n, dtype=torch.bool)
+        keep[rows] = False
+        rows, keep = rows.to(x_mem.device), keep.to(x_mem.device)
+        lost_pivot = False
+        try:
+            self.engine.sparse_forget(x_mem[rows], y_mem[rows])
+        except GpmpcError as e:
+            if e.code != GPMPC_ERR_NOT_PD:
+                raise                                # GPMPC_ERR_ARG: no record -- the memory stays, as on the exact path
+            lost_pivot = True
+        if lost_pivot:                               # the engine holds no model: the reduced memory through the full path
+            self._sparse_record = None
+            self.prepare_inference(x_mem[keep], y_mem[keep])
+            return
+        self.x_mem, self.y_mem = x_mem[keep], y_mem[keep]
+        rec["changed"] += k
+        self.inducing_idx = _renumber_inducing(self.inducing_idx, idx)
 
     def set_cost(self, reward_config):
         """Load the quadratic-cost / LCB settings into the engine.  The reference reads its reward config on every
@@ -641,7 +702,7 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                           constraints_hyperparams={k: v for k, v in vars(self.config).items()
                                                    if k not in ("gp_init", "uncertainty_propagation", "num_inducing_points",
                                                                 "inducing_jitter", "inducing_selection",
-                                                                "inducing_refresh_every")})
+                                                                "inducing_refresh_every", "inducing_forget")})
 
     def load_state(self, saved_state):
         for m, p in zip(self.models, saved_state.parameters):

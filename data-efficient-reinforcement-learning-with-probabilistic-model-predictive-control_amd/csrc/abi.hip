@@ -55,7 +55,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 23; }
+int gpmpc_abi_version(void) { return 24; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -83,7 +83,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spfg};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -815,6 +815,18 @@ int gpmpc_sparse_append(gpmpc_t* g, const double* Xnew, const double* Ynew, int 
     if (D != h->D || E != h->E) return bad(g, "sparse_append: D and E must be those of the cached sparse model");
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_sparse_append(h, Xnew, Ynew, k, (hipStream_t)stream);
+}
+
+int gpmpc_sparse_forget(gpmpc_t* g, const double* Xold, const double* Yold, int k, int D, int E, void* stream) {
+    Range roctx_range("gpmpc_sparse_forget");
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready || !h->sp_have) return bad(g, "sparse_forget: the handle holds no record of a gpmpc_prepare_sparse");
+    if (!Xold || !Yold) return bad(g, "null argument");
+    if (k < 1) return bad(g, "sparse_forget: need k >= 1 points");
+    if (D != h->D || E != h->E) return bad(g, "sparse_forget: D and E must be those of the cached sparse model");
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_sparse_forget(h, Xold, Yold, k, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -300,7 +300,7 @@ struct Handle {
     int opt_prepare_overlap = 1;     // 32-wide panel path: the inverse's launches on a side stream beside the factorisation's (0: one stream, A/B)
     int opt_gram_shared = 1;         // large N: K of all GPs by one workgroup per tile, squared differences shared (0: per-GP kernel, A/B)
     int opt_fused_prepare = 1;       // N <= 256: the whole factorisation in one launch (prepare_small.hip); 0: panel path (A/B, tests)
-    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget), 4 sparse (gpmpc_prepare_sparse), 5 sparse append (gpmpc_sparse_append)
+    int last_prepare_mode = 0;       // 0 full, 1 border update(s), 2 unchanged (cache hit), 3 downdate (gpmpc_forget), 4 sparse (gpmpc_prepare_sparse), 5 sparse append (gpmpc_sparse_append), 6 sparse forget (gpmpc_sparse_forget)
     int opt_sparse_chunk = 0;        // gpmpc_prepare_sparse: memory points per chunk (0: as many as a 64 MB workspace holds; else a multiple of 64)
     long long opt_select_max_mb = 0; // gpmpc_select_inducing: cap on its workspace in MiB (0: 4096)
     int opt_predict_chunk = 0;       // gpmpc_predict: query rows per chunk (0: as many as a 4 MB workspace holds; tests set a small one)
@@ -316,6 +316,7 @@ struct Handle {
     Buf sprec;    // gpmpc_sparse_append: the record of the last gpmpc_prepare_sparse (Yb | w | noises) | vectors of the point at hand (sparse_append_plan.h)
     bool sp_have = false;        // ... is there: Yu at spws + sp_yu, Yb / w / noises in sprec, Z and the hyper-parameters packed in the handle
     size_t sp_yu = 0;
+    Buf spfg;     // gpmpc_sparse_forget: failure words | vectors of the point at hand (sparse_forget_plan.h)
 };
 
 // Raise a kernel's dynamic-LDS limit to the device maximum once per handle (= per device).
@@ -517,6 +518,14 @@ struct SparseAppendPlan;
 int check_sparse_append(Handle* h, const SparseAppendPlan& ap);
 int launch_sparse_append_point(Handle* h, const SparseAppendPlan& ap, const double* Yu, double* rec, const double* x, const double* y,
                                int M, int D, int E, hipStream_t s);
+// ... gpmpc_sparse_forget: the memory points of the VALUES (Xo (k, E), Yo (k, D)) leave the sparse model of the record (validated by
+// the entry point: a record, k >= 1); synchronises s and reports a lost pivot (GPMPC_ERR_NOT_PD: no model, no record)
+int run_sparse_forget(Handle* h, const double* Xo, const double* Yo, int k, hipStream_t s);
+// sparse_forget.hip: the LDS check before a call's first launch, and the two launches of point number `point` of the call
+struct SparseForgetPlan;
+int check_sparse_forget(Handle* h, const SparseForgetPlan& fp);
+int launch_sparse_forget_point(Handle* h, const SparseAppendPlan& ap, const SparseForgetPlan& fp, const double* Yu, double* rec,
+                               double* ws, const double* x, const double* y, int point, int M, int D, int E, hipStream_t s);
 // select_inducing.hip: greedy variance selection of M of the N points X as inducing inputs (validated by the entry point; Z_out and
 // trace_out may be NULL); asynchronous on s, the cached model is neither read nor written
 int run_select_inducing(Handle* h, const double* X, int N, int M, const double* ls, const double* os, double jitter_rel, int D, int E,

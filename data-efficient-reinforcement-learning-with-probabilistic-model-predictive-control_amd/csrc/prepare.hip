@@ -16,6 +16,7 @@
 #include "prepare_tiled.h"
 #include "prepare_sparse_plan.h"
 #include "sparse_append_plan.h"
+#include "sparse_forget_plan.h"
 
 namespace gpmpc_hip {
 
@@ -1813,6 +1814,49 @@ int run_sparse_append(Handle* h, const double* Xn, const double* Yn, int k, hipS
     h->ready = true;
     h->sp_have = true;
     h->last_prepare_mode = 5;
+    return GPMPC_OK;
+}
+
+// gpmpc_sparse_forget (kernels and formulas: sparse_forget.hip): the append with the opposite sign -- per point the two launches
+// of launch_sparse_forget_point, then once per call beta_eff and the T table by the launches of the append's tail.  The failure
+// words are cleared first, the stream is synchronised at the end and they are read: an output that lost its pivot stopped every
+// later launch of the forget's kernels (the tail then ran on the model of the points removed before, and is discarded), and the
+// call leaves no model and no record, as a HIP error from the first launch on does.
+int run_sparse_forget(Handle* h, const double* Xo, const double* Yo, int k, hipStream_t s) {
+    const int M = h->N, D = h->D, E = h->E;
+    SparseAppendPlan ap;
+    plan_sparse_append(M, D, ap);
+    SparseForgetPlan fp;
+    plan_sparse_forget(M, D, fp);
+    int rc;
+    if ((rc = check_sparse_forget(h, fp))) return rc;
+    if ((rc = grow(h, h->spfg, fp.total))) return rc;
+    h->ready = false;
+    h->sp_have = false;
+    const double* Yu = h->spws.p + h->sp_yu;
+    double* rec = h->sprec.p;
+    double* ws = h->spfg.p;
+    GPMPC_HIP_CHECK(h, hipMemsetAsync(ws + fp.fail, 0, kForgetFailWords * sizeof(int), s));
+    for (int q = 0; q < k; ++q)
+        if ((rc = launch_sparse_forget_point(h, ap, fp, Yu, rec, ws, Xo + (size_t)q * E, Yo + (size_t)q * D, q, M, D, E, s))) return rc;
+    if ((rc = launch_sparse_beta(h, Yu, rec + ap.yb, rec + ap.w, rec + ap.noise, M, D, ws + fp.t1, ws + fp.t2, h->beta.p, s))) return rc;
+    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
+    GPMPC_HIP_CHECK(h, hipGetLastError());
+    int fail[kForgetFailWords];
+    GPMPC_HIP_CHECK(h, hipMemcpyAsync(fail, ws + fp.fail, sizeof fail, hipMemcpyDeviceToHost, s));
+    GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
+    for (int a = 0; a < D; ++a) {
+        if (fail[a] != 0) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "sparse_forget: point %d of the call, output %d: the pivot is lost (the point is not in the model, "
+                     "or too little of the model would remain)", fail[a] - 1, a);
+            h->err = buf;
+            return GPMPC_ERR_NOT_PD;
+        }
+    }
+    h->ready = true;
+    h->sp_have = true;
+    h->last_prepare_mode = 6;
     return GPMPC_OK;
 }
 

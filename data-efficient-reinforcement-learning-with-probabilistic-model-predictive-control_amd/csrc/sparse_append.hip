@@ -21,6 +21,7 @@
 // workgroups; every sum runs in an order fixed by M, D and E alone.  The driver (run_sparse_append) is in prepare.hip.
 #include "device_common.h"
 #include "sparse_append_plan.h"
+#include "sparse_rank_one.h"
 
 // every fused multiply-add of this file is written out as fma(): the recurrence's sums round as gpmpc.h writes them
 #pragma clang fp contract(off)
@@ -28,38 +29,6 @@
 namespace gpmpc_hip {
 
 namespace {
-
-// a row of a lower-triangular matrix times x (LDS): lane-strided partial sums, then the xor tree -- every lane gets the total
-__device__ inline double row_dot(const double* __restrict__ row, const double* x, int i, int lane) {
-    double s = 0.0;
-    for (int k = lane; k <= i; k += 64) s = fma(row[k], x[k], s);
-    return wave_xor_sum(s);
-}
-
-// out = A^T x for a lower-triangular row-major A (M, M), x in LDS: work item (column tile, row group) per wavefront, lane = column,
-// rows ascending inside a group (the first row of column j is j); then the groups' partial sums in group order
-__device__ inline void trans_product(const double* __restrict__ A, const double* x, int M, int nct, int groups, int rpg,
-                                     double* part, double* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int it = wave; it < nct * groups; it += kAppendWaves) {
-        const int tile = it % nct, grp = it / nct;
-        const int j = tile * kAppendTile + lane;
-        if (j >= M) continue;
-        const int r1 = (grp + 1) * rpg < M ? (grp + 1) * rpg : M;
-        int i = grp * rpg > j ? grp * rpg : j;
-        double s = 0.0;
-#pragma unroll 4
-        for (; i < r1; ++i) s = fma(A[(size_t)i * M + j], x[i], s);
-        part[(size_t)grp * M + j] = s;
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < M; j += kAppendThreads) {
-        double s = part[j];
-        for (int q = 1; q < groups; ++q) s += part[(size_t)q * M + j];
-        out[j] = s;
-    }
-    __syncthreads();
-}
 
 // The vectors of one appended point, a workgroup per output.  Dynamic LDS (plan_sparse_append): x / l and 1 / l (2 x 24) | kz, later
 // q = Yb^T p (M) | u (M) | p (M) | t (M + 1) | partial sums of the transposed products (groups x M).

@@ -160,6 +160,23 @@ class HipEngine:
         self._check(self.lib.gpmpc_sparse_append(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
         self._keep_append = (X, Y)                     # inputs of launches that may still be in flight
 
+    def sparse_forget(self, X_old, Y_old):
+        """Remove the memory points whose VALUES are (X_old (k, E), Y_old (k, D)) from the sparse model of the last
+        `prepare_sparse` / `sparse_append` (gpmpc_sparse_forget): same inducing inputs, hyper-parameters and jitter, O(k M^2) per
+        output, nothing of size N touched.  Afterwards the engine is in the state `prepare_sparse` would leave for the memory
+        without these rows, up to rounding; forgets and appends chain in any order.  `last_prepare_mode` is 6.  Synchronises the
+        current stream, so the inputs need not be kept alive.  The engine cannot know whether a row is in the model: one that
+        never was either loses the pivot or silently leaves the model of "the memory minus a phantom point".
+        An engine without the record of a `prepare_sparse`, k = 0 or other shapes than the model's: GpmpcError(GPMPC_ERR_ARG), the
+        cached model untouched.  A lost pivot: GpmpcError(GPMPC_ERR_NOT_PD), and the engine holds no model -- prepare again."""
+        X = self._dev(X_old)
+        Y = self._dev(Y_old)
+        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError(f"expected inputs (k, E) and targets (k, D), got {tuple(X.shape)} and {tuple(Y.shape)}")
+        k, E = X.shape
+        D = Y.shape[1]
+        self._check(self.lib.gpmpc_sparse_forget(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
+
     def select_inducing(self, X, M, lengthscales, outputscales, jitter_rel=1e-6):
         """Choose M of the memory points X (N, E) as inducing inputs for `prepare_sparse` by greedy variance selection
         (gpmpc_select_inducing: a pivoted partial Cholesky of the D kernel matrices in lockstep, each step picking the point the
@@ -223,7 +240,8 @@ class HipEngine:
     @property
     def last_prepare_mode(self):
         """0 = full factorisation, 1 = border update of the cached factors, 2 = cache hit, 3 = downdate (`forget`),
-        4 = sparse model (`prepare_sparse`), 5 = points appended to a sparse model (`sparse_append`)."""
+        4 = sparse model (`prepare_sparse`), 5 = points appended to a sparse model (`sparse_append`),
+        6 = points removed from a sparse model (`sparse_forget`)."""
         return int(self.lib.gpmpc_last_prepare_mode(self._h))
 
     @property

@@ -44,7 +44,8 @@ const char* gpmpc_last_error(const gpmpc_t* h);
  * Synchronises `stream` (a failed factorisation is reported here: GPMPC_ERR_NOT_PD).  Reuse across control steps (the reference
  * refactorises every step, gp_mpc_controller.py:117): gpmpc_last_prepare_mode = 0 full factorisation, 1 border update (the
  * cached memory plus <= 8 appended points, same hyper-parameters), 2 cache hit, 3 downdate (gpmpc_forget), 4 sparse model
- * (gpmpc_prepare_sparse), 5 points appended to a sparse model (gpmpc_sparse_append).
+ * (gpmpc_prepare_sparse), 5 points appended to a sparse model (gpmpc_sparse_append), 6 points removed from one
+ * (gpmpc_sparse_forget).
  */
 int gpmpc_prepare(gpmpc_t* h, const double* X_dev, const double* Y_dev, const double* lengthscales_dev,
                   const double* outputscales_dev, const double* noises_dev, int N, int D, int E, void* stream);
@@ -126,6 +127,50 @@ int gpmpc_prepare_sparse(gpmpc_t* h, const double* X_dev, const double* Y_dev, i
  * GPMPC_ERR_LIMIT: M beyond what a workgroup's LDS holds (about 4000).  GPMPC_ERR_HIP leaves no model, as after a failed prepare.
  */
 int gpmpc_sparse_append(gpmpc_t* h, const double* Xnew_dev, const double* Ynew_dev, int k, int D, int E, void* stream);
+
+/*
+ * gpmpc_sparse_forget: k memory points leave the sparse model cached by gpmpc_prepare_sparse (and grown by gpmpc_sparse_append),
+ * with the same Z, hyper-parameters and jitter, in O(M^2) per point and output -- the shrinking half of an incremental sparse
+ * model (the exact model's is gpmpc_forget).  Nothing of size N is touched: removing a point is the rank-one change of
+ * B = I + V V^T / n_a that gpmpc_sparse_append makes, with the opposite sign, from the same record (Yu, Yb, w, the noises).
+ *   Xold_dev (k,E)  Yold_dev (k,D)      the VALUES of the rows that leave (a sparse model keeps no (X, Y) record, so indices would
+ *                                       mean nothing);  D, E: those of the cached model
+ * Per output a (n = n_a, sigma2 = sigma2_a) and per removed point (x, y) in ascending row order, in this order of operations:
+ *   kz = k_a(Z, x)                                   (differences per element, as in gpmpc_sparse_append)
+ *   v  = Yu kz          u = v / sqrt(n)              p = Yb u
+ *   t_0 = 1,  t_{i+1} = t_i - p_i^2  (i ascending)   tau = t_M  ( = 1 - p^T p )
+ *   LOST PIVOT if some t_{i+1} is not > 0 (NaN included), or tau < 1 / (2 (1 + sigma2 / n))
+ *   g  = Yu^T (Yb^T p)                               with the OLD Yb
+ *   iK_eff[i,j] -= g_i g_j / tau                     (exactly symmetric)
+ *   d_i = sqrt(t_{i+1} / t_i),  c_i = p_i / sqrt(t_i t_{i+1})
+ *   per column j:  acc = 0;  for i = j .. M-1:  Yb'[i,j] = (Yb[i,j] + p_i acc) / d_i;   acc += c_i Yb'[i,j]
+ *   w' = w - v y
+ *   beta_eff' = Yu^T Yb'^T Yb' w' / n                (as in gpmpc_prepare_sparse; once per call, after the last point)
+ * B' = B - u u^T = LB (I - p p^T) LB^T, and chol(I - p p^T) has the diagonal d_i and the entries -p_i c_j below it, so Yb' is the
+ * inverse Cholesky factor of B'; B'^-1 = B^-1 + (B^-1 u)(B^-1 u)^T / tau.  Unlike the append this subtracts from positive
+ * quantities: a pivot can be lost, and digits are lost when most of the data behind an inducing input leaves, so
+ * count removals toward a periodic gpmpc_prepare_sparse.  The floor on tau is no tuning knob: for a point that is in the model
+ * tau = 1 / (1 + u^T B'^-1 u) >= 1 / (1 + sigma2 / n), since v^T v <= k(x, x) = sigma2; half of that separates rounding from a point
+ * that never was in the model.
+ * CALLER'S CONTRACT: the call cannot know whether a row really is in the model.  A row that never was either trips the pivot check
+ * or silently yields the model of "the memory minus a phantom point".  The call puts no bound on k: removing every point, or more
+ * than were ever there, is the caller's error (the model layer enforces k < rows).
+ * Afterwards the handle is in the state gpmpc_prepare_sparse would leave for the memory without those rows, up to rounding:
+ * iK_eff, beta_eff and the tables of the rollouts; no (X, Y) record, N stays M, every other entry point runs on the result
+ * unchanged, and the record follows, so forgets and appends chain in any order.  gpmpc_last_prepare_mode = 6.  Two plain launches
+ * per point and four per call; every sum runs in an order fixed by M, D and E alone, no atomics, no waits between workgroups: two
+ * runs give the same bits, and k points in one call give the bits of k calls of one point each.  Synchronises `stream` at the
+ * end, as gpmpc_forget does, to report a lost pivot.  The record is dropped by gpmpc_prepare, gpmpc_set_factors, gpmpc_mll, a
+ * failed gpmpc_prepare_sparse, and GPMPC_ERR_NOT_PD or GPMPC_ERR_HIP in here.
+ *   reported before anything is launched, the cached model and the record untouched:
+ *     GPMPC_ERR_ARG     no record of a gpmpc_prepare_sparse, a NULL pointer, k < 1, D or E different from the model's
+ *     GPMPC_ERR_LIMIT   M beyond what a workgroup's LDS holds (about 4000, as for gpmpc_sparse_append)
+ *   reported after the call's launches have completed:
+ *     GPMPC_ERR_NOT_PD  a lost pivot: the kernels stop at the first point that loses one (the points before it have left), and the
+ *                       call leaves no model and no record, as after a failed prepare; gpmpc_last_error names point and output
+ *     GPMPC_ERR_HIP     likewise leaves no model
+ */
+int gpmpc_sparse_forget(gpmpc_t* h, const double* Xold_dev, const double* Yold_dev, int k, int D, int E, void* stream);
 
 /*
  * gpmpc_select_inducing: chooses the M inducing inputs of gpmpc_prepare_sparse among the N memory points on the device (the

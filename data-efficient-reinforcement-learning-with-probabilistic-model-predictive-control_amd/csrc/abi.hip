@@ -83,7 +83,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spfg};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -805,28 +805,28 @@ int gpmpc_argmin_export(gpmpc_t* g, const double* J, int B, long long first, con
     return launch_argmin_to(h, J, B, first, actions, HA, out_dev, static_cast<double*>(dev_view), (hipStream_t)stream);
 }
 
-int gpmpc_sparse_append(gpmpc_t* g, const double* Xnew, const double* Ynew, int k, int D, int E, void* stream) {
-    Range roctx_range("gpmpc_sparse_append");
+// the checks gpmpc_sparse_append and gpmpc_sparse_forget share (`name` heads the messages), then the update itself
+static int sparse_update_entry(gpmpc_t* g, const char* name, const double* X, const double* Y, int k, int D, int E, bool forget,
+                               void* stream) {
     if (!g) return GPMPC_ERR_ARG;
     Handle* h = H_(g);
-    if (!h->ready || !h->sp_have) return bad(g, "sparse_append: the handle holds no record of a gpmpc_prepare_sparse");
-    if (!Xnew || !Ynew) return bad(g, "null argument");
-    if (k < 1) return bad(g, "sparse_append: need k >= 1 points");
-    if (D != h->D || E != h->E) return bad(g, "sparse_append: D and E must be those of the cached sparse model");
+    const std::string pre = std::string(name) + ": ";
+    if (!h->ready || !h->sp_have) return bad(g, (pre + "the handle holds no record of a gpmpc_prepare_sparse").c_str());
+    if (!X || !Y) return bad(g, "null argument");
+    if (k < 1) return bad(g, (pre + "need k >= 1 points").c_str());
+    if (D != h->D || E != h->E) return bad(g, (pre + "D and E must be those of the cached sparse model").c_str());
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_sparse_append(h, Xnew, Ynew, k, (hipStream_t)stream);
+    return run_sparse_update(h, X, Y, k, forget, (hipStream_t)stream);
+}
+
+int gpmpc_sparse_append(gpmpc_t* g, const double* Xnew, const double* Ynew, int k, int D, int E, void* stream) {
+    Range roctx_range("gpmpc_sparse_append");
+    return sparse_update_entry(g, "sparse_append", Xnew, Ynew, k, D, E, false, stream);
 }
 
 int gpmpc_sparse_forget(gpmpc_t* g, const double* Xold, const double* Yold, int k, int D, int E, void* stream) {
     Range roctx_range("gpmpc_sparse_forget");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready || !h->sp_have) return bad(g, "sparse_forget: the handle holds no record of a gpmpc_prepare_sparse");
-    if (!Xold || !Yold) return bad(g, "null argument");
-    if (k < 1) return bad(g, "sparse_forget: need k >= 1 points");
-    if (D != h->D || E != h->E) return bad(g, "sparse_forget: D and E must be those of the cached sparse model");
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_sparse_forget(h, Xold, Yold, k, (hipStream_t)stream);
+    return sparse_update_entry(g, "sparse_forget", Xold, Yold, k, D, E, true, stream);
 }
 
 }  // extern "C"

@@ -313,10 +313,10 @@ struct Handle {
     int opt_lqr_gains_chunk = 0;     // gpmpc_lqr_gains: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int lds_limit = 160 * 1024;
     int num_cu = 256;
-    Buf sprec;    // gpmpc_sparse_append: the record of the last gpmpc_prepare_sparse (Yb | w | noises) | vectors of the point at hand (sparse_append_plan.h)
+    Buf sprec;    // gpmpc_sparse_append / gpmpc_sparse_forget: the record of the last gpmpc_prepare_sparse (Yb | w | noises; sparse_update_plan.h)
     bool sp_have = false;        // ... is there: Yu at spws + sp_yu, Yb / w / noises in sprec, Z and the hyper-parameters packed in the handle
     size_t sp_yu = 0;
-    Buf spfg;     // gpmpc_sparse_forget: failure words | vectors of the point at hand (sparse_forget_plan.h)
+    Buf spupd;    // ... and their scratch, allocated with the record: the forget's failure words | vectors of the point at hand
 };
 
 // Raise a kernel's dynamic-LDS limit to the device maximum once per handle (= per device).
@@ -510,22 +510,15 @@ int launch_sparse_bmat(Handle* h, const double* G, const double* wpart, const do
 int launch_sparse_beta(Handle* h, const double* Yu, const double* Yb, const double* w, const double* noise, int M, int D, double* t1,
                        double* t2, double* beta, hipStream_t s);
 int launch_sparse_atb_sym(Handle* h, const double* A, const double* B, int M, int D, double* C, bool ident_minus, hipStream_t s);
-// ... gpmpc_sparse_append: k more memory points (Xn (k, E), Yn (k, D)) join the sparse model of the record (validated by the entry
-// point: a record, k >= 1); asynchronous on s
-int run_sparse_append(Handle* h, const double* Xn, const double* Yn, int k, hipStream_t s);
-// sparse_append.hip: the LDS check before a call's first launch, and the two launches of one point
-struct SparseAppendPlan;
-int check_sparse_append(Handle* h, const SparseAppendPlan& ap);
-int launch_sparse_append_point(Handle* h, const SparseAppendPlan& ap, const double* Yu, double* rec, const double* x, const double* y,
-                               int M, int D, int E, hipStream_t s);
-// ... gpmpc_sparse_forget: the memory points of the VALUES (Xo (k, E), Yo (k, D)) leave the sparse model of the record (validated by
-// the entry point: a record, k >= 1); synchronises s and reports a lost pivot (GPMPC_ERR_NOT_PD: no model, no record)
-int run_sparse_forget(Handle* h, const double* Xo, const double* Yo, int k, hipStream_t s);
-// sparse_forget.hip: the LDS check before a call's first launch, and the two launches of point number `point` of the call
-struct SparseForgetPlan;
-int check_sparse_forget(Handle* h, const SparseForgetPlan& fp);
-int launch_sparse_forget_point(Handle* h, const SparseAppendPlan& ap, const SparseForgetPlan& fp, const double* Yu, double* rec,
-                               double* ws, const double* x, const double* y, int point, int M, int D, int E, hipStream_t s);
+// ... gpmpc_sparse_append / gpmpc_sparse_forget: k memory points (X (k, E), Y (k, D)) join the sparse model of the record, or --
+// `forget`, by their VALUES -- leave it (validated by the entry point: a record, k >= 1).  The append is asynchronous on s; the forget
+// synchronises s and reports a lost pivot (GPMPC_ERR_NOT_PD: no model, no record)
+int run_sparse_update(Handle* h, const double* X, const double* Y, int k, bool forget, hipStream_t s);
+// sparse_update.hip: the LDS check before a call's first launch, and the two launches of point number `point` of the call
+struct SparseUpdatePlan;
+int check_sparse_update(Handle* h, const SparseUpdatePlan& p, bool forget);
+int launch_sparse_update_point(Handle* h, const SparseUpdatePlan& p, const double* Yu, double* rec, double* ws, const double* x,
+                               const double* y, int point, bool forget, int M, int D, int E, hipStream_t s);
 // select_inducing.hip: greedy variance selection of M of the N points X as inducing inputs (validated by the entry point; Z_out and
 // trace_out may be NULL); asynchronous on s, the cached model is neither read nor written
 int run_select_inducing(Handle* h, const double* X, int N, int M, const double* ls, const double* os, double jitter_rel, int D, int E,

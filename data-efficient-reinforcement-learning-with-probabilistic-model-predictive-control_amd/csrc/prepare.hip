@@ -15,8 +15,7 @@
 #include "device_common.h"
 #include "prepare_tiled.h"
 #include "prepare_sparse_plan.h"
-#include "sparse_append_plan.h"
-#include "sparse_forget_plan.h"
+#include "sparse_update_plan.h"
 
 namespace gpmpc_hip {
 
@@ -1058,6 +1057,11 @@ __global__ __launch_bounds__(256) void tm_kernel(const double* __restrict__ iK, 
     T[((size_t)a * (N + kTPad) + i) * N + j] = t;        // upper triangle only
 }
 
+// ... launched for the n-point model in h->iK / h->beta, into h->Tm
+static void launch_tm(Handle* h, int n, int D, const int* skip, hipStream_t s) {
+    hipLaunchKernelGGL(tm_kernel, dim3((n + 63) / 64, (n + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, n, h->Tm.p, skip);
+}
+
 // ------------------------------------------------------------------------------------------
 int grow(Handle* h, Buf& b, size_t need) {
     if (b.p && need <= b.cap) return GPMPC_OK;
@@ -1135,7 +1139,7 @@ int run_set_factors(Handle* h, const double* X, const double* iK, const double* 
     if ((rc = pack(h, X, ls, os, N, D, E, s))) return rc;
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->iK.p, iK, (size_t)D * N * N * sizeof(double), hipMemcpyDeviceToDevice, s));
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->beta.p, beta, (size_t)D * N * sizeof(double), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p, nullptr);
+    launch_tm(h, N, D, nullptr, s);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     h->N = N; h->D = D; h->E = E; h->ready = true;
     h->have_state = false;                      // no (X, Y, hyper-parameters) record for these factors
@@ -1312,8 +1316,7 @@ static int try_incremental(Handle* h, const double* X, const double* Y, const do
         t = h->linv; h->linv = h->Tm; h->Tm = t;
         t = h->beta; h->beta = h->zvec; h->zvec = t;
     }
-    hipLaunchKernelGGL(tm_kernel, dim3((N + 63) / 64, (N + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, N, h->Tm.p,
-                       h->mismatch);
+    launch_tm(h, N, D, h->mismatch, s);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     int verdict[kMaxD + 1];
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(verdict, h->info, (kMaxD + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1644,9 +1647,10 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     plan_prepare_sparse(N, M, D, h->opt_sparse_chunk, sp);
     h->sp_have = false;
     if ((rc = grow(h, h->spws, sp.total))) return rc;
-    SparseAppendPlan ap;
-    plan_sparse_append(M, D, ap);
-    if ((rc = grow(h, h->sprec, ap.total))) return rc;
+    SparseUpdatePlan ap;                                           // the record and the scratch of gpmpc_sparse_append / _forget
+    plan_sparse_update(M, D, ap);
+    if ((rc = grow(h, h->sprec, ap.rec_total))) return rc;
+    if ((rc = grow(h, h->spupd, ap.ws_total))) return rc;
     h->ready = false;
     h->have_state = false;
     h->last_prepare_mode = 4;
@@ -1688,7 +1692,7 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     }
     if ((rc = launch_sparse_bmat(h, G, ws + sp.wpart, noise, M, D, h->gram.p, ws + sp.w, s))) return rc;
     if ((rc = factor())) return rc;
-    // the record gpmpc_sparse_append continues from: Yb, w and the noises in buffers of their own (Yu stays at ws + sp.yu, which
+    // the record gpmpc_sparse_append / gpmpc_sparse_forget continue from: Yb, w and the noises in buffers of their own (Yu stays at ws + sp.yu, which
     // nothing but this function writes)
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->sprec.p + ap.yb, h->linv.p, MM * sizeof(double), hipMemcpyDeviceToDevice, s));
     GPMPC_HIP_CHECK(h, hipMemcpyAsync(h->sprec.p + ap.w, ws + sp.w, (size_t)D * M * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1699,7 +1703,7 @@ int run_prepare_sparse(Handle* h, const double* X, const double* Y, int N, const
     hipLaunchKernelGGL(gemm_nn_tiled_kernel, dim3((M + TS - 1) / TS, (M + TS - 1) / TS, D), dim3(256), 0, s, h->gram.p, M, NNm,
                        ws + sp.yu, M, NNm, ws + sp.r, M, NNm, M, M, M, 1.0, 1, 0);
     if ((rc = launch_sparse_atb_sym(h, ws + sp.yu, ws + sp.r, M, D, h->iK.p, false, s))) return rc;
-    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
+    launch_tm(h, M, D, nullptr, s);
     GPMPC_HIP_CHECK(h, hipGetLastError());
     GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
     h->N = M; h->D = D; h->E = E; h->ready = true;
@@ -1755,8 +1759,7 @@ int run_forget(Handle* h, const int* idx, int k, hipStream_t s) {
         t = h->linv; h->linv = h->Tm; h->Tm = t;
         t = h->beta; h->beta = h->zvec; h->zvec = t;
     }
-    hipLaunchKernelGGL(tm_kernel, dim3((n1 + 63) / 64, (n1 + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, n1, h->Tm.p,
-                       nullptr);
+    launch_tm(h, n1, D, nullptr, s);
     if ((rc = launch_forget_pack(h, rm, n1, D, E, h->Xf.p, h->Yf.p, true, s))) return rc;
     Buf t = h->Xc; h->Xc = h->Xf; h->Xf = t;
     t = h->Yc; h->Yc = h->Yf; h->Yf = t;
@@ -1793,70 +1796,46 @@ int run_mll(Handle* h, const double* X, const double* Y, const double* ls, const
     return GPMPC_OK;
 }
 
-// gpmpc_sparse_append (kernels and formulas: sparse_append.hip): per point the two launches of launch_sparse_append_point, then
-// once per call beta_eff by the three triangular products of the tail above and the T table.  No host synchronisation.  From the
-// first launch on a HIP error leaves no model and no record.
-int run_sparse_append(Handle* h, const double* Xn, const double* Yn, int k, hipStream_t s) {
+// gpmpc_sparse_append and gpmpc_sparse_forget (kernels and formulas: sparse_update.hip): per point the two launches of
+// launch_sparse_update_point, then once per call beta_eff by the three triangular products of the tail above and the T table.
+// Nothing is allocated: record and scratch are those run_prepare_sparse left.  From the first launch on a HIP error leaves no model
+// and no record.  The append does not synchronise.  The forget clears the failure words first, synchronises the stream at the end
+// and reads them: an output that lost its pivot stopped every later launch of the forget's kernels (the tail then ran on the model
+// of the points removed before, and is discarded), and the call leaves no model and no record either.
+int run_sparse_update(Handle* h, const double* X, const double* Y, int k, bool forget, hipStream_t s) {
     const int M = h->N, D = h->D, E = h->E;
-    SparseAppendPlan ap;
-    plan_sparse_append(M, D, ap);
+    SparseUpdatePlan p;
+    plan_sparse_update(M, D, p);
     int rc;
-    if ((rc = check_sparse_append(h, ap))) return rc;
+    if ((rc = check_sparse_update(h, p, forget))) return rc;
     h->ready = false;
     h->sp_have = false;
     const double* Yu = h->spws.p + h->sp_yu;
     double* rec = h->sprec.p;
+    double* ws = h->spupd.p;
+    if (forget) GPMPC_HIP_CHECK(h, hipMemsetAsync(ws + p.fail, 0, kUpdFailWords * sizeof(int), s));
     for (int q = 0; q < k; ++q)
-        if ((rc = launch_sparse_append_point(h, ap, Yu, rec, Xn + (size_t)q * E, Yn + (size_t)q * D, M, D, E, s))) return rc;
-    if ((rc = launch_sparse_beta(h, Yu, rec + ap.yb, rec + ap.w, rec + ap.noise, M, D, rec + ap.t1, rec + ap.t2, h->beta.p, s))) return rc;
-    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
+        if ((rc = launch_sparse_update_point(h, p, Yu, rec, ws, X + (size_t)q * E, Y + (size_t)q * D, q, forget, M, D, E, s))) return rc;
+    if ((rc = launch_sparse_beta(h, Yu, rec + p.yb, rec + p.w, rec + p.noise, M, D, ws + p.t1, ws + p.t2, h->beta.p, s))) return rc;
+    launch_tm(h, M, D, nullptr, s);
     GPMPC_HIP_CHECK(h, hipGetLastError());
-    h->ready = true;
-    h->sp_have = true;
-    h->last_prepare_mode = 5;
-    return GPMPC_OK;
-}
-
-// gpmpc_sparse_forget (kernels and formulas: sparse_forget.hip): the append with the opposite sign -- per point the two launches
-// of launch_sparse_forget_point, then once per call beta_eff and the T table by the launches of the append's tail.  The failure
-// words are cleared first, the stream is synchronised at the end and they are read: an output that lost its pivot stopped every
-// later launch of the forget's kernels (the tail then ran on the model of the points removed before, and is discarded), and the
-// call leaves no model and no record, as a HIP error from the first launch on does.
-int run_sparse_forget(Handle* h, const double* Xo, const double* Yo, int k, hipStream_t s) {
-    const int M = h->N, D = h->D, E = h->E;
-    SparseAppendPlan ap;
-    plan_sparse_append(M, D, ap);
-    SparseForgetPlan fp;
-    plan_sparse_forget(M, D, fp);
-    int rc;
-    if ((rc = check_sparse_forget(h, fp))) return rc;
-    if ((rc = grow(h, h->spfg, fp.total))) return rc;
-    h->ready = false;
-    h->sp_have = false;
-    const double* Yu = h->spws.p + h->sp_yu;
-    double* rec = h->sprec.p;
-    double* ws = h->spfg.p;
-    GPMPC_HIP_CHECK(h, hipMemsetAsync(ws + fp.fail, 0, kForgetFailWords * sizeof(int), s));
-    for (int q = 0; q < k; ++q)
-        if ((rc = launch_sparse_forget_point(h, ap, fp, Yu, rec, ws, Xo + (size_t)q * E, Yo + (size_t)q * D, q, M, D, E, s))) return rc;
-    if ((rc = launch_sparse_beta(h, Yu, rec + ap.yb, rec + ap.w, rec + ap.noise, M, D, ws + fp.t1, ws + fp.t2, h->beta.p, s))) return rc;
-    hipLaunchKernelGGL(tm_kernel, dim3((M + 63) / 64, (M + kTPad + 3) / 4, D), dim3(256), 0, s, h->iK.p, h->beta.p, M, h->Tm.p, nullptr);
-    GPMPC_HIP_CHECK(h, hipGetLastError());
-    int fail[kForgetFailWords];
-    GPMPC_HIP_CHECK(h, hipMemcpyAsync(fail, ws + fp.fail, sizeof fail, hipMemcpyDeviceToHost, s));
-    GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
-    for (int a = 0; a < D; ++a) {
-        if (fail[a] != 0) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "sparse_forget: point %d of the call, output %d: the pivot is lost (the point is not in the model, "
-                     "or too little of the model would remain)", fail[a] - 1, a);
-            h->err = buf;
-            return GPMPC_ERR_NOT_PD;
+    if (forget) {
+        int fail[kUpdFailWords];
+        GPMPC_HIP_CHECK(h, hipMemcpyAsync(fail, ws + p.fail, sizeof fail, hipMemcpyDeviceToHost, s));
+        GPMPC_HIP_CHECK(h, hipStreamSynchronize(s));
+        for (int a = 0; a < D; ++a) {
+            if (fail[a] != 0) {
+                char buf[200];
+                snprintf(buf, sizeof buf, "sparse_forget: point %d of the call, output %d: the pivot is lost (the point is not in the model, "
+                         "or too little of the model would remain)", fail[a] - 1, a);
+                h->err = buf;
+                return GPMPC_ERR_NOT_PD;
+            }
         }
     }
     h->ready = true;
     h->sp_have = true;
-    h->last_prepare_mode = 6;
+    h->last_prepare_mode = forget ? 6 : 5;
     return GPMPC_OK;
 }
 

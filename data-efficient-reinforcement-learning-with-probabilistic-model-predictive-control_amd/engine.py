@@ -144,6 +144,17 @@ class HipEngine:
                                                   osc.data_ptr(), nz.data_ptr(), float(jitter_rel), D, E, self._stream()))
         self.N, self.D, self.E = M, D, E
 
+    def _sparse_update(self, entry, X, Y):
+        """The argument checks and the call `sparse_append` and `sparse_forget` share; returns the device tensors passed."""
+        X = self._dev(X)
+        Y = self._dev(Y)
+        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError(f"expected inputs (k, E) and targets (k, D), got {tuple(X.shape)} and {tuple(Y.shape)}")
+        k, E = X.shape
+        D = Y.shape[1]
+        self._check(entry(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
+        return X, Y
+
     def sparse_append(self, X_new, Y_new):
         """Append the memory points (X_new (k, E), Y_new (k, D)) to the sparse model of the last `prepare_sparse`
         (gpmpc_sparse_append): same inducing inputs, hyper-parameters and jitter, O(k M^2) per output, nothing of size N touched.
@@ -151,14 +162,7 @@ class HipEngine:
         rounding; calls chain.  `last_prepare_mode` is 5.  Nothing synchronises: the update is ordered on the current stream.
         An engine without the record of a `prepare_sparse` (after `prepare`, `set_factors`, `mll`), k = 0 or other shapes than the
         model's: GpmpcError(GPMPC_ERR_ARG), the cached model untouched."""
-        X = self._dev(X_new)
-        Y = self._dev(Y_new)
-        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
-            raise ValueError(f"expected inputs (k, E) and targets (k, D), got {tuple(X.shape)} and {tuple(Y.shape)}")
-        k, E = X.shape
-        D = Y.shape[1]
-        self._check(self.lib.gpmpc_sparse_append(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
-        self._keep_append = (X, Y)                     # inputs of launches that may still be in flight
+        self._keep_append = self._sparse_update(self.lib.gpmpc_sparse_append, X_new, Y_new)    # inputs of launches that may still be in flight
 
     def sparse_forget(self, X_old, Y_old):
         """Remove the memory points whose VALUES are (X_old (k, E), Y_old (k, D)) from the sparse model of the last
@@ -169,13 +173,7 @@ class HipEngine:
         never was either loses the pivot or silently leaves the model of "the memory minus a phantom point".
         An engine without the record of a `prepare_sparse`, k = 0 or other shapes than the model's: GpmpcError(GPMPC_ERR_ARG), the
         cached model untouched.  A lost pivot: GpmpcError(GPMPC_ERR_NOT_PD), and the engine holds no model -- prepare again."""
-        X = self._dev(X_old)
-        Y = self._dev(Y_old)
-        if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
-            raise ValueError(f"expected inputs (k, E) and targets (k, D), got {tuple(X.shape)} and {tuple(Y.shape)}")
-        k, E = X.shape
-        D = Y.shape[1]
-        self._check(self.lib.gpmpc_sparse_forget(self._h, X.data_ptr(), Y.data_ptr(), int(k), int(D), int(E), self._stream()))
+        self._sparse_update(self.lib.gpmpc_sparse_forget, X_old, Y_old)
 
     def select_inducing(self, X, M, lengthscales, outputscales, jitter_rel=1e-6):
         """Choose M of the memory points X (N, E) as inducing inputs for `prepare_sparse` by greedy variance selection

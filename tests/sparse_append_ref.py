@@ -8,6 +8,7 @@ that lets one more memory point (x, y) join it,
     per column j:  acc = 0;  for i = j .. M-1:  Yb'[i,j] = (Yb[i,j] - p_i acc) / d_i;  acc += c_i Yb'[i,j]
     w' = w + v y,   beta_eff' = Yu^T Yb'^T Yb' w' / n
 
+(`update`; with `forget` the same recurrence with the opposite sign and the pivot check, as tests/sparse_forget_ref.py states it),
 plus the cases the CPU and GPU tests share: the memory splits of sparse_gp_ref's cases and a few small ones of other shapes, each
 with its tolerance computed as sparse_gp_ref.case computes it (10 x the from-scratch float64 error + 64 eps scale, for the FULL
 memory; never taken from the code under test).
@@ -52,36 +53,58 @@ def build_record(X, Y, Z, ls, os_, nz, jitter_rel, dtype=np.float64):
     return r
 
 
-def append(r, X_new, Y_new):
-    """The rows of (X_new (k, E), Y_new (k, D)) join the record in place, in ascending row order."""
+class LostPivot(ArithmeticError):
+    """The check of the forget's t chain failed: `point` (row of the call) and `output`."""
+
+    def __init__(self, point, output, p2):
+        super().__init__(f"sparse forget: point {point}, output {output}: the pivot is lost (p^T p = {float(p2):.3g})")
+        self.point, self.output, self.p2 = point, output, float(p2)
+
+
+def update(r, X_pts, Y_pts, forget=False):
+    """The rows of (X_pts (k, E), Y_pts (k, D)) join the record in place -- or, with `forget`, leave it: the same recurrence with
+    the opposite sign (tests/sparse_forget_ref.py), which raises LostPivot and records min tau in r.min_tau -- in ascending row
+    order."""
     dtype = r.dtype
-    X_new, Y_new = np.asarray(X_new, dtype=dtype), np.asarray(Y_new, dtype=dtype)
+    X_pts, Y_pts = np.asarray(X_pts, dtype=dtype), np.asarray(Y_pts, dtype=dtype)
     D, M = r.w.shape
     one = dtype(1)
-    for q in range(X_new.shape[0]):
+    s = -one if forget else one                              # a + s b is a + b or a - b bit for bit: the product with +-1 is exact
+    for q in range(X_pts.shape[0]):
         for a in range(D):
             Yu, Yb = r.Yu[a], r.Yb[a]
             n = dtype(r.nz[a])
-            kz = ref.cross_gram(r.Z, X_new[q:q + 1], r.ls[a], r.os[a], dtype)[:, 0]
+            kz = ref.cross_gram(r.Z, X_pts[q:q + 1], r.ls[a], r.os[a], dtype)[:, 0]
             v = Yu @ kz
             u = v / np.sqrt(n)
             p = Yb @ u
             t = np.empty(M + 1, dtype=dtype)
             t[0] = one
+            lost = False
             for i in range(M):
-                t[i + 1] = t[i] + p[i] * p[i]
+                t[i + 1] = t[i] + s * (p[i] * p[i])
+                lost = lost or not (t[i + 1] > 0)
+            if forget:
+                if lost or t[M] < one / (2 * (one + dtype(r.os[a]) / n)):
+                    raise LostPivot(q, a, p @ p)
+                r.min_tau = min(getattr(r, "min_tau", 1.0), float(t[M]))
             g = Yu.T @ (Yb.T @ p)
-            r.iK[a] = r.iK[a] + ref._mirror_upper(np.outer(g, g) / t[M])
+            r.iK[a] = r.iK[a] + s * ref._mirror_upper(np.outer(g, g) / t[M])
             d = np.sqrt(t[1:] / t[:-1])
             c = p / np.sqrt(t[:-1] * t[1:])
             acc = np.zeros(M, dtype=dtype)
             Yn = np.zeros((M, M), dtype=dtype)
             for i in range(M):                               # row i of every column j <= i at once: the columns are independent
-                Yn[i, :i + 1] = (Yb[i, :i + 1] - p[i] * acc[:i + 1]) / d[i]
+                Yn[i, :i + 1] = (Yb[i, :i + 1] - s * (p[i] * acc[:i + 1])) / d[i]
                 acc[:i + 1] += c[i] * Yn[i, :i + 1]
             r.Yb[a] = Yn
-            r.w[a] = r.w[a] + v * Y_new[q, a]
+            r.w[a] = r.w[a] + s * (v * Y_pts[q, a])
     return r
+
+
+def append(r, X_new, Y_new):
+    """The rows of (X_new (k, E), Y_new (k, D)) join the record in place, in ascending row order."""
+    return update(r, X_new, Y_new)
 
 
 # -- cases --------------------------------------------------------------------------------------------------------------------------

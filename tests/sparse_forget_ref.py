@@ -8,7 +8,7 @@ lets a memory point (x, y) leave the record gpmpc_prepare_sparse keeps (tests/sp
     per column j:  acc = 0;  for i = j .. M-1:  Yb'[i,j] = (Yb[i,j] + p_i acc) / d_i;  acc += c_i Yb'[i,j]
     w' = w - v y,   beta_eff' = Yu^T Yb'^T Yb' w' / n
 
-plus the cases the CPU and GPU tests share: a memory, the rows that leave it, and per case, from numpy alone,
+(one function with the append: sparse_append_ref.update), plus the cases the CPU and GPU tests share: a memory, the rows that leave it, and per case, from numpy alone,
 
     e_scratch = the float64 from-scratch build of the REDUCED memory against its longdouble build
     e_rec     = the float64 recurrence against the same longdouble build
@@ -28,49 +28,13 @@ LD = ref.LD
 EPS = ref.EPS
 
 
-class LostPivot(ArithmeticError):
-    """The check of the t chain failed: `point` (row of the call) and `output`."""
-
-    def __init__(self, point, output, p2):
-        super().__init__(f"sparse forget: point {point}, output {output}: the pivot is lost (p^T p = {float(p2):.3g})")
-        self.point, self.output, self.p2 = point, output, float(p2)
+LostPivot = ar.LostPivot
 
 
 def forget(r, X_old, Y_old):
-    """The rows of (X_old (k, E), Y_old (k, D)) leave the record in place, in ascending row order.  Records min tau in r.min_tau."""
-    dtype = r.dtype
-    X_old, Y_old = np.asarray(X_old, dtype=dtype), np.asarray(Y_old, dtype=dtype)
-    D, M = r.w.shape
-    one = dtype(1)
-    for q in range(X_old.shape[0]):
-        for a in range(D):
-            Yu, Yb = r.Yu[a], r.Yb[a]
-            n = dtype(r.nz[a])
-            kz = ref.cross_gram(r.Z, X_old[q:q + 1], r.ls[a], r.os[a], dtype)[:, 0]
-            v = Yu @ kz
-            u = v / np.sqrt(n)
-            p = Yb @ u
-            t = np.empty(M + 1, dtype=dtype)
-            t[0] = one
-            lost = False
-            for i in range(M):
-                t[i + 1] = t[i] - p[i] * p[i]
-                lost = lost or not (t[i + 1] > 0)
-            if lost or t[M] < one / (2 * (one + dtype(r.os[a]) / n)):
-                raise LostPivot(q, a, p @ p)
-            r.min_tau = min(getattr(r, "min_tau", 1.0), float(t[M]))
-            g = Yu.T @ (Yb.T @ p)
-            r.iK[a] = r.iK[a] - ref._mirror_upper(np.outer(g, g) / t[M])
-            d = np.sqrt(t[1:] / t[:-1])
-            c = p / np.sqrt(t[:-1] * t[1:])
-            acc = np.zeros(M, dtype=dtype)
-            Yn = np.zeros((M, M), dtype=dtype)
-            for i in range(M):                               # row i of every column j <= i at once: the columns are independent
-                Yn[i, :i + 1] = (Yb[i, :i + 1] + p[i] * acc[:i + 1]) / d[i]
-                acc[:i + 1] += c[i] * Yn[i, :i + 1]
-            r.Yb[a] = Yn
-            r.w[a] = r.w[a] - v * Y_old[q, a]
-    return r
+    """The rows of (X_old (k, E), Y_old (k, D)) leave the record in place, in ascending row order: sparse_append_ref.update with
+    the opposite sign.  Records min tau in r.min_tau."""
+    return ar.update(r, X_old, Y_old, forget=True)
 
 
 # -- cases --------------------------------------------------------------------------------------------------------------------------

@@ -402,6 +402,7 @@ int gpmpc_last_prepare_mode(gpmpc_t* g) { return g ? g->h.last_prepare_mode : GP
 
 int gpmpc_last_rollout_path(gpmpc_t* g) { return g ? g->h.last_rollout_path : GPMPC_ERR_ARG; }
 int gpmpc_last_cluster(gpmpc_t* g) { return g ? g->h.last_cluster : GPMPC_ERR_ARG; }
+int gpmpc_last_pair_groups(gpmpc_t* g) { return g ? g->h.last_pair_groups : GPMPC_ERR_ARG; }
 
 int gpmpc_last_grad_path(gpmpc_t* g) { return g ? g->h.last_grad_path : GPMPC_ERR_ARG; }
 

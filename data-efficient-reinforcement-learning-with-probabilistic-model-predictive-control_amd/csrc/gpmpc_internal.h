@@ -251,6 +251,7 @@ struct Handle {
     int opt_cluster = 0;         // workgroups per candidate of the few-candidate path: 0 auto, 1 never, n >= 2 fixed
     int opt_cl_dbg = 0;
     int last_cluster = 1;        // what the last fused-horizon launch used
+    int last_pair_groups = 1;    // groups of output pairs per horizon step of the last fused-horizon / batch-major launch
     Buf mono_w;   // (CM) 1 / alpha!
     int* mono_exp = nullptr;    // (CM, 4)
     int mono_D = -1;            // state dimension the monomial tables were built for

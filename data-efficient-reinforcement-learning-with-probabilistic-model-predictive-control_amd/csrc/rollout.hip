@@ -491,6 +491,10 @@ int launch_rollout(Handle* h, RolloutArgs& a, const RolloutPlan& p, hipStream_t 
     }
     h->last_rollout_path = p.path;
     h->last_cluster = p.cluster;
+    {
+        const int Pk = tiled ? a.D * (a.D - 1) / 2 : a.D * (a.D + 1) / 2;      // pairs whose N x N work the per-candidate kernel does
+        h->last_pair_groups = (p.path == 1 || p.G < 1 || Pk < 1) ? 1 : (Pk + p.G - 1) / p.G;
+    }
     return GPMPC_OK;
 }
 

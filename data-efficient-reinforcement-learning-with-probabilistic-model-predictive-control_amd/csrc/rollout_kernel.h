@@ -170,7 +170,11 @@ __host__ __device__ inline Layout make_layout(int N, int D, int A, int E, int G,
 //  (ii) "fused tail": the wavefront that finishes a pair's last work item forms the pair's total, the one that forms the step's
 //  last total updates the state, three barriers per step instead of five: P4 + P5 2.9 k -> 0.4 k cycles, but the queue phase
 //  + 2.3 k and P1 + 0.7 k -- the chain last item -> total -> state update is serial wherever it runs; 0.411 vs 0.409 ms, and the
-//  two-workgroups-per-CU regime (B = 4096) lost its second workgroup to the registers.  profiles/r05f_*, r05g_*.)
+//  two-workgroups-per-CU regime (B = 4096) lost its second workgroup to the registers.  profiles/r05f_*, r05g_*.
+//  That attempt MOVED the chain (into the queue phase, behind atomic counters and fences); it did not shorten it.  The horizon loop
+//  below shortens it where it is: the totals stay spread over the wavefronts behind their barrier, then the state update and the
+//  next step's small algebra run on one wavefront with no barrier between them -- four barriers per step instead of five; with
+//  the totals on that wavefront too (three barriers) the chain got longer -- see the comment at the loop and profiles/step_chain_*.)
 // Gaussian elimination with partial pivoting on an augmented [A | RHS] block (row stride ld).
 // The solution replaces the RHS; returns det(A).  Same algorithm class (LU, partial pivoting)
 // as the torch.linalg.solve / torch.det calls of the reference (gp_model.py:146,150,163,176).
@@ -763,9 +767,11 @@ __device__ __attribute__((noinline)) void sep3_item(int band, int lane, int N, i
 // Four wavefronts per SIMD (<= 128 registers) is what a 1024-thread workgroup needs anyway; the narrower workgroups of DP = 2 and of
 // the plain DP = 3 form rely on it too (two 512-thread or four 256-thread workgroups per CU) and sat just below 128 by themselves
 // until the read-ahead's second register set: the bound keeps them there (no scratch: profiles/item_loop_resource_usage_new.txt).
-// The wider ones (DP >= 4, the cooperative DP = 3 form) never fitted and keep their free allocation.
+// The wider ones (DP >= 4, the cooperative DP = 3 form) never fitted and keep their free allocation -- but for DP = 6, whose 256- and
+// 512-thread workgroups ran three wavefronts per SIMD (163-165 registers) and crossed to 171 = two with the step-chain loop: three
+// is asked for, which the allocator meets at 141-145 registers without scratch (no effect at 1024 threads, which need four anyway).
 template <int DP, bool CL>
-constexpr int rollout_min_waves() { return (DP == 2 || (DP == 3 && !CL)) ? 4 : 1; }
+constexpr int rollout_min_waves() { return (DP == 2 || (DP == 3 && !CL)) ? 4 : (DP == 6 ? 3 : 1); }
 
 template <int DP, int NT, int DX, bool C2, bool TILED = false, bool CL = false>
 __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_kernel(const RolloutArgs p) {
@@ -789,6 +795,13 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     const int member = CL ? (spread ? (int)blockIdx.x % CS : (int)(blockIdx.x >> 3) % CS) : 0;
     const int c = CL ? (spread ? (int)blockIdx.x / CS : (int)(blockIdx.x & 7) + 8 * ((int)(blockIdx.x >> 3) / CS)) : (int)blockIdx.x;
     if constexpr (CL) { if (c >= p.B) return; }
+    // the step's state update and the next step's small algebra as ONE chain on wavefront 0 (see the horizon loop): the plain and
+    // batch-major forms with the state dimension known at compile time (DP <= 4); the others keep two problem streams behind a barrier
+    constexpr bool kMerged = !CL && DX > 0 && DP <= 4;
+    // run-time D and DP > 4: the 1024-thread units sit at the register limit with scratch, and whatever a trip carries over the
+    // per-point and pairwise passes for a tail at the top of the next trip costs them more of it.  They form the tail at the end of
+    // its own trip (totals and their barrier, state update and its barrier, every wavefront) and carry nothing.
+    constexpr bool kTailInTrip = DX == 0 || DP > 4;
     const int D = (DX > 0) ? DX : p.D;
     const int N = p.N, A = p.A, E = p.E, H = p.H, G = p.G, CM = p.CM;
     const int P = TILED ? D * (D - 1) / 2 : D * (D + 1) / 2;      // output pairs whose N x N work is done here
@@ -878,11 +891,15 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     const double* act = p.actions + (size_t)c * H * A;
 
 #if defined(GPMPC_PROF_ON)
-    long long prof_x[3] = {0, 0, 0};
+    long long prof_left = 0;             // cycles from the start of P3 until this wavefront found the queue empty
     long long prof_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long prof_last = __builtin_readcyclecounter();
     long long prof_wall[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long prof_wlast = wall_clock64();
+    // the serial chain between two pairwise passes: release of the barrier that ends P3 -> this wavefront's arrival at the barrier
+    // that ends the next P1, summed over the launch (first lane of wavefronts 0 and 1)
+    long long prof_b3 = 0, prof_chain = 0;
+    int prof_chain_n = 0;
 #endif
     // ---- init -----------------------------------------------------------------------
     if constexpr (TILED) {
@@ -1107,10 +1124,44 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
         }
     }
 
+    // ---- the horizon loop ---------------------------------------------------------------------------------------------
+    // A trip = one group of output pairs (q0) of one horizon step (t), FOUR workgroup barriers per trip:
+    //     B3 (end of the previous trip's P3) -> totals, M, V (a wavefront per pair) -> B4 -> chain -> B1 -> P2 -> B2 -> P3 -> B3.
+    // The chain is the serial part of the recurrence behind the totals.  Wavefront 0 walks it alone, with no workgroup barrier
+    // inside: (last group of a step) the state update and the trajectory store, then straight on into this trip's small D x D
+    // algebra, mean and pair problems as ONE instruction stream; the other wavefronts go from B4 to B1.  The loop runs one trip
+    // more than there are groups: the first trip has no tail, the last one nothing but the tail, so the tail's code exists once.
+    // (Until this form the state update was a phase of its own behind a fifth barrier, every wavefront re-entering its strided
+    // loops to find that nine threads had work, and the mean and pair problems were two instruction streams on two wavefronts.
+    // The form with THREE barriers -- the totals on wavefront 0 too -- was built and measured: see at the totals below.)
+    // LDS the tail and the chain touch:
+    //   array                  written by                               read by                              ordered by
+    //   s_part, s_mom, s_s1,   P3 (any wavefront; cooperative form:     totals, M, V                         B3
+    //   s_sepv, s_nslot        the gather), P2 (s_nslot)
+    //   s_Sp, s_M, s_Vs        totals, M, V (one writer per element)    chain: state update                  B4
+    //   s_Sig2 (two buffers)   chain: state update (the other buffer)   chain: small algebra; nothing later  program order
+    //   s_mu, s_m              chain: state update, small algebra       chain; P2                            program order; B1
+    //   s_aug, s_cc            chain: small algebra                     P2; M, V of the next tail            B1
+    //   s_rdet, s_K            chain: small algebra                     P2, P3; totals of the next tail      B1
+    //   s_counter, s_off,      the last thread, between B4 and B1       P2, P3                               B1
+    //   s_noff
+    //   s_rdiag (TILED)        wavefronts 2, 3 before B1                totals of the trip's tail            B1
+    //   "program order" = wavefront 0 alone, its LDS accesses ordered by wave_lds_sync().
+    // Run-time D and DP > 4 (kTailInTrip) keep the loop as it was before this form: the tail at the end of its own trip, totals,
+    // M, V -> barrier -> state update on every wavefront -> barrier, five barriers per trip, nothing of a trip carried into the next.
+    // TILED: the horizon slice [p.t_begin, p.t_end) is ONE step long (launch_rollout), which the merged form relies on: with a
+    // second step in the slice, wavefronts 2 and 3 would read the covariance and write s_rdiag while the chain writes / reads them.
     int cur = 0;
     const int tid_outer = tid;
-    for (int t = TILED ? p.t_begin : 0; t < (TILED ? p.t_end : H); ++t) {
-        // Re-derive the thread coordinates inside every step from an opaque copy: otherwise the compiler
+    const int t_last = TILED ? p.t_end : H;
+    int t = TILED ? p.t_begin : 0, q0 = 0;
+    bool have_prev = false;             // a trip whose tail is still to be formed
+    int pq0 = 0;                        // ... its group
+    // trajectory rows of the state being formed, advanced once per step
+    double* traj_mu = p.mu_out + ((size_t)c * (H + 1) + (t + 1)) * D;
+    double* traj_Sig = p.Sig_out + ((size_t)c * (H + 1) + (t + 1)) * D * D;
+    for (;;) {
+        // Re-derive the thread coordinates inside every trip from an opaque copy: otherwise the compiler
         // hoists dozens of per-thread address computations out of the horizon loop and keeps them live
         // across all phases, which overflows the 128-VGPR budget of a 1024-thread workgroup (spills).
         int tid_opaque = tid_outer;
@@ -1118,160 +1169,367 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
         const int tid = tid_opaque;
         const int lane = tid & 63;
         const int wave = tid >> 6;
-        const double* s_Sig = s_Sig2 + cur * SD2;
-        double* s_SigNext = s_Sig2 + (cur ^ 1) * SD2;
+        const bool more = t < t_last;                           // a trip (t, q0) to run; otherwise only the last tail
+        const bool step_done = have_prev && pq0 + G >= P;       // the previous trip was the last group of its step
+        const double* s_SigOld = s_Sig2 + cur * SD2;
+        if (step_done) cur ^= 1;
+        const double* s_Sig = s_Sig2 + cur * SD2;               // the covariance this trip's algebra starts from
         if constexpr (CL) {
             // two exchange buffers by step parity: a member writes step t + 2 only after every member published t + 1, i.e. read t
             x_tag = p.xch_tag0 + (unsigned)t + 1u;
             x_cur = (same_xcd ? xbuf : xbuf_uc) + (size_t)(t & 1) * 2 * p.xch_n;
         }
 
-        for (int q0 = 0; q0 < P || (TILED && q0 == 0); q0 += G) {       // TILED, D = 1: no pair, the mean part still runs
-            const int Gc = (P - q0 < G) ? (P - q0) : G;
+        {
+            const int Gc = (P - q0 < G) ? (P - q0) : G;         // (TILED, D = 1: no pair, the mean part still runs)
             const bool first = (q0 == 0);
             const int nmean = first ? D : 0;
 
-            // ---- P1: small D x D algebra, one thread per problem ------------------------------
-            // (mean problems on wave 0, pair problems on wave 1: the two instruction streams are long dependent fp64
-            //  chains and would run one after the other as divergent branches of one wavefront)
-            constexpr int kPairBase = (NT >= 256) ? 64 : 0;
-#if defined(GPMPC_PROF_ON)
-            const long long prof_p1 = __builtin_readcyclecounter();
-#endif
-            if (first) {
-                // input mean of this step: [mu, a_t, (time)]  (gp_model.py:98-102)
-                for (int i = tid; i < E; i += NT) {
-                    double v;
-                    if (i < D) v = s_mu[i];
-                    else if (i < DA) v = c_act[t * A + (i - D)];
-                    else v = p.time0 + (double)t;
-                    s_m[i] = v;
+            if (!kTailInTrip && have_prev) {
+                // ---- tail of the previous trip: per-pair totals (one wave per pair, fixed order), M and V ----------------------
+                // (All six totals of a D = 3 step on wavefront 0 were measured: a lone wavefront issues an instruction every ~5
+                //  cycles, the six trees and their loads are ~700 instructions, 5.9 k cycles against 2.0 k for this phase with its
+                //  barrier -- profiles/step_chain_phases.txt.  The totals stay spread over the wavefronts; M and V go to the first
+                //  wavefront without a pair.)
+                const int pGc = (P - pq0 < G) ? (P - pq0) : G;
+                const bool pfirst = (pq0 == 0);
+                for (int gq = wave; gq < pGc; gq += NW) {
+                    const int Kraw = s_K[gq];
+                    double v = 0.0;
+                    if ((Kraw & 64) && CL) {
+                        v = s_sepv[gq];                          // summed by the owning member in this very order
+                    } else {
+                        if (Kraw & 64) {
+                            const int C = s_mcum[Kraw & 63];
+                            const double* Gm = s_mom + (gq * 2) * rnd2(CM);
+                            const double* Wm = Gm + rnd2(CM);
+                            for (int al = lane; al < C; al += 64) v = fma(Gm[al] * Wm[al], c_monow[al], v);
+                        } else {
+                            const int ns = s_nslot[gq];              // the slots the list held (the others were empty: exact zeros before)
+                            for (int k = lane; k < ns; k += 64) v += s_part[gq * wpp + k];
+                        }
+                        v = wave_sum(v);
+                    }
+                    if constexpr (TILED) {
+                        const int a = s_pa[pq0 + gq], b = s_pb[pq0 + gq];
+                        if (lane == 0) s_Sp[a * D - (a * (a - 1)) / 2 + (b - a)] = v * s_rdet[gq];
+                    } else {
+                        if (lane == 0) s_Sp[pq0 + gq] = v * s_rdet[gq];
+                    }
                 }
+                if (pfirst && wave == (pGc < NW ? pGc : NW - 1)) {
+                    if constexpr (TILED) {
+                        // i <= j only: factor 2
+                        if (lane < D) s_Sp[lane * D - (lane * (lane - 1)) / 2] = 2.0 * s_rdiag[4 + lane] * s_rdiag[lane];
+                    }
+                    if (lane < D) s_M[lane] = s_cc[lane] * s_s1[lane * (D + 1)];                 // M_a (:152)
+                    for (int idx = lane; idx < D * D; idx += 64) {
+                        const int k = idx / D, a = idx - k * D;
+                        const double* Ai = s_aug + a * (D * LD) + D;
+                        double s = 0.0;
+                        for (int j = 0; j < D; ++j) s = fma(Ai[k * LD + j], s_s1[a * (D + 1) + 1 + j], s);
+                        s_Vs[idx] = s_cc[a] * s;                                             // state rows of V (:153)
+                    }
+                }
+                __syncthreads();
+                GPMPC_TRACE(5);
             }
-            if (tid < nmean) {
-                // A_a = Sigma + diag(l_a^2) -> A_a^-1, det  (restated B of gp_model.py:141)
-                const int a = tid;
-                double* aug = s_aug + a * (D * LD);
-                double prodil = 1.0;
-                double detA;
-                if constexpr (DP <= 4) {
-                    double m[DP][2 * DP];
-#pragma unroll
-                    for (int i = 0; i < DP; ++i) {
-                        const double il2 = (i < D) ? c_ils2[a * E + i] : 1.0;
-                        prodil *= il2;
-#pragma unroll
-                        for (int j = 0; j < DP; ++j) {
-                            const bool in = (i < D && j < D);
-                            m[i][j] = (in ? s_Sig[i * D + j] : 0.0) + (i == j ? 1.0 / il2 : 0.0);
-                            m[i][DP + j] = (in && i == j) ? 1.0 : 0.0;
+            if (!kTailInTrip && wave == 0 && have_prev) {
+                if (step_done) {
+                    // ---- chain: state update  (gp_model.py:105-108, 177-178) ---------------------------------------------
+                    wave_lds_sync();
+                    double* s_SigNext = s_Sig2 + cur * SD2;
+                    for (int idx = lane; idx < D * D; idx += 64) {
+                        const int i = idx / D, j = idx - i * D;
+                        const int a = i < j ? i : j, b = i < j ? j : i;
+                        const int q = a * D - (a * (a - 1)) / 2 + (b - a);
+                        const double S = s_Sp[q] - s_M[i] * s_M[j] + (i == j ? c_var[i] : 0.0);
+                        double cij = 0.0, cji = 0.0;
+                        for (int k = 0; k < D; ++k) {
+                            cij = fma(s_SigOld[i * D + k], s_Vs[k * D + j], cij);
+                            cji = fma(s_SigOld[j * D + k], s_Vs[k * D + i], cji);
                         }
+                        const double v = S + s_SigOld[idx] + (cij + cji);   // (cij + cji) commutes: Sigma stays exactly symmetric
+                        s_SigNext[idx] = v;
+                        if (member == 0) traj_Sig[idx] = v;
                     }
-                    detA = small_solve<DP>(m);
-#pragma unroll
-                    for (int i = 0; i < DP; ++i)
-#pragma unroll
-                        for (int j = 0; j < DP; ++j)
-                            if (i < D && j < D) aug[i * LD + D + j] = m[i][DP + j];
-                } else {
-                    for (int i = 0; i < D; ++i) {
-                        const double il2 = c_ils2[a * E + i];
-                        prodil *= il2;
-                        for (int j = 0; j < D; ++j) {
-                            aug[i * LD + j] = s_Sig[i * D + j] + (i == j ? 1.0 / il2 : 0.0);
-                            aug[i * LD + D + j] = (i == j ? 1.0 : 0.0);
-                        }
+                    for (int i = lane; i < D; i += 64) {
+                        const double v = s_mu[i] + s_M[i];
+                        s_mu[i] = v;
+                        if (member == 0) traj_mu[i] = v;
                     }
-                    detA = gauss_solve(aug, D, D, LD);
                 }
-                s_cc[a] = c_var[a] / sqrt(detA * prodil);            // c_a = var_a / sqrt(det B_a)  (:150)
-            } else if (tid >= kPairBase + (kPairBase ? 0 : nmean) && tid < kPairBase + (kPairBase ? 0 : nmean) + Gc) {
-                const int gq = tid - kPairBase - (kPairBase ? 0 : nmean);
-                const int a = s_pa[q0 + gq], b = s_pb[q0 + gq];
-                double* aug = s_aug + (D + gq) * (D * LD);
-                double detR;
-                double cmax = 0.0;
-                // |g_i . w_j| <= sum_dd' |Z_dd'| umax_d wmax_d' with the data range of the memory points
-                if constexpr (DP <= 4) {
-                    double m[DP][2 * DP];
-#pragma unroll
-                    for (int i = 0; i < DP; ++i)
-#pragma unroll
-                        for (int j = 0; j < DP; ++j) {
-                            const bool in = (i < D && j < D);
-                            const double sg = in ? s_Sig[i * D + j] : 0.0;
-                            const double dab = in ? c_ils2[a * E + j] + c_ils2[b * E + j] : 0.0;
-                            m[i][j] = sg * dab + (i == j ? 1.0 : 0.0);                   // R (:156-159)
-                            m[i][DP + j] = sg;
+                wave_lds_sync();
+                GPMPC_TRACE(6);
+            }
+            // The small algebra in one of two forms (kMerged, at the top of the kernel):
+            //   merged  -- wavefront 0 goes straight on, both kinds of problem in one instruction stream;
+            //   two streams behind a barrier, as before the merge -- the cooperative form (its members' barriers span 8 wavefronts and
+            //   are cheap, and one stream of both kinds is longer than the barrier it saves: one candidate at the config-2 shape
+            //   0.2019 -> 0.2051 ms with the merged form), and run-time D and DP > 4, which form their tail at the end of its own
+            //   trip (kTailInTrip: the one-stream build keeps both kinds' operands live around the solve, and DP = 4 / 6 units lost a
+            //   wavefront of occupancy or gained scratch, profiles/step_chain_resource_usage_*.txt).
+            if constexpr (!kMerged) {
+                if (step_done) __syncthreads();
+            }
+            if constexpr (kMerged) {
+                if (wave == 0 && more) {
+                    // ---- chain, P1: small D x D algebra, one lane per problem ---------------------------------------------------
+                    // Mean problems (the first nmean lanes) and pair problems side by side in ONE instruction stream: each lane builds
+                    // its own augmented matrix, one solve serves both kinds (as divergent branches their two long dependent fp64
+                    // chains would run one after the other), then the short epilogues of each kind.
+                    if (first) {
+                        // input mean of this step: [mu, a_t, (time)]  (gp_model.py:98-102)
+                        for (int i = lane; i < E; i += 64) {
+                            double v;
+                            if (i < D) v = s_mu[i];
+                            else if (i < DA) v = c_act[t * A + (i - D)];
+                            else v = p.time0 + (double)t;
+                            s_m[i] = v;
                         }
-                    double ur[DP], wr[DP];                 // data-range bounds of |u_d|, |w_d|: independent of the solve
-#pragma unroll
-                    for (int i = 0; i < DP; ++i) {
-                        const double mi = (i < D) ? s_mu[i] : 0.0;
-                        const double rg = (i < D) ? fmax(fabs(c_xr[i] - mi), fabs(c_xr[E + i] - mi)) : 0.0;
-                        ur[i] = (i < D) ? rg * c_ils2[a * E + i] : 0.0;
-                        wr[i] = (i < D) ? rg * c_ils2[b * E + i] : 0.0;
                     }
-                    detR = small_solve<DP>(m);                                            // Z = R^-1 Sigma = 2Q (:163)
-                    double rowc[DP];                       // row sums first: three short chains instead of one of D^2 FMAs
+                    if (lane < nmean + Gc) {
+                        const bool is_mean = lane < nmean;
+                        const int gq = lane - nmean;
+                        // mean: A_a = Sigma + diag(l_a^2) -> A_a^-1, det  (restated B of gp_model.py:141)
+                        // pair: R = Sigma (Lambda_a^-1 + Lambda_b^-1) + I (:156-159) -> Z = R^-1 Sigma = 2Q (:163), det
+                        const int a = is_mean ? lane : s_pa[q0 + gq], b = is_mean ? lane : s_pb[q0 + gq];
+                        double* aug = s_aug + (is_mean ? a : D + gq) * (D * LD);
+                        double prodil = 1.0;
+                        double det;
+                        double cmax = 0.0;
+                        // |g_i . w_j| <= sum_dd' |Z_dd'| umax_d wmax_d' with the data range of the memory points
+                        {
+                            // no branch between the two kinds: every lane forms both candidates of an entry (the mean form of an
+                            // entry is one addition, the pair form one multiply-add) and keeps its own
+                            double m[DP][2 * DP];
+                            double ur[DP], wr[DP];                 // data-range bounds of |u_d|, |w_d|: independent of the solve
 #pragma unroll
-                    for (int i = 0; i < DP; ++i) {
-                        double r = 0.0;
+                            for (int i = 0; i < DP; ++i) {
+                                const double il2 = (i < D) ? c_ils2[a * E + i] : 1.0;
+                                prodil *= il2;
 #pragma unroll
-                        for (int j = 0; j < DP; ++j) {
-                            if (i < D && j < D) {
-                                aug[i * LD + D + j] = m[i][DP + j];
-                                r = fma(fabs(m[i][DP + j]), wr[j], r);
+                                for (int j = 0; j < DP; ++j) {
+                                    const bool in = (i < D && j < D);
+                                    const double sg = in ? s_Sig[i * D + j] : 0.0;
+                                    const double dab = in ? c_ils2[a * E + j] + c_ils2[b * E + j] : 0.0;
+                                    const double m_mean = (in ? s_Sig[i * D + j] : 0.0) + (i == j ? 1.0 / il2 : 0.0);
+                                    const double m_pair = sg * dab + (i == j ? 1.0 : 0.0);                   // R (:156-159)
+                                    m[i][j] = is_mean ? m_mean : m_pair;
+                                    m[i][DP + j] = is_mean ? ((in && i == j) ? 1.0 : 0.0) : sg;
+                                }
+                            }
+                            prodil = is_mean ? prodil : 1.0;
+#pragma unroll
+                            for (int i = 0; i < DP; ++i) {
+                                const double mi = (i < D) ? s_mu[i] : 0.0;
+                                const double rg = (i < D) ? fmax(fabs(c_xr[i] - mi), fabs(c_xr[E + i] - mi)) : 0.0;
+                                ur[i] = (i < D) ? rg * c_ils2[a * E + i] : 0.0;
+                                wr[i] = (i < D) ? rg * c_ils2[b * E + i] : 0.0;
+                            }
+                            det = small_solve<DP>(m);                  // mean: A_a^-1; pair: Z = R^-1 Sigma = 2Q (:163)
+                            double rowc[DP];                       // row sums first: three short chains instead of one of D^2 FMAs
+#pragma unroll
+                            for (int i = 0; i < DP; ++i) {
+                                double r = 0.0;
+#pragma unroll
+                                for (int j = 0; j < DP; ++j) {
+                                    if (i < D && j < D) {
+                                        aug[i * LD + D + j] = m[i][DP + j];
+                                        r = fma(fabs(m[i][DP + j]), wr[j], r);
+                                    }
+                                }
+                                rowc[i] = r * ur[i];
+                            }
+#pragma unroll
+                            for (int i = 0; i < DP; ++i) cmax += rowc[i];       // (a mean lane's sum is not used)
+                        }
+                        // one division and square root for both kinds (a pair lane's prodil is 1):
+                        // mean: c_a = var_a / sqrt(det B_a)  (:150); pair: 1 / sqrt(det R)  (:176)
+                        const double rs = (is_mean ? c_var[a] : 1.0) / sqrt(det * prodil);
+                        if (is_mean) {
+                            s_cc[a] = rs;
+                        } else {
+                            s_rdet[gq] = rs;
+                            // smallest K with cmax^(K+1)/(K+1)! * exp(2 cmax) <= 2^-54 (truncation below fp64 rounding)
+                            int K = 0;
+                            if (p.force_path != 1 && cmax <= kTaylorMaxArg[kMaxTaylor]) {
+                                K = 1;
+#pragma unroll
+                                for (int k = 1; k < kMaxTaylor; ++k) K += (cmax > kTaylorMaxArg[k]) ? 1 : 0;
+                            }
+                            // separable (moment) evaluation of an off-diagonal pair when it is the cheaper one
+                            if (a != b && K > 0 && K <= p.sep_kmax && (DX != 3 || K <= 6) && p.force_path == 0) {
+                                // wavefront instructions against ~(D + K + 3) per element of the pairwise loop.  D = 3 (compile-time
+                                // monomial structure): ~2 per monomial and 64 points + the 8-value reductions; otherwise per block of 8
+                                // monomials and side ~(6 + 8 (avg degree + 1)) per 64 points + one 8-value reduction
+                                const long long C_ = s_mcum[K < 3 ? 3 : K];
+                                const long long NBk = (s_mcum[K] + 7) / 8;
+                                const long long cost_sep = (DX == 3) ? 2 * (((N + 63) / 64) * (2 * C_ + 40) + (C_ / 8 + 4) * 70)
+                                                                     : 2 * NBk * (((N + 63) / 64) * (6 + 8 * K) + 80);
+                                const long long cost_el = (long long)N * N * (D + K + 3) / 64;
+                                if (p.force_sep || cost_sep < cost_el) K |= 64;
+                            }
+                            s_K[gq] = K;
+                        }
+                    }
+#if defined(GPMPC_PROF_ON)
+                    if (threadIdx.x == 0 && blockIdx.x == 0) {
+                        long long now_ = __builtin_readcyclecounter();
+                        prof_acc[7] += now_ - prof_last;
+                        if (prof_b3 != 0) { prof_chain += now_ - prof_b3; ++prof_chain_n; }
+                    }
+#endif
+                }
+            } else if (more) {
+                // ---- P1: small D x D algebra, one thread per problem ------------------------------
+                // (mean problems on wave 0, pair problems on wave 1: the two instruction streams are long dependent fp64
+                //  chains and would run one after the other as divergent branches of one wavefront)
+                constexpr int kPairBase = (NT >= 256) ? 64 : 0;
+                if (first) {
+                    // input mean of this step: [mu, a_t, (time)]  (gp_model.py:98-102)
+                    for (int i = tid; i < E; i += NT) {
+                        double v;
+                        if (i < D) v = s_mu[i];
+                        else if (i < DA) v = c_act[t * A + (i - D)];
+                        else v = p.time0 + (double)t;
+                        s_m[i] = v;
+                    }
+                }
+                if (tid < nmean) {
+                    // A_a = Sigma + diag(l_a^2) -> A_a^-1, det  (restated B of gp_model.py:141)
+                    const int a = tid;
+                    double* aug = s_aug + a * (D * LD);
+                    double prodil = 1.0;
+                    double detA;
+                    if constexpr (DP <= 4) {
+                        double m[DP][2 * DP];
+#pragma unroll
+                        for (int i = 0; i < DP; ++i) {
+                            const double il2 = (i < D) ? c_ils2[a * E + i] : 1.0;
+                            prodil *= il2;
+#pragma unroll
+                            for (int j = 0; j < DP; ++j) {
+                                const bool in = (i < D && j < D);
+                                m[i][j] = (in ? s_Sig[i * D + j] : 0.0) + (i == j ? 1.0 / il2 : 0.0);
+                                m[i][DP + j] = (in && i == j) ? 1.0 : 0.0;
                             }
                         }
-                        rowc[i] = r * ur[i];
-                    }
+                        detA = small_solve<DP>(m);
 #pragma unroll
-                    for (int i = 0; i < DP; ++i) cmax += rowc[i];
-                } else {
-                    for (int i = 0; i < D; ++i)
-                        for (int j = 0; j < D; ++j) {
-                            const double dab = c_ils2[a * E + j] + c_ils2[b * E + j];
-                            aug[i * LD + j] = s_Sig[i * D + j] * dab + (i == j ? 1.0 : 0.0);
-                            aug[i * LD + D + j] = s_Sig[i * D + j];
+                        for (int i = 0; i < DP; ++i)
+#pragma unroll
+                            for (int j = 0; j < DP; ++j)
+                                if (i < D && j < D) aug[i * LD + D + j] = m[i][DP + j];
+                    } else {
+                        for (int i = 0; i < D; ++i) {
+                            const double il2 = c_ils2[a * E + i];
+                            prodil *= il2;
+                            for (int j = 0; j < D; ++j) {
+                                aug[i * LD + j] = s_Sig[i * D + j] + (i == j ? 1.0 / il2 : 0.0);
+                                aug[i * LD + D + j] = (i == j ? 1.0 : 0.0);
+                            }
                         }
-                    detR = gauss_solve(aug, D, D, LD);
-                    const double* Z = aug + D;
-                    for (int i = 0; i < D; ++i) {
-                        const double mi = s_mu[i];
-                        const double ui = fmax(fabs(c_xr[i] - mi), fabs(c_xr[E + i] - mi)) * c_ils2[a * E + i];
-                        for (int j = 0; j < D; ++j) {
-                            const double mj = s_mu[j];
-                            const double wj = fmax(fabs(c_xr[j] - mj), fabs(c_xr[E + j] - mj)) * c_ils2[b * E + j];
-                            cmax = fma(fabs(Z[i * LD + j]) * ui, wj, cmax);
+                        detA = gauss_solve(aug, D, D, LD);
+                    }
+                    s_cc[a] = c_var[a] / sqrt(detA * prodil);            // c_a = var_a / sqrt(det B_a)  (:150)
+                } else if (tid >= kPairBase + (kPairBase ? 0 : nmean) && tid < kPairBase + (kPairBase ? 0 : nmean) + Gc) {
+                    const int gq = tid - kPairBase - (kPairBase ? 0 : nmean);
+                    const int a = s_pa[q0 + gq], b = s_pb[q0 + gq];
+                    double* aug = s_aug + (D + gq) * (D * LD);
+                    double detR;
+                    double cmax = 0.0;
+                    // |g_i . w_j| <= sum_dd' |Z_dd'| umax_d wmax_d' with the data range of the memory points
+                    if constexpr (DP <= 4) {
+                        double m[DP][2 * DP];
+#pragma unroll
+                        for (int i = 0; i < DP; ++i)
+#pragma unroll
+                            for (int j = 0; j < DP; ++j) {
+                                const bool in = (i < D && j < D);
+                                const double sg = in ? s_Sig[i * D + j] : 0.0;
+                                const double dab = in ? c_ils2[a * E + j] + c_ils2[b * E + j] : 0.0;
+                                m[i][j] = sg * dab + (i == j ? 1.0 : 0.0);                   // R (:156-159)
+                                m[i][DP + j] = sg;
+                            }
+                        double ur[DP], wr[DP];                 // data-range bounds of |u_d|, |w_d|: independent of the solve
+#pragma unroll
+                        for (int i = 0; i < DP; ++i) {
+                            const double mi = (i < D) ? s_mu[i] : 0.0;
+                            const double rg = (i < D) ? fmax(fabs(c_xr[i] - mi), fabs(c_xr[E + i] - mi)) : 0.0;
+                            ur[i] = (i < D) ? rg * c_ils2[a * E + i] : 0.0;
+                            wr[i] = (i < D) ? rg * c_ils2[b * E + i] : 0.0;
+                        }
+                        detR = small_solve<DP>(m);                                            // Z = R^-1 Sigma = 2Q (:163)
+                        double rowc[DP];                       // row sums first: three short chains instead of one of D^2 FMAs
+#pragma unroll
+                        for (int i = 0; i < DP; ++i) {
+                            double r = 0.0;
+#pragma unroll
+                            for (int j = 0; j < DP; ++j) {
+                                if (i < D && j < D) {
+                                    aug[i * LD + D + j] = m[i][DP + j];
+                                    r = fma(fabs(m[i][DP + j]), wr[j], r);
+                                }
+                            }
+                            rowc[i] = r * ur[i];
+                        }
+#pragma unroll
+                        for (int i = 0; i < DP; ++i) cmax += rowc[i];
+                    } else {
+                        for (int i = 0; i < D; ++i)
+                            for (int j = 0; j < D; ++j) {
+                                const double dab = c_ils2[a * E + j] + c_ils2[b * E + j];
+                                aug[i * LD + j] = s_Sig[i * D + j] * dab + (i == j ? 1.0 : 0.0);
+                                aug[i * LD + D + j] = s_Sig[i * D + j];
+                            }
+                        detR = gauss_solve(aug, D, D, LD);
+                        const double* Z = aug + D;
+                        for (int i = 0; i < D; ++i) {
+                            const double mi = s_mu[i];
+                            const double ui = fmax(fabs(c_xr[i] - mi), fabs(c_xr[E + i] - mi)) * c_ils2[a * E + i];
+                            for (int j = 0; j < D; ++j) {
+                                const double mj = s_mu[j];
+                                const double wj = fmax(fabs(c_xr[j] - mj), fabs(c_xr[E + j] - mj)) * c_ils2[b * E + j];
+                                cmax = fma(fabs(Z[i * LD + j]) * ui, wj, cmax);
+                            }
                         }
                     }
-                }
-                s_rdet[gq] = 1.0 / sqrt(detR);                                           // (:176)
-                // smallest K with cmax^(K+1)/(K+1)! * exp(2 cmax) <= 2^-54 (truncation below fp64 rounding)
-                int K = 0;
-                if (p.force_path != 1 && cmax <= kTaylorMaxArg[kMaxTaylor]) {
-                    K = 1;
+                    s_rdet[gq] = 1.0 / sqrt(detR);                                           // (:176)
+                    // smallest K with cmax^(K+1)/(K+1)! * exp(2 cmax) <= 2^-54 (truncation below fp64 rounding)
+                    int K = 0;
+                    if (p.force_path != 1 && cmax <= kTaylorMaxArg[kMaxTaylor]) {
+                        K = 1;
 #pragma unroll
-                    for (int k = 1; k < kMaxTaylor; ++k) K += (cmax > kTaylorMaxArg[k]) ? 1 : 0;
+                        for (int k = 1; k < kMaxTaylor; ++k) K += (cmax > kTaylorMaxArg[k]) ? 1 : 0;
+                    }
+                    // separable (moment) evaluation of an off-diagonal pair when it is the cheaper one
+                    if (a != b && K > 0 && K <= p.sep_kmax && (DX != 3 || K <= 6) && p.force_path == 0) {
+                        // wavefront instructions against ~(D + K + 3) per element of the pairwise loop.  D = 3 (compile-time
+                        // monomial structure): ~2 per monomial and 64 points + the 8-value reductions; otherwise per block of 8
+                        // monomials and side ~(6 + 8 (avg degree + 1)) per 64 points + one 8-value reduction
+                        const long long C_ = s_mcum[K < 3 ? 3 : K];
+                        const long long NBk = (s_mcum[K] + 7) / 8;
+                        const long long cost_sep = (DX == 3) ? 2 * (((N + 63) / 64) * (2 * C_ + 40) + (C_ / 8 + 4) * 70)
+                                                             : 2 * NBk * (((N + 63) / 64) * (6 + 8 * K) + 80);
+                        const long long cost_el = (long long)N * N * (D + K + 3) / 64;
+                        if (p.force_sep || cost_sep < cost_el) K |= 64;
+                    }
+                    // (cooperative form: the LDS slot of the pair's records rides in the bits above the degree and the separable flag, so the
+                    //  readers of s_K get it without another dependent LDS read)
+                    if constexpr (CL) K |= (s_slot[gq] + 1) << 8;
+                    s_K[gq] = K;
                 }
-                // separable (moment) evaluation of an off-diagonal pair when it is the cheaper one
-                if (a != b && K > 0 && K <= p.sep_kmax && (DX != 3 || K <= 6) && p.force_path == 0) {
-                    // wavefront instructions against ~(D + K + 3) per element of the pairwise loop.  D = 3 (compile-time
-                    // monomial structure): ~2 per monomial and 64 points + the 8-value reductions; otherwise per block of 8
-                    // monomials and side ~(6 + 8 (avg degree + 1)) per 64 points + one 8-value reduction
-                    const long long C_ = s_mcum[K < 3 ? 3 : K];
-                    const long long NBk = (s_mcum[K] + 7) / 8;
-                    const long long cost_sep = (DX == 3) ? 2 * (((N + 63) / 64) * (2 * C_ + 40) + (C_ / 8 + 4) * 70)
-                                                         : 2 * NBk * (((N + 63) / 64) * (6 + 8 * K) + 80);
-                    const long long cost_el = (long long)N * N * (D + K + 3) / 64;
-                    if (p.force_sep || cost_sep < cost_el) K |= 64;
+#if defined(GPMPC_PROF_ON)
+                if (threadIdx.x == 0 && blockIdx.x == 0) { long long now_ = __builtin_readcyclecounter(); prof_acc[7] += now_ - prof_last; }
+                if (blockIdx.x == 0 && (threadIdx.x == 0 || threadIdx.x == kPairBase) && prof_b3 != 0) {
+                    prof_chain += __builtin_readcyclecounter() - prof_b3;
+                    ++prof_chain_n;
                 }
-                // (cooperative form: the LDS slot of the pair's records rides in the bits above the degree and the separable flag, so the
-                //  readers of s_K get it without another dependent LDS read)
-                if constexpr (CL) K |= (s_slot[gq] + 1) << 8;
-                s_K[gq] = K;
+#endif
             }
+            if (step_done) { traj_mu += D; traj_Sig += D * D; }
+            if (!more) break;
             if constexpr (TILED) {
                 if (first && tid >= 128 && tid < 128 + D) {
                     // diagonal pair (a, a): only det R is needed here (Z and the degree: tile_params_kernel)
@@ -1299,19 +1557,12 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                     }
                 }
             }
-#if defined(GPMPC_PROF_ON)
-            if (threadIdx.x == 0 && blockIdx.x == 0) { long long now_ = __builtin_readcyclecounter(); prof_acc[7] += now_ - prof_last; }
-            if (blockIdx.x == 0 && threadIdx.x == 64) prof_x[0] += __builtin_readcyclecounter() - prof_p1;     // pair problems done
-#endif
             if (tid == NT - 1) {
                 *s_counter = 0;
                 int no = 0;
                 for (int gq = 0; gq < Gc; ++gq)
                     if (s_pa[q0 + gq] != s_pb[q0 + gq]) s_off[no++] = gq;
                 *s_noff = no;
-#if defined(GPMPC_PROF_ON)
-                if (blockIdx.x == 0) prof_x[1] += __builtin_readcyclecounter() - prof_p1;                        // last thread's bookkeeping done
-#endif
             }
             __syncthreads();
             GPMPC_TRACE(2);
@@ -1816,93 +2067,104 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                 }
             }
 #if defined(GPMPC_PROF_ON)
-            if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) prof_x[2] += __builtin_readcyclecounter() - prof_p3;     // this wavefront left the queue
+            if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) prof_left += __builtin_readcyclecounter() - prof_p3;     // this wavefront left the queue
 #endif
             __syncthreads();
             GPMPC_TRACE(4);
-
-            // ---- P4: per-pair totals (one wave per pair, fixed order), M and V -------------------
-            for (int gq = wave; gq < Gc; gq += NW) {
-                const int Kraw = s_K[gq];
-                double v = 0.0;
-                if ((Kraw & 64) && CL) {
-                    v = s_sepv[gq];                          // summed by the owning member in this very order
-                } else {
-                    if (Kraw & 64) {
-                        const int C = s_mcum[Kraw & 63];
-                        const double* Gm = s_mom + (gq * 2) * rnd2(CM);
-                        const double* Wm = Gm + rnd2(CM);
-                        for (int al = lane; al < C; al += 64) v = fma(Gm[al] * Wm[al], c_monow[al], v);
-                    } else {
-                        const int ns = s_nslot[gq];              // the slots the list held (the others were empty: exact zeros before)
-                        for (int k = lane; k < ns; k += 64) v += s_part[gq * wpp + k];
+#if defined(GPMPC_PROF_ON)
+            if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && threadIdx.x <= 64) prof_b3 = __builtin_readcyclecounter();
+#endif
+            if constexpr (CL) {
+                if (*s_fail) {
+                    // a member never arrived (bounded wait): poison the rest of the trajectory instead of spinning on
+                    // (nobody writes the flag between this barrier and the next trip's gather: the exit is workgroup-uniform)
+                    if (member == 0) {
+                        for (int i = tid; i < (H - t) * D; i += NT) p.mu_out[((size_t)c * (H + 1) + (t + 1)) * D + i] = __builtin_nan("");
+                        for (int i = tid; i < (H - t) * D * D; i += NT) p.Sig_out[((size_t)c * (H + 1) + (t + 1)) * D * D + i] = __builtin_nan("");
                     }
-                    v = wave_sum(v);
+                    return;
+                }
+            }
+            if constexpr (kTailInTrip) {
+                // ---- P4: per-pair totals (one wave per pair, fixed order), M and V -------------------
+                for (int gq = wave; gq < Gc; gq += NW) {
+                    const int Kraw = s_K[gq];
+                    double v = 0.0;
+                    if ((Kraw & 64) && CL) {
+                        v = s_sepv[gq];                          // summed by the owning member in this very order
+                    } else {
+                        if (Kraw & 64) {
+                            const int C = s_mcum[Kraw & 63];
+                            const double* Gm = s_mom + (gq * 2) * rnd2(CM);
+                            const double* Wm = Gm + rnd2(CM);
+                            for (int al = lane; al < C; al += 64) v = fma(Gm[al] * Wm[al], c_monow[al], v);
+                        } else {
+                            const int ns = s_nslot[gq];              // the slots the list held (the others were empty: exact zeros before)
+                            for (int k = lane; k < ns; k += 64) v += s_part[gq * wpp + k];
+                        }
+                        v = wave_sum(v);
+                    }
+                    if constexpr (TILED) {
+                        const int a = s_pa[q0 + gq], b = s_pb[q0 + gq];
+                        if (lane == 0) s_Sp[a * D - (a * (a - 1)) / 2 + (b - a)] = v * s_rdet[gq];
+                    } else {
+                        if (lane == 0) s_Sp[q0 + gq] = v * s_rdet[gq];
+                    }
                 }
                 if constexpr (TILED) {
-                    const int a = s_pa[q0 + gq], b = s_pb[q0 + gq];
-                    if (lane == 0) s_Sp[a * D - (a * (a - 1)) / 2 + (b - a)] = v * s_rdet[gq];
-                } else {
-                    if (lane == 0) s_Sp[q0 + gq] = v * s_rdet[gq];
+                    // i <= j only: factor 2
+                    if (first && tid < D) s_Sp[tid * D - (tid * (tid - 1)) / 2] = 2.0 * s_rdiag[4 + tid] * s_rdiag[tid];
+                }
+                if (first) {
+                    if (tid < D) s_M[tid] = s_cc[tid] * s_s1[tid * (D + 1)];                 // M_a (:152)
+                    for (int idx = tid; idx < D * D; idx += NT) {
+                        const int k = idx / D, a = idx - k * D;
+                        const double* Ai = s_aug + a * (D * LD) + D;
+                        double s = 0.0;
+                        for (int j = 0; j < D; ++j) s = fma(Ai[k * LD + j], s_s1[a * (D + 1) + 1 + j], s);
+                        s_Vs[idx] = s_cc[a] * s;                                             // state rows of V (:153)
+                    }
+                }
+                __syncthreads();
+                GPMPC_TRACE(5);
+                if (q0 + G >= P) {
+                    // ---- P5: state update  (gp_model.py:105-108, 177-178) ---------------------------------
+                    double* s_SigNext = s_Sig2 + (cur ^ 1) * SD2;
+                    for (int idx = tid; idx < D * D; idx += NT) {
+                        const int i = idx / D, j = idx - i * D;
+                        const int a = i < j ? i : j, b = i < j ? j : i;
+                        const int q = a * D - (a * (a - 1)) / 2 + (b - a);
+                        const double S = s_Sp[q] - s_M[i] * s_M[j] + (i == j ? c_var[i] : 0.0);
+                        double cij = 0.0, cji = 0.0;
+                        for (int k = 0; k < D; ++k) {
+                            cij = fma(s_Sig[i * D + k], s_Vs[k * D + j], cij);
+                            cji = fma(s_Sig[j * D + k], s_Vs[k * D + i], cji);
+                        }
+                        const double v = S + s_Sig[idx] + (cij + cji);   // (cij + cji) commutes: Sigma stays exactly symmetric
+                        s_SigNext[idx] = v;
+                        if (member == 0) p.Sig_out[((size_t)c * (H + 1) + (t + 1)) * D * D + idx] = v;
+                    }
+                    for (int i = tid; i < D; i += NT) {
+                        const double v = s_mu[i] + s_M[i];
+                        s_mu[i] = v;
+                        if (member == 0) p.mu_out[((size_t)c * (H + 1) + (t + 1)) * D + i] = v;
+                    }
+                    cur ^= 1;
+                    __syncthreads();
+                    GPMPC_TRACE(6);
                 }
             }
-            if constexpr (TILED) {
-                // i <= j only: factor 2
-                if (first && tid < D) s_Sp[tid * D - (tid * (tid - 1)) / 2] = 2.0 * s_rdiag[4 + tid] * s_rdiag[tid];
-            }
-            if (first) {
-                if (tid < D) s_M[tid] = s_cc[tid] * s_s1[tid * (D + 1)];                 // M_a (:152)
-                for (int idx = tid; idx < D * D; idx += NT) {
-                    const int k = idx / D, a = idx - k * D;
-                    const double* Ai = s_aug + a * (D * LD) + D;
-                    double s = 0.0;
-                    for (int j = 0; j < D; ++j) s = fma(Ai[k * LD + j], s_s1[a * (D + 1) + 1 + j], s);
-                    s_Vs[idx] = s_cc[a] * s;                                             // state rows of V (:153)
-                }
-            }
-            __syncthreads();
-            GPMPC_TRACE(5);
         }
-
-        // ---- P5: state update  (gp_model.py:105-108, 177-178) ---------------------------------
-        for (int idx = tid; idx < D * D; idx += NT) {
-            const int i = idx / D, j = idx - i * D;
-            const int a = i < j ? i : j, b = i < j ? j : i;
-            const int q = a * D - (a * (a - 1)) / 2 + (b - a);
-            const double S = s_Sp[q] - s_M[i] * s_M[j] + (i == j ? c_var[i] : 0.0);
-            double cij = 0.0, cji = 0.0;
-            for (int k = 0; k < D; ++k) {
-                cij = fma(s_Sig[i * D + k], s_Vs[k * D + j], cij);
-                cji = fma(s_Sig[j * D + k], s_Vs[k * D + i], cji);
-            }
-            const double v = S + s_Sig[idx] + (cij + cji);   // (cij + cji) commutes: Sigma stays exactly symmetric
-            s_SigNext[idx] = v;
-            if (member == 0) p.Sig_out[((size_t)c * (H + 1) + (t + 1)) * D * D + idx] = v;
-        }
-        for (int i = tid; i < D; i += NT) {
-            const double v = s_mu[i] + s_M[i];
-            s_mu[i] = v;
-            if (member == 0) p.mu_out[((size_t)c * (H + 1) + (t + 1)) * D + i] = v;
-        }
-        cur ^= 1;
-        __syncthreads();
-        if constexpr (CL) {
-            if (*s_fail) {
-                // a member never arrived (bounded wait): poison the rest of the trajectory instead of spinning on
-                if (member == 0) {
-                    for (int i = tid; i < (H - t) * D; i += NT) p.mu_out[((size_t)c * (H + 1) + (t + 1)) * D + i] = __builtin_nan("");
-                    for (int i = tid; i < (H - t) * D * D; i += NT) p.Sig_out[((size_t)c * (H + 1) + (t + 1)) * D * D + i] = __builtin_nan("");
-                }
-                return;
-            }
-        }
-        GPMPC_TRACE(6);
+        if constexpr (!kTailInTrip) have_prev = true;
+        pq0 = q0;
+        q0 += G;
+        if (q0 >= P) { q0 = 0; ++t; }
     }
 #if defined(GPMPC_PROF_ON)
     if (threadIdx.x == 0 && blockIdx.x == 0) printf("PROF wave0 small algebra cycles %lld\n", prof_acc[7]);
-    if (blockIdx.x == 0 && threadIdx.x == 64) printf("PROF P1 pair problems done after %lld cycles (summed over steps)\n", prof_x[0]);
-    if (blockIdx.x == 0 && threadIdx.x == NT - 1) printf("PROF P1 last thread done after %lld\n", prof_x[1]);
-    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) printf("PROF P3 wave %d left the queue after %lld\n", (int)(threadIdx.x >> 6), prof_x[2]);
+    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && prof_chain_n > 0)      // wavefront 0; two streams: the pair problems' wavefront too
+        printf("PROF chain wave %d: end of P3 -> arrival at the P1 barrier %lld cycles over %d intervals\n", (int)(threadIdx.x >> 6), prof_chain, prof_chain_n);
+    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) printf("PROF P3 wave %d left the queue after %lld\n", (int)(threadIdx.x >> 6), prof_left);
     if (CL && threadIdx.x == 0 && (blockIdx.x & 7) == 0)
         printf("PROF member %2d xcc %d same_xcd %d\n", member, (int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)), (int)same_xcd);
     if (CL && threadIdx.x == 0 && (blockIdx.x & 7) == 0)

@@ -253,6 +253,11 @@ class HipEngine:
         return int(self.lib.gpmpc_last_cluster(self._h))
 
     @property
+    def last_pair_groups(self):
+        """Groups of output pairs the last fused-horizon / batch-major launch walked per horizon step (1 = all pairs in one pass)."""
+        return int(self.lib.gpmpc_last_pair_groups(self._h))
+
+    @property
     def last_grad_path(self):
         """Moment passes of the last `rollout_grad` (bit mask): 1 separable off-diagonal pairs, 2 tile moments of the diagonal
         pairs, 4 streaming element-wise pass, 8 the 8 < D <= 16 pass, 16 tile moments formed inside the batch-major forward."""

@@ -423,13 +423,16 @@ int gpmpc_set_cost(gpmpc_t* h, const double* target_host, const double* W_host, 
  * beyond an XCD's L2, B >= 2 x CUs).  gpmpc_last_cluster: workgroups per candidate of the last fused-horizon launch; > 1 = the
  * few-candidate cooperative form -- the reference evaluates ONE sequence per objective call (restarts_optim 1-2,
  * gp_mpc_controller.py:125-141), so while candidates x cluster fit the chip a cluster of workgroups shares each candidate's
- * horizon step (bit-identical to one workgroup per candidate at equal "rows_per_chunk").
+ * horizon step (bit-identical to one workgroup per candidate at equal "rows_per_chunk").  gpmpc_last_pair_groups: groups of output
+ * pairs the last fused-horizon or batch-major launch walked per horizon step (1 = the records of all pairs fit the LDS together;
+ * more under a small "lds_limit_kb"); 1 for the streaming kernel.
  */
 int gpmpc_rollout(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B, int H, int A,
                   int include_time, double time0, double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev,
                   double* cost_var_out_dev, double* J_out_dev, void* stream);
 int gpmpc_last_rollout_path(gpmpc_t* h);
 int gpmpc_last_cluster(gpmpc_t* h);
+int gpmpc_last_pair_groups(gpmpc_t* h);
 
 /*
  * gpmpc_rollout_linear: gpmpc_rollout -- the same arguments and outputs -- with the step of gpmpc_moments_linear in place of

@@ -75,13 +75,17 @@ SIGNATURES = {
     "gpmpc_cem_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, C.c_ulonglong, _P, _I, _P, _P, _P, _P, _P]),
     "gpmpc_cem_local": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _I, _I, C.c_ulonglong, _P, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_cem_merge": (C.c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "gpmpc_lbfgs_state_size": (C.c_longlong, [_I, _I, _I]),
+    "gpmpc_lbfgs_init": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "gpmpc_lbfgs_step": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
+    "gpmpc_lbfgs_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P]),
     "gpmpc_argmin_async": (C.c_int, [_P, _P, _I, C.c_longlong, _P, _I, _P, _P]),
     "gpmpc_argmin_export": (C.c_int, [_P, _P, _I, C.c_longlong, _P, _I, _P, _P, _P]),
     "gpmpc_argmin": (C.c_int, [_P, _P, _I, C.c_longlong, C.POINTER(_D), C.POINTER(C.c_longlong), _P]),
 }
 
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 def load(path=LIB_PATH):

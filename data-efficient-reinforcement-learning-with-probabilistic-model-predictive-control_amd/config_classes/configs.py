@@ -100,12 +100,16 @@ class ControllerConfig:
     the sequential scipy restarts: `candidate_optimizer="cem"` (cross-entropy search, one
     rollout launch per iteration) or `"lbfgs"` (the reference's scipy L-BFGS-B restarts advanced in lockstep: one
     objective + analytic-gradient launch serves every restart's pending evaluation; same result as the sequential
-    loop, wall time of the longest restart)."""
+    loop, wall time of the longest restart) or `"lbfgs_device"` (a box-constrained L-BFGS whose whole loop stays on the
+    GPU, gpmpc_lbfgs_search: `lbfgs_candidates` starts in lockstep, one objective + gradient launch and one trial point per
+    restart and iteration, `lbfgs_device_iterations` of them with `lbfgs_device_history` curvature pairs; also the one
+    gradient search of the linearised propagation)."""
 
     def __init__(self, len_horizon=15, actions_optimizer_params=None, init_from_previous_actions=True,
                  restarts_optim=1, optimize=True, num_repeat_actions=1,
                  candidate_optimizer=None, cem_candidates=256, cem_iterations=4, cem_elite_fraction=0.1,
-                 lbfgs_candidates=None, shard_over_ranks=False, feedback_gain=None, feedback_lqr_reg=0.0):
+                 lbfgs_candidates=None, shard_over_ranks=False, feedback_gain=None, feedback_lqr_reg=0.0,
+                 lbfgs_device_iterations=30, lbfgs_device_history=10):
         self.len_horizon = len_horizon
         self.actions_optimizer_params = dict(_DEFAULT_OPTIMIZER if actions_optimizer_params is None
                                              else actions_optimizer_params)
@@ -118,6 +122,9 @@ class ControllerConfig:
         self.cem_iterations = cem_iterations
         self.cem_elite_fraction = cem_elite_fraction
         self.lbfgs_candidates = lbfgs_candidates            # None: restarts_optim starting points
+        # "lbfgs_device": evaluations per restart (mirrors maxfun = 30 of the scipy solver) and pairs of the L-BFGS memory
+        self.lbfgs_device_iterations = lbfgs_device_iterations
+        self.lbfgs_device_history = lbfgs_device_history
         # one process per GPU (torch.distributed initialised by the launcher): split the candidates / restarts over the ranks.
         # Opt-in: every rank must then call get_action with the same observation (checked inside the exchange)
         self.shard_over_ranks = shard_over_ranks

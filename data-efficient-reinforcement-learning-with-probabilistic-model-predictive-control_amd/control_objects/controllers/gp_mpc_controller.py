@@ -68,13 +68,16 @@ class GpMpcController(BaseControllerObject):
         self.process_group = None      # torch.distributed group the candidates shard over (None: the default group)
         self._check_propagation_supported()
 
-    LINEARIZED_OPTIMIZERS = "optimize=False (random shooting) or candidate_optimizer='cem'"
+    LINEARIZED_OPTIMIZERS = ("optimize=False (random shooting), candidate_optimizer='cem' or, in open loop, "
+                             "candidate_optimizer='lbfgs_device'")
 
     def _check_propagation_supported(self, what=None):
         """ModelConfig.uncertainty_propagation = "linearized" has objective values only (gpmpc_rollout_linear): the searches
-        that go through `evaluate_candidates` work; the device-side search, the batched L-BFGS and the scipy L-BFGS-B loop
-        need kernels (search, gradient) the linearised path does not have.  ControllerConfig.feedback_gain (closed-loop
-        planning, gpmpc_rollout_linear_feedback) exists for the linearised propagation only."""
+        that go through `evaluate_candidates` work, and so does the device-resident L-BFGS ("lbfgs_device": gpmpc_lbfgs_search
+        drives gpmpc_rollout_linear and its backward itself) in open loop; the device-side cross-entropy search, the batched
+        L-BFGS and the scipy L-BFGS-B loop need host-side gradient plumbing the linearised path does not have.
+        ControllerConfig.feedback_gain (closed-loop planning, gpmpc_rollout_linear_feedback) exists for the linearised
+        propagation only, and not for "lbfgs_device" (its objective is the open-loop one)."""
         if self.transition_model.propagation() != "linearized":
             if getattr(self.config.controller, "feedback_gain", None) is not None:
                 raise ValueError("ControllerConfig.feedback_gain needs ModelConfig.uncertainty_propagation='linearized': "
@@ -83,6 +86,11 @@ class GpMpcController(BaseControllerObject):
         cc = self.config.controller
         if what is None:
             if not cc.optimize or getattr(cc, "candidate_optimizer", None) == "cem":
+                return
+            if getattr(cc, "candidate_optimizer", None) == "lbfgs_device":
+                if getattr(cc, "feedback_gain", None) is not None:
+                    raise ValueError("candidate_optimizer='lbfgs_device' searches the open-loop objective: it does not support "
+                                     "ControllerConfig.feedback_gain")
                 return
             what = f"candidate_optimizer={getattr(cc, 'candidate_optimizer', None)!r} with optimize=True"
         raise ValueError(f"uncertainty_propagation='linearized' does not support {what}: it has no gradient or device-search "
@@ -366,6 +374,8 @@ class GpMpcController(BaseControllerObject):
             return self._device_cross_entropy_search(state_mu, state_var)
         if getattr(cc, "candidate_optimizer", None) == "lbfgs":
             return self._batched_lbfgs_search(state_mu, state_var)
+        if getattr(cc, "candidate_optimizer", None) == "lbfgs_device":
+            return self._device_lbfgs_search(state_mu, state_var)
         opt_fun, best = np.inf, None
         for idx_restart in range(cc.restarts_optim):
             if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and idx_restart == 0:
@@ -694,6 +704,51 @@ class GpMpcController(BaseControllerObject):
         self._cache_trajectory(out, 0)
         self.actions_mpc_previous_iter = best.copy()
         return self.actions_mapper.transform_action_mpc_to_action_model(best)
+
+    def _device_lbfgs_search(self, state_mu, state_var):
+        """candidate_optimizer = "lbfgs_device": a box-constrained L-BFGS from `lbfgs_candidates` starts whose whole loop stays on
+        the GPU (gpmpc_lbfgs_search: per iteration one objective + analytic-gradient launch over the restarts' trial points and
+        one step kernel; the line search is spread over iterations, so nothing is read back until the winner).  The starts are
+        those `_batched_lbfgs_search` draws (same generator order, the shifted previous solution in slot 0).  Two host
+        synchronisations per control step: the winner, then its trajectory for the logging caches.  Works for both uncertainty
+        propagations (open loop); the restarts are not sharded over ranks."""
+        cc = self.config.controller
+        world, _ = self._ranks()
+        if world > 1:                                  # every rank raises here, before any collective
+            raise ValueError("candidate_optimizer='lbfgs_device' does not shard its restarts over ranks: switch "
+                             "ControllerConfig.shard_over_ranks off (every rank then runs the whole search)")
+        H, A = cc.len_horizon, self.actions_mapper.dim_action
+        B = int(cc.lbfgs_candidates or cc.restarts_optim)
+        iterations = int(cc.lbfgs_device_iterations)
+        x0s = []
+        for b in range(B):
+            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and b == 0:
+                x0s.append(generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A))
+            else:
+                x0s.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
+        self.lbfgs_device_starts = np.stack(x0s).astype(np.float64).reshape(B, H * A)
+        kw = {}
+        if isinstance(self.actions_mapper, DerivativeActionMapper):
+            kw = dict(max_change=np.asarray(self.config.actions.max_change_action_norm, dtype=np.float64),
+                      action_prev=self.actions_mapper.action_model_previous_iter.numpy())
+        tm = self.transition_model
+        tm.set_cost(self.config.reward)
+        best_x, best_J, J_all, status = tm.engine.lbfgs_search_host(
+            self.lbfgs_device_starts, np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), H, A,
+            iterations, history=int(cc.lbfgs_device_history),
+            propagation="linearized" if tm.propagation() == "linearized" else "moment",
+            include_time=tm.config.include_time_model, time0=float(self.iter_ctrl), **kw)
+        if not np.isfinite(best_J):
+            raise FloatingPointError("no finite objective among the restarts")
+        self.num_rollouts += B * iterations
+        self.lbfgs_evaluations = iterations
+        self.candidates_final_J, self.candidates_final_status = J_all, status
+        best_i = int(np.flatnonzero(J_all == best_J)[0])          # the first strict minimum: gpmpc_argmin's rule
+        self.best_candidate_index, self.best_candidate_J = best_i, float(best_J)
+        out = self.evaluate_candidates(best_x[None], state_mu, state_var, trajectories=True)
+        self._cache_trajectory(out, 0)
+        self.actions_mpc_previous_iter = best_x.copy()
+        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
 
     def _get_random_actions(self, state_mu, state_var):
         """Reference :155-163: one random sequence, evaluated only to fill the logging caches."""

@@ -6,6 +6,7 @@
 
 #include "gpmpc_internal.h"
 #include "lqr_gains_plan.h"
+#include "lbfgs_state.h"
 
 // ROCTx ranges around the entry points (tracing row): visible in `rocprofv3 --marker-trace` timelines
 // as gpmpc_prepare / gpmpc_rollout / gpmpc_rollout_grad / gpmpc_argmin.  The marker library is looked up at first use
@@ -55,7 +56,7 @@ static void free_buf(Buf& b) {
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 24; }
+int gpmpc_abi_version(void) { return 25; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -83,7 +84,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -734,6 +735,80 @@ int gpmpc_cem_merge(gpmpc_t* g, const double* elites_dev, int lists, int n_elite
     Handle* h = H_(g);
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_cem_merge(h, elites_dev, lists, n_elite, n, iteration, state_dev, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Device-resident L-BFGS (lbfgs_search.hip).  The mapper's parameters travel in the kernels' argument blocks.
+// the checks the three entry points share; on success `mp` holds the mapper's parameters
+static int lbfgs_entry_checks(gpmpc_t* g, int B, int H, int A, int history, int mapper, const double* max_change,
+                              const double* action_prev, LbfgsMapper& mp) {
+    bool limit = false;
+    const char* msg = lbfgs_check_shape(B, H, A, history, limit);
+    if (!msg) msg = lbfgs_check_mapper(mapper, A, max_change != nullptr, action_prev != nullptr, limit);
+    if (msg) { g->h.err = msg; return limit ? GPMPC_ERR_LIMIT : GPMPC_ERR_ARG; }
+    memset(&mp, 0, sizeof mp);
+    mp.mapper = mapper;
+    if (mapper == 1) {
+        memcpy(mp.max_change, max_change, A * sizeof(double));
+        memcpy(mp.action_prev, action_prev, A * sizeof(double));
+    }
+    return GPMPC_OK;
+}
+
+long long gpmpc_lbfgs_state_size(int B, int n, int history) {
+    bool limit = false;
+    if (lbfgs_check_shape(B, n, 1, history, limit)) return -1;
+    return (long long)make_lbfgs_layout(B, n, history).total;
+}
+
+int gpmpc_lbfgs_init(gpmpc_t* g, const double* x0_dev, int B, int H, int A, int history, int mapper, const double* max_change,
+                     const double* action_prev, double* state_dev, void* stream) {
+    Range roctx_range("gpmpc_lbfgs_init");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!x0_dev || !state_dev) return bad(g, "null argument");
+    LbfgsMapper mp;
+    int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_lbfgs_init(H_(g), x0_dev, B, H, A, history, mp, state_dev, (hipStream_t)stream);
+}
+
+int gpmpc_lbfgs_step(gpmpc_t* g, const double* J_dev, const double* grad_model_dev, int B, int H, int A, int iteration, int history,
+                     double c1, double pgtol, int mapper, const double* max_change, const double* action_prev, double* state_dev,
+                     void* stream) {
+    Range roctx_range("gpmpc_lbfgs_step");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!J_dev || !grad_model_dev || !state_dev) return bad(g, "null argument");
+    LbfgsMapper mp;
+    int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
+    if (rc) return rc;
+    if (const char* msg = lbfgs_check_step(iteration, c1, pgtol)) return bad(g, msg);
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_lbfgs_step(H_(g), J_dev, grad_model_dev, B, H, A, iteration, history, c1, pgtol, mp, state_dev, (hipStream_t)stream);
+}
+
+int gpmpc_lbfgs_search(gpmpc_t* g, const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
+                       int propagation, int first_iteration, int iterations, int history, double c1, double pgtol, int mapper,
+                       const double* max_change, const double* action_prev, const double* x0_dev, double* state_dev,
+                       double* best_out_dev, void* stream) {
+    Range roctx_range("gpmpc_lbfgs_search");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!state_dev || (first_iteration == 0 && !x0_dev)) return bad(g, "null argument");
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "search before prepare / set_factors");
+    LbfgsMapper mp;
+    int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
+    if (rc) return rc;
+    if (const char* msg = lbfgs_check_step(first_iteration, c1, pgtol)) return bad(g, msg);
+    if (iterations < 1) return bad(g, "lbfgs: need iterations >= 1");
+    if (propagation != 0 && propagation != 1) return bad(g, "lbfgs: propagation must be 0 (moment matching) or 1 (linearised)");
+    // fill_args wants an actions pointer; the search points it at the state's model actions afterwards
+    RolloutArgs a;
+    rc = fill_args(g, a, state_dev, mu0, S0, B, H, A, include_time, time0);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return run_lbfgs_search(h, a, propagation, first_iteration, iterations, history, c1, pgtol, mp, x0_dev, state_dev, best_out_dev,
+                            (hipStream_t)stream);
 }
 
 int gpmpc_rollout_timed(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,

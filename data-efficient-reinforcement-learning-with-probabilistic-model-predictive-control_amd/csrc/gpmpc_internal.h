@@ -213,6 +213,7 @@ struct Handle {
     Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
     Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward / gpmpc_rollout_linear_feedback_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
     Buf lqrws;    // gpmpc_lqr_gains: model inputs | M of the step at hand | every step's V of one chunk of candidates
+    Buf lbfgsws;  // gpmpc_lbfgs_search: J (B) | dJ/d(model actions) (B, H, A) | ones (B), the J_bar of the linearised gradient
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -483,6 +484,8 @@ int plan_rollout_grad(Handle* h, int N, int D, int A, int E, int H, int B, int B
 int launch_rollout_grad(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s, const RolloutSeeds* seeds = nullptr);
 int launch_rollout_grad_wide(Handle* h, RolloutArgs& a, double* grad_out, hipStream_t s,          // grad_wide.hip: 8 < D <= 16
                              const RolloutSeeds* seeds = nullptr);
+int check_rollout_grad_wide(Handle* h, int N, int D, int A, int E, int H, int B,           // ... its limits, before anything is
+                            size_t* mom_lds = nullptr, size_t* sweep_lds = nullptr);     // launched, and its kernels' LDS bytes
 int launch_argmin_to(Handle* h, const double* J, int B, long long first, const double* actions, int HA, double* out_dev,
                      double* out_host, hipStream_t s);     // out_host: device address of pinned host memory, or NULL
 // prepare.hip (allow_reuse = false: a full factorisation even where the cached factors could be reused or border-updated)
@@ -577,6 +580,17 @@ int run_cem_local(Handle* h, RolloutArgs& a, int B_total, int b0, int it, int n_
                   const double* first_host, int mapper, const double* max_change_host, const double* a_prev_host,
                   const double* noise_dev, const double* state_dev, double* elites_out_dev, hipStream_t s);
 int run_cem_merge(Handle* h, const double* elites_dev, int lists, int n_elite, int n, int it, double* state_dev, hipStream_t s);
+// lbfgs_search.hip: box-constrained L-BFGS over B restarts in lockstep whose loop stays on the device (lbfgs_state.h: the state
+// buffer and the argument checks).  `a` as fill_args leaves it (actions / J_out are set inside); propagation 0 moment matching,
+// 1 linearised; best_out_dev [J | restart | x (n)] or NULL
+struct LbfgsMapper;
+int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int history, const LbfgsMapper& mp, double* state_dev,
+                   hipStream_t s);
+int run_lbfgs_step(Handle* h, const double* J_dev, const double* grad_model_dev, int B, int H, int A, int iteration, int history,
+                   double c1, double pgtol, const LbfgsMapper& mp, double* state_dev, hipStream_t s);
+int run_lbfgs_search(Handle* h, RolloutArgs& a, int propagation, int first_iteration, int iterations, int history, double c1,
+                     double pgtol, const LbfgsMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
+                     hipStream_t s);
 // prepare_small.hip: the single-launch paths of a plan (PreparePath::small_whole / small_cholesky)
 int launch_prepare_small(Handle* h, const PreparePlan& pp, const double* X, const double* Y, const double* ls, const double* os,
                          const double* noise, int N, int D, int E, hipStream_t s);

@@ -840,6 +840,101 @@ class HipEngine:
         self._check(self.lib.gpmpc_cem_merge(self._h, elites.data_ptr(), lists, int(n_elite), int(n), int(iteration),
                                              state.data_ptr(), self._stream()))
 
+    # -- device-resident L-BFGS (gpmpc_lbfgs_*) -----------------------------------------------------
+    def lbfgs_state(self, B, n, history):
+        """The caller-owned state of the device L-BFGS for B restarts of n coordinates and `history` pairs: dict of named views
+        (x, g, d, xt, actions (B, n); J, alpha, status, pushes (B); S, Y (B, history, n); sy, yy (B, history) -- `pairs` is the
+        tuple (S, Y, sy, yy)) into ONE device buffer (`buffer`), laid out as include/gpmpc.h documents."""
+        B, n, m = int(B), int(n), int(history)
+        size = int(self.lib.gpmpc_lbfgs_state_size(B, n, m))
+        if size < 0:
+            raise ValueError("lbfgs_state: need 1 <= B <= 4096, 1 <= n <= 4096, 1 <= history <= 32")
+        buf = torch.zeros(size, dtype=torch.float64, device=self.device)
+        st, off = {"buffer": buf, "B": B, "n": n, "history": m}, 0
+        for k, sh in (("x", (B, n)), ("g", (B, n)), ("d", (B, n)), ("xt", (B, n)), ("actions", (B, n)), ("J", (B,)),
+                      ("alpha", (B,)), ("status", (B,)), ("pushes", (B,)), ("S", (B, m, n)), ("Y", (B, m, n)), ("sy", (B, m)),
+                      ("yy", (B, m))):
+            cnt = int(np.prod(sh))
+            st[k] = buf[off:off + cnt].view(sh)
+            off += cnt
+        assert off == size
+        st["pairs"] = (st["S"], st["Y"], st["sy"], st["yy"])
+        return st
+
+    @staticmethod
+    def _lbfgs_mapper(A, max_change, action_prev):
+        """(mapper, max_change, action_prev) as the C entries take them: either array given => the derivative mapper (a missing
+        partner is the library's GPMPC_ERR_ARG)."""
+        if max_change is None and action_prev is None:
+            return 0, None, None
+        return 1, (None if max_change is None else _host(max_change, (A,))), (None if action_prev is None else _host(action_prev, (A,)))
+
+    def lbfgs_init(self, state, x0, H, A, max_change=None, action_prev=None):
+        """gpmpc_lbfgs_init: trial point = clip(x0 (B, H*A)), its model actions, everything else reset.  No synchronisation."""
+        B, n, m = state["B"], state["n"], state["history"]
+        if n != H * A:
+            raise ValueError("the state was made for another number of coordinates")
+        x0 = self._dev(x0, (B, n))
+        mapper, mc, ap = self._lbfgs_mapper(A, max_change, action_prev)
+        self._check(self.lib.gpmpc_lbfgs_init(self._h, x0.data_ptr(), B, H, A, m, mapper, None if mc is None else _hp(mc),
+                                              None if ap is None else _hp(ap), state["buffer"].data_ptr(), self._stream()))
+        self._keep_lbfgs = (x0, state["buffer"])
+
+    def lbfgs_step(self, state, J, grad_model, H, A, iteration, c1=1e-4, pgtol=1e-5, max_change=None, action_prev=None):
+        """gpmpc_lbfgs_step: iteration `iteration` from J (B) and dJ/d(model actions) (B, H, A) at the state's `actions`.  No
+        synchronisation."""
+        B, n, m = state["B"], state["n"], state["history"]
+        if n != H * A:
+            raise ValueError("the state was made for another number of coordinates")
+        J = self._dev(J, (B,))
+        G = self._dev(grad_model, (B, H, A))
+        mapper, mc, ap = self._lbfgs_mapper(A, max_change, action_prev)
+        self._check(self.lib.gpmpc_lbfgs_step(self._h, J.data_ptr(), G.data_ptr(), B, H, A, int(iteration), m, float(c1),
+                                              float(pgtol), mapper, None if mc is None else _hp(mc),
+                                              None if ap is None else _hp(ap), state["buffer"].data_ptr(), self._stream()))
+        self._keep_lbfgs = (J, G, state["buffer"])
+
+    def lbfgs_search(self, state, mu0, S0, H, A, iterations, x0=None, first_iteration=0, c1=1e-4, pgtol=1e-5, propagation="moment",
+                     include_time=False, time0=0.0, max_change=None, action_prev=None, best_out=None):
+        """gpmpc_lbfgs_search: the whole loop on the device -- with first_iteration == 0 the init from x0 (B, H*A), then
+        `iterations` x [objective + gradient of the state's actions, step]; `propagation` "moment" or "linearized".  Returns the
+        device record [best J | restart | best x (H*A)] (`best_out`, or a new tensor).  No synchronisation."""
+        B, n, m = state["B"], state["n"], state["history"]
+        if n != H * A:
+            raise ValueError("the state was made for another number of coordinates")
+        if propagation not in ("moment", "linearized"):
+            raise ValueError("propagation must be 'moment' or 'linearized'")
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        x0 = self._dev(x0, (B, n)) if x0 is not None else None
+        if best_out is None:
+            best_out = torch.empty(2 + n, dtype=torch.float64, device=self.device)
+        mapper, mc, ap = self._lbfgs_mapper(A, max_change, action_prev)
+        self._check(self.lib.gpmpc_lbfgs_search(self._h, _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)), float(time0),
+                                                0 if propagation == "moment" else 1, int(first_iteration), int(iterations), m,
+                                                float(c1), float(pgtol), mapper, None if mc is None else _hp(mc),
+                                                None if ap is None else _hp(ap), None if x0 is None else x0.data_ptr(),
+                                                state["buffer"].data_ptr(), best_out.data_ptr(), self._stream()))
+        self._keep_lbfgs = (x0, state["buffer"], best_out)
+        return best_out
+
+    def lbfgs_search_host(self, x0, mu0, S0, H, A, iterations, history=10, c1=1e-4, pgtol=1e-5, propagation="moment",
+                          include_time=False, time0=0.0, max_change=None, action_prev=None):
+        """The device L-BFGS from the starts x0 (B, H*A) -> (best x (H*A,), best J, per-restart J (B,), per-restart status (B,)) as
+        numpy, with ONE host synchronisation (a single copy of the winner record and the per-restart values)."""
+        x0 = np.asarray(x0, dtype=np.float64)
+        B, n = x0.shape
+        st = self.lbfgs_state(B, n, history)
+        out = torch.empty(2 + n + 2 * B, dtype=torch.float64, device=self.device)
+        self.lbfgs_search(st, mu0, S0, H, A, iterations, x0=x0, c1=c1, pgtol=pgtol, propagation=propagation,
+                          include_time=include_time, time0=time0, max_change=max_change, action_prev=action_prev,
+                          best_out=out[:2 + n])
+        out[2 + n:2 + n + B].copy_(st["J"])
+        out[2 + n + B:].copy_(st["status"])
+        host = out.cpu().numpy()                                # the one synchronisation
+        return host[2:2 + n].copy(), float(host[0]), host[2 + n:2 + n + B].copy(), host[2 + n + B:].astype(np.int64)
+
     # -- a8 ----------------------------------------------------------------------------
     # sharding.select_best_async looks for this attribute: argmin_async can deliver the record to pinned host memory itself
     argmin_exports_host = True

@@ -699,6 +699,56 @@ int gpmpc_cem_local(gpmpc_t* h, const double* mu0_host, const double* S0_host, i
 int gpmpc_cem_merge(gpmpc_t* h, const double* elites_dev, int lists, int n_elite, int n, int iteration, double* state_dev,
                     void* stream);
 
+/*
+ * Gradient-based candidate optimisation whose loop stays on the device: a box-constrained (projected) L-BFGS over [0,1]^n,
+ * n = H*A, for B restarts in lockstep -- the counterpart of gpmpc_cem_search for the analytic gradient (the reference: one scipy
+ * L-BFGS-B solve per restart, gp_mpc_controller.py:125-141).  EVERY iteration evaluates exactly ONE trial point per restart, so
+ * the launch sequence never depends on data: the line search (Armijo, constant c1, step halved on a reject) is spread over
+ * iterations.  Iteration k is handed (Jt, Gt) = objective and dJ/d(model actions) at the state's `actions`:
+ *   chain rule to the optimiser vector (mapper 0: Gt; 1: gt[s,a] = 2 max_change[a] sum_{t>=s} Gt[t,a], clamp passed through);
+ *   k = 0 accepts (non-finite Jt / gt: status 3); k > 0 accepts when Jt and gt are finite and Jt <= J + c1 g.(xt - x);
+ *   accept (k > 0): the pair s = xt - x, y = gt - g joins the ring of `history` pairs when s.y > 1e-10 |s| |y| (the oldest
+ *     leaves), then (x, J, g) <- (xt, Jt, gt);
+ *   reject: alpha <- alpha / 2, below 2^-40 status 2, else xt = clip(x + alpha d);
+ *   after an accept: free set F = coordinates not (x <= 0, g > 0) and not (x >= 1, g < 0), gf = g on F; max |gf| <= pgtol: status 1;
+ *     else the two-loop recursion on gf (initial scaling s.y / y.y of the newest pair, 1 / |gf| without pairs), d = -r on F;
+ *     d.gf not < 0: d = -gf and all pairs are dropped; alpha = 1, xt = clip(x + d);
+ *   a restart whose status != 0 keeps xt = x, is still evaluated (lockstep) and its state no longer changes;
+ *   actions = mapper(xt) (mapper as in gpmpc_cem_search: 0 identity reshape, 1 scaled deltas + running sum + pass-through clamp).
+ * J never increases along x, so x is each restart's best point.  status: 0 running, 1 converged, 2 step underflow, 3 non-finite
+ * start.
+ *
+ * state_dev is the CALLER's buffer of gpmpc_lbfgs_state_size(B, n, history) doubles (< 0: bad arguments), m = history:
+ *   x (B,n) | g (B,n) | d (B,n) | xt (B,n) | actions (B,n) | J (B) | alpha (B) | status (B) | pushes (B)
+ *   | S (B,m,n) | Y (B,m,n) | sy (B,m) | yy (B,m)
+ * status and pushes are whole numbers stored as doubles; `pushes` counts the pairs pushed since the last drop: min(pushes, m) are
+ * held, the newest in ring slot (pushes - 1) mod m.  sy / yy = s.y and y.y of the slot's pair.
+ *
+ * gpmpc_lbfgs_init: xt = clip(x0_dev (B,n)), actions = mapper(xt), status 0, alpha 1, everything else 0.  gpmpc_lbfgs_step: one
+ * iteration k = `iteration` from supplied J_dev (B) and grad_model_dev (B,H,A) -- the unit the search is built from (and the parity
+ * tests' hook); neither needs a model.  gpmpc_lbfgs_search (model and gpmpc_set_cost needed): with first_iteration == 0 the init
+ * from x0_dev, then `iterations` times [objective + gradient of the state's actions; step k = first_iteration + i] -- propagation
+ * 0: the launches of gpmpc_rollout_grad, 1: those of gpmpc_rollout_linear then gpmpc_rollout_linear_backward with J_bar = 1 --
+ * and the winner by gpmpc_argmin's rule over the restarts' J to best_out_dev (2 + n) = [J | restart | x] (may be NULL).
+ * first_iteration > 0 continues a state (x0_dev unused).  All three are asynchronous on `stream`, without host synchronisation;
+ * the host arrays are read before the call returns.
+ *
+ * Limits: 1 <= B <= 4096, 1 <= history <= 32, 1 <= n <= 4096, iterations >= 1, first_iteration / iteration >= 0, 0 < c1 < 1,
+ * pgtol >= 0; mapper 1 needs max_change_host (A) and action_prev_host (A) (GPMPC_ERR_ARG) and A <= 24 (GPMPC_ERR_LIMIT).  A shape
+ * outside the gradient kernels is GPMPC_ERR_LIMIT as in gpmpc_rollout_grad.  Every such error is reported before anything is
+ * enqueued or written.
+ */
+long long gpmpc_lbfgs_state_size(int B, int n, int history);
+int gpmpc_lbfgs_init(gpmpc_t* h, const double* x0_dev, int B, int H, int A, int history, int mapper, const double* max_change_host,
+                     const double* action_prev_host, double* state_dev, void* stream);
+int gpmpc_lbfgs_step(gpmpc_t* h, const double* J_dev, const double* grad_model_dev, int B, int H, int A, int iteration, int history,
+                     double c1, double pgtol, int mapper, const double* max_change_host, const double* action_prev_host,
+                     double* state_dev, void* stream);
+int gpmpc_lbfgs_search(gpmpc_t* h, const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time, double time0,
+                       int propagation, int first_iteration, int iterations, int history, double c1, double pgtol, int mapper,
+                       const double* max_change_host, const double* action_prev_host, const double* x0_dev, double* state_dev,
+                       double* best_out_dev, void* stream);
+
 /* bench.py: `reps` rollouts back to back bracketed by HIP events recorded on `stream`; average ms per launch in *ms_host. */
 int gpmpc_rollout_timed(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B, int H, int A,
                         int include_time, double time0, double* J_out_dev, int reps, float* ms_host, void* stream);

@@ -1,0 +1,101 @@
+// Stand-alone host check of the state layout and the argument checks of gpmpc_lbfgs_* (csrc/lbfgs_state.h): over a grid of
+// (B, n, history), the limits included, the arrays of the state follow one another without gaps or overlap, and every index the
+// init and step kernels may form for the last restart, the last ring slot and the last coordinate stays inside its array; the
+// checks accept exactly the documented box.  Build with a host sanitizer and run on the CPU:
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/host_checks/lbfgs_state_check.cpp -o state_check && ./state_check
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../../data-efficient-reinforcement-learning-with-probabilistic-model-predictive-control_amd/csrc/lbfgs_state.h"
+
+using namespace gpmpc_hip;
+
+static int fails = 0;
+#define CHECK(c)                                                        \
+    do {                                                                \
+        if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++fails; } \
+    } while (0)
+
+static void one(int B, int n, int m) {
+    const LbfgsLayout L = make_lbfgs_layout(B, n, m);
+    const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
+    const size_t offs[] = {L.x, L.g, L.d, L.xt, L.actions, L.J, L.alpha, L.status, L.pushes, L.S, L.Y, L.sy, L.yy};
+    const size_t lens[] = {Bn, Bn, Bn, Bn, Bn, (size_t)B, (size_t)B, (size_t)B, (size_t)B, Bm * n, Bm * n, Bm, Bm};
+    size_t o = 0;
+    for (int i = 0; i < 13; ++i) {
+        CHECK(offs[i] == o);
+        o += lens[i];
+    }
+    CHECK(L.total == o);
+    if (L.total > ((size_t)256 << 20) / sizeof(double)) return;
+    // touch what the kernels touch for the first and the last restart (the sanitizer sees an overrun)
+    std::vector<double> st(L.total, 0.0);
+    for (int b : {0, B - 1}) {
+        const size_t bn = (size_t)b * n, bm = (size_t)b * m;
+        for (size_t base : {L.x, L.g, L.d, L.xt, L.actions}) {
+            st[base + bn] += 1.0;
+            st[base + bn + (n - 1)] += 1.0;
+        }
+        for (size_t base : {L.J, L.alpha, L.status, L.pushes}) st[base + b] += 1.0;
+        for (size_t base : {L.S, L.Y}) {
+            st[base + bn * m] += 1.0;                                        // slot 0, coordinate 0
+            st[base + bn * m + (size_t)(m - 1) * n + (n - 1)] += 1.0;        // the last slot's last coordinate
+            CHECK(bn * m + (size_t)(m - 1) * n + (n - 1) < Bm * n);
+        }
+        for (size_t base : {L.sy, L.yy}) {
+            st[base + bm] += 1.0;
+            st[base + bm + (m - 1)] += 1.0;
+        }
+    }
+    // ring arithmetic of the step kernel: the slots of the held pairs are distinct and inside [0, m)
+    for (int pushes : {0, 1, m - 1, m, m + 1, 3 * m + 2, 1000000}) {
+        if (pushes < 0) continue;
+        const int held = pushes < m ? pushes : m;
+        std::vector<int> seen(m, 0);
+        for (int j = 0; j < held; ++j) {
+            const int slot = (pushes - 1 - j) % m;
+            CHECK(slot >= 0 && slot < m);
+            if (slot >= 0 && slot < m) CHECK(seen[slot]++ == 0);
+        }
+        CHECK(pushes % m >= 0 && pushes % m < m);
+    }
+}
+
+int main() {
+    const int Bs[] = {1, 2, 65, 4096}, ns[] = {1, 63, 64, 65, 200, 4096}, ms[] = {1, 3, 10, 32};
+    int cnt = 0;
+    for (int B : Bs)
+        for (int n : ns)
+            for (int m : ms) {
+                one(B, n, m);
+                ++cnt;
+            }
+    bool limit = false;
+    CHECK(lbfgs_check_shape(1, 1, 1, 1, limit) == nullptr);
+    CHECK(lbfgs_check_shape(4096, 64, 64, 32, limit) == nullptr);
+    CHECK(lbfgs_check_shape(0, 1, 1, 1, limit) && !limit);
+    CHECK(lbfgs_check_shape(1, 0, 1, 1, limit) && !limit);
+    CHECK(lbfgs_check_shape(1, 1, 0, 1, limit) && !limit);
+    CHECK(lbfgs_check_shape(1, 1, 1, 0, limit) && !limit);
+    CHECK(lbfgs_check_shape(4097, 1, 1, 1, limit) && limit);
+    CHECK(lbfgs_check_shape(1, 1, 1, 33, limit) && limit);
+    CHECK(lbfgs_check_shape(1, 4097, 1, 1, limit) && limit);
+    CHECK(lbfgs_check_shape(1, 65, 64, 1, limit) && limit);
+    CHECK(lbfgs_check_shape(1, 2147483647LL, 2147483647LL, 1, limit) && limit);         // no overflow in H * A
+    CHECK(lbfgs_check_mapper(0, 100, false, false, limit) == nullptr);
+    CHECK(lbfgs_check_mapper(1, 24, true, true, limit) == nullptr);
+    CHECK(lbfgs_check_mapper(2, 1, true, true, limit) && !limit);
+    CHECK(lbfgs_check_mapper(1, 1, true, false, limit) && !limit);
+    CHECK(lbfgs_check_mapper(1, 1, false, true, limit) && !limit);
+    CHECK(lbfgs_check_mapper(1, 25, true, true, limit) && limit);
+    CHECK(lbfgs_check_step(0, 1e-4, 0.0) == nullptr);
+    CHECK(lbfgs_check_step(-1, 1e-4, 0.0) != nullptr);
+    const double nan = std::strtod("nan", nullptr);
+    for (double c1 : {0.0, 1.0, -0.5, 2.0, nan}) CHECK(lbfgs_check_step(0, c1, 0.0) != nullptr);
+    for (double pg : {-1e-300, nan}) CHECK(lbfgs_check_step(0, 1e-4, pg) != nullptr);
+    // the mapper's parameters fit the argument block
+    CHECK(sizeof(LbfgsMapper) <= 512);
+    std::printf("%d layouts checked, %d failures\n", cnt, fails);
+    return fails ? 1 : 0;
+}

@@ -1,4 +1,5 @@
 // abi.hip -- extern "C" entry points of libgpmpc_hip.so (declared in include/gpmpc.h).
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -54,6 +55,96 @@ static void free_buf(Buf& b) {
     b.cap = 0;
 }
 
+// gpmpc_set_option: one row per name.  A row with a message rejects, with that message, a value outside [lo, hi] or off the
+// multiple `mult` (a power of two); a row without one takes any value through the (int) cast, raised to `lo`.
+struct Option {
+    const char* name;
+    int Handle::*field;
+    long long lo = INT_MIN, hi = INT_MAX;
+    int mult = 1;
+    const char* msg = nullptr;
+    long long Handle::*wide = nullptr;   // the one option wider than an int
+    bool cast_first = false;             // the value goes through the (int) cast before the range check
+};
+
+constexpr long long kChunkMax = 1 << 24;
+const Option kOptions[] = {
+    {"threads", &Handle::opt_threads},
+    {"lds_limit_kb", &Handle::opt_lds_kb},
+    {"force_global_scratch", &Handle::opt_force_global},
+    {"rows_per_chunk", &Handle::opt_rows_per_chunk},
+    {"force_path", &Handle::opt_force_path},
+    {"force_separable", &Handle::opt_force_sep},
+    {"cols_per_lane", &Handle::opt_cols_per_lane},
+    {"grad_share_cu", &Handle::opt_grad_share},
+    {"grad_chunk_rows", &Handle::opt_grad_chunk, 0, 64, 4, "grad_chunk_rows: 0 (auto) or a multiple of 4 up to 64", nullptr, true},
+    {"predict_chunk_rows", &Handle::opt_predict_chunk, 0, kChunkMax, 64, "predict_chunk_rows: 0 (auto) or a multiple of 64"},
+    {"predict_backward_chunk_rows", &Handle::opt_predict_bwd_chunk, 0, kChunkMax, 64,
+     "predict_backward_chunk_rows: 0 (auto) or a multiple of 64"},
+    {"predict_cov_chunk_rows", &Handle::opt_predict_cov_chunk, 0, kChunkMax, 64, "predict_cov_chunk_rows: 0 (auto) or a multiple of 64"},
+    {"moments_chunk_points", &Handle::opt_moments_chunk, 0, kChunkMax, 1, "moments_chunk_points: 0 (auto) or a number of points"},
+    {"moments_backward_chunk_points", &Handle::opt_moments_bwd_chunk, 0, kChunkMax, 1,
+     "moments_backward_chunk_points: 0 (auto) or a number of points"},
+    {"moments_linear_chunk_points", &Handle::opt_moments_linear_chunk, 0, kChunkMax, 1,
+     "moments_linear_chunk_points: 0 (auto) or a number of points"},
+    {"moments_linear_backward_chunk_points", &Handle::opt_moments_linear_bwd_chunk, 0, kChunkMax, 1,
+     "moments_linear_backward_chunk_points: 0 (auto) or a number of points"},
+    {"lqr_gains_chunk_points", &Handle::opt_lqr_gains_chunk, 0, kChunkMax, 1, "lqr_gains_chunk_points: 0 (auto) or a number of candidates"},
+    {"sparse_chunk_points", &Handle::opt_sparse_chunk, 0, kChunkMax, 64, "sparse_chunk_points: 0 (auto) or a multiple of 64"},
+    {"select_inducing_max_mb", nullptr, 1, LLONG_MAX, 1, "select_inducing_max_mb: a number of MiB >= 1", &Handle::opt_select_max_mb},
+    {"incremental", &Handle::opt_incremental},
+    {"grad_stream", &Handle::opt_grad_stream},
+    {"grad_separable", &Handle::opt_grad_sep},
+    {"grad_tiles", &Handle::opt_grad_tiles},
+    {"grad_mean", &Handle::opt_grad_mean},
+    {"prepare_overlap", &Handle::opt_prepare_overlap},
+    {"prepare_fuse", &Handle::opt_prepare_fuse},
+    {"prepare_invcols", &Handle::opt_prepare_invcols},
+    {"prepare_inv_batch", &Handle::opt_prepare_inv_batch},
+    {"fused_prepare", &Handle::opt_fused_prepare},
+    {"gram_shared", &Handle::opt_gram_shared},
+    {"outer_block", &Handle::opt_outer_block},
+    {"tile128", &Handle::opt_tile128},
+    {"block128", &Handle::opt_block128},
+    {"outer_min_n", &Handle::opt_outer_min_n, 256},
+    {"inner_left", &Handle::opt_inner_left},
+    {"outer2", &Handle::opt_outer2},
+    {"refresh_every", &Handle::opt_refresh_every},
+    {"pair_tiles", &Handle::opt_pair_tiles},
+    {"cluster_debug", &Handle::opt_cl_dbg},
+    {"cluster", &Handle::opt_cluster, 0, 32, 1, "cluster: 0 (auto), 1 (never) or 2..32 workgroups per candidate"},
+};
+
+// The checks the seven query-point entries (gpmpc_predict*, gpmpc_moments*) share, in their order: a handle, a cached model, for
+// the moments entries the compiled limits, the model's D and E, a count >= 0.  `name` heads the messages; `count_name` is the
+// count's letter in them, NULL for gpmpc_predict_cov, which checks its own two counts.
+static int query_checks(gpmpc_t* g, const char* name, const char* count_name, int count, int D, int E, bool check_limits) {
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    auto fail = [&](const char* tail) { return bad(g, (std::string(name) + tail).c_str()); };
+    if (!h->ready) return fail(" before prepare / set_factors / mll");
+    if (check_limits && (D > GPMPC_MAX_D || E > GPMPC_MAX_E)) {
+        fail(": D or E beyond the compiled limits");
+        return GPMPC_ERR_LIMIT;
+    }
+    if (D != h->D || E != h->E) return fail(": D / E differ from the cached model");
+    if (count_name && count < 0) return fail((std::string(": ") + count_name + " < 0").c_str());
+    return GPMPC_OK;
+}
+
+// ... and what all of them but gpmpc_predict_cov do next: the entry's own pointers (`have_ptrs`) where there is work to do,
+// nothing for an empty call, then the device and the entry's run_* function.
+template <class Run>
+static int query_entry(gpmpc_t* g, const char* name, const char* count_name, int count, int D, int E, bool check_limits,
+                       bool have_ptrs, Run run) {
+    int rc = query_checks(g, name, count_name, count, D, E, check_limits);
+    if (rc) return rc;
+    if (count > 0 && !have_ptrs) return bad(g, "null argument");
+    if (count == 0) return GPMPC_OK;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run(H_(g));
+}
+
 extern "C" {
 
 int gpmpc_abi_version(void) { return 25; }
@@ -105,88 +196,15 @@ const char* gpmpc_last_error(const gpmpc_t* g) { return g ? g->h.err.c_str() : "
 int gpmpc_set_option(gpmpc_t* g, const char* name, long long value) {
     if (!g || !name) return GPMPC_ERR_ARG;
     Handle* h = H_(g);
-    if (!strcmp(name, "threads")) h->opt_threads = (int)value;
-    else if (!strcmp(name, "lds_limit_kb")) h->opt_lds_kb = (int)value;
-    else if (!strcmp(name, "force_global_scratch")) h->opt_force_global = (int)value;
-    else if (!strcmp(name, "rows_per_chunk")) h->opt_rows_per_chunk = (int)value;
-    else if (!strcmp(name, "force_path")) h->opt_force_path = (int)value;
-    else if (!strcmp(name, "force_separable")) h->opt_force_sep = (int)value;
-    else if (!strcmp(name, "cols_per_lane")) h->opt_cols_per_lane = (int)value;
-    else if (!strcmp(name, "grad_share_cu")) h->opt_grad_share = (int)value;
-    else if (!strcmp(name, "grad_chunk_rows")) {
-        const int v = (int)value;
-        if (v < 0 || v > 64 || (v & 3)) { h->err = "grad_chunk_rows: 0 (auto) or a multiple of 4 up to 64"; return GPMPC_ERR_ARG; }
-        h->opt_grad_chunk = v;
+    for (const Option& o : kOptions) {
+        if (strcmp(name, o.name)) continue;
+        const long long v = (!o.msg || o.cast_first) ? (long long)(int)value : value;
+        if (o.msg && (v < o.lo || v > o.hi || (v & (o.mult - 1)))) { h->err = o.msg; return GPMPC_ERR_ARG; }
+        if (o.wide) h->*o.wide = v;
+        else h->*o.field = (int)(v < o.lo ? o.lo : v);
+        return GPMPC_OK;
     }
-    else if (!strcmp(name, "predict_chunk_rows")) {
-        const long long v = value;
-        if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
-        h->opt_predict_chunk = (int)v;
-    }
-    else if (!strcmp(name, "predict_backward_chunk_rows")) {
-        const long long v = value;
-        if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_backward_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
-        h->opt_predict_bwd_chunk = (int)v;
-    }
-    else if (!strcmp(name, "predict_cov_chunk_rows")) {
-        const long long v = value;
-        if (v < 0 || v > (1 << 24) || (v & 63)) { h->err = "predict_cov_chunk_rows: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
-        h->opt_predict_cov_chunk = (int)v;
-    }
-    else if (!strcmp(name, "moments_chunk_points")) {
-        if (value < 0 || value > (1 << 24)) { h->err = "moments_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
-        h->opt_moments_chunk = (int)value;
-    }
-    else if (!strcmp(name, "moments_backward_chunk_points")) {
-        if (value < 0 || value > (1 << 24)) { h->err = "moments_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
-        h->opt_moments_bwd_chunk = (int)value;
-    }
-    else if (!strcmp(name, "moments_linear_chunk_points")) {
-        if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
-        h->opt_moments_linear_chunk = (int)value;
-    }
-    else if (!strcmp(name, "moments_linear_backward_chunk_points")) {
-        if (value < 0 || value > (1 << 24)) { h->err = "moments_linear_backward_chunk_points: 0 (auto) or a number of points"; return GPMPC_ERR_ARG; }
-        h->opt_moments_linear_bwd_chunk = (int)value;
-    }
-    else if (!strcmp(name, "lqr_gains_chunk_points")) {
-        if (value < 0 || value > (1 << 24)) { h->err = "lqr_gains_chunk_points: 0 (auto) or a number of candidates"; return GPMPC_ERR_ARG; }
-        h->opt_lqr_gains_chunk = (int)value;
-    }
-    else if (!strcmp(name, "sparse_chunk_points")) {
-        if (value < 0 || value > (1 << 24) || (value & 63)) { h->err = "sparse_chunk_points: 0 (auto) or a multiple of 64"; return GPMPC_ERR_ARG; }
-        h->opt_sparse_chunk = (int)value;
-    }
-    else if (!strcmp(name, "select_inducing_max_mb")) {
-        if (value < 1) { h->err = "select_inducing_max_mb: a number of MiB >= 1"; return GPMPC_ERR_ARG; }
-        h->opt_select_max_mb = value;
-    }
-    else if (!strcmp(name, "incremental")) h->opt_incremental = (int)value;
-    else if (!strcmp(name, "grad_stream")) h->opt_grad_stream = (int)value;
-    else if (!strcmp(name, "grad_separable")) h->opt_grad_sep = (int)value;
-    else if (!strcmp(name, "grad_tiles")) h->opt_grad_tiles = (int)value;
-    else if (!strcmp(name, "grad_mean")) h->opt_grad_mean = (int)value;
-    else if (!strcmp(name, "prepare_overlap")) h->opt_prepare_overlap = (int)value;
-    else if (!strcmp(name, "prepare_fuse")) h->opt_prepare_fuse = (int)value;
-    else if (!strcmp(name, "prepare_invcols")) h->opt_prepare_invcols = (int)value;
-    else if (!strcmp(name, "prepare_inv_batch")) h->opt_prepare_inv_batch = (int)value;
-    else if (!strcmp(name, "fused_prepare")) h->opt_fused_prepare = (int)value;
-    else if (!strcmp(name, "gram_shared")) h->opt_gram_shared = (int)value;
-    else if (!strcmp(name, "outer_block")) h->opt_outer_block = (int)value;
-    else if (!strcmp(name, "tile128")) h->opt_tile128 = (int)value;
-    else if (!strcmp(name, "block128")) h->opt_block128 = (int)value;
-    else if (!strcmp(name, "outer_min_n")) h->opt_outer_min_n = (int)value < 256 ? 256 : (int)value;
-    else if (!strcmp(name, "inner_left")) h->opt_inner_left = (int)value;
-    else if (!strcmp(name, "outer2")) h->opt_outer2 = (int)value;
-    else if (!strcmp(name, "refresh_every")) h->opt_refresh_every = (int)value;
-    else if (!strcmp(name, "pair_tiles")) h->opt_pair_tiles = (int)value;
-    else if (!strcmp(name, "cluster_debug")) h->opt_cl_dbg = (int)value;
-    else if (!strcmp(name, "cluster")) {
-        if (value < 0 || value > 32) { h->err = "cluster: 0 (auto), 1 (never) or 2..32 workgroups per candidate"; return GPMPC_ERR_ARG; }
-        h->opt_cluster = (int)value;
-    }
-    else return bad(g, "unknown option");
-    return GPMPC_OK;
+    return bad(g, "unknown option");
 }
 
 static int check_dims(gpmpc_t* g, int N, int D, int E) {
@@ -260,118 +278,64 @@ int gpmpc_read_factors(gpmpc_t* g, double* iK_dst, double* beta_dst, void* strea
 int gpmpc_predict(gpmpc_t* g, const double* Xq, int M, int D, int E, const double* noises_host, double* mean_out,
                   double* var_out, void* stream) {
     Range roctx_range("gpmpc_predict");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "predict before prepare / set_factors / mll");
-    if (D != h->D || E != h->E) return bad(g, "predict: D / E differ from the cached model");
-    if (M < 0) return bad(g, "predict: M < 0");
-    if (M > 0 && !Xq) return bad(g, "null argument");
-    if (M == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_predict(h, Xq, M, noises_host, mean_out, var_out, (hipStream_t)stream);
+    return query_entry(g, "predict", "M", M, D, E, false, Xq != nullptr, [&](Handle* h) {
+        return run_predict(h, Xq, M, noises_host, mean_out, var_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_predict_backward(gpmpc_t* g, const double* Xq, int M, int D, int E, const double* mean_bar, const double* var_bar,
                            double* Xq_bar_out, void* stream) {
     Range roctx_range("gpmpc_predict_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "predict_backward before prepare / set_factors / mll");
-    if (D != h->D || E != h->E) return bad(g, "predict_backward: D / E differ from the cached model");
-    if (M < 0) return bad(g, "predict_backward: M < 0");
-    if (M > 0 && (!Xq || !Xq_bar_out)) return bad(g, "null argument");
-    if (M == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_predict_backward(h, Xq, M, mean_bar, var_bar, Xq_bar_out, (hipStream_t)stream);
+    return query_entry(g, "predict_backward", "M", M, D, E, false, Xq && Xq_bar_out, [&](Handle* h) {
+        return run_predict_backward(h, Xq, M, mean_bar, var_bar, Xq_bar_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_predict_cov(gpmpc_t* g, const double* Xa, int Ma, const double* Xb, int Mb, int D, int E, const double* noises_host,
                       double* cov_out, void* stream) {
     Range roctx_range("gpmpc_predict_cov");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "predict_cov before prepare / set_factors / mll");
-    if (D != h->D || E != h->E) return bad(g, "predict_cov: D / E differ from the cached model");
+    int rc = query_checks(g, "predict_cov", nullptr, 0, D, E, false);
+    if (rc) return rc;
     if (Ma < 0 || (Xb && Mb < 0)) return bad(g, "predict_cov: negative number of points");
     if (Xb && noises_host) return bad(g, "predict_cov: the cross form takes no noise");
     if (Ma > (1 << 22) || (Xb && Mb > (1 << 22))) return bad(g, "predict_cov: more than 2^22 points");
     if (Ma == 0 || (Xb && Mb == 0)) return GPMPC_OK;
     if (!Xa || !cov_out) return bad(g, "null argument");
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_predict_cov(h, Xa, Ma, Xb, Mb, noises_host, cov_out, (hipStream_t)stream);
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_predict_cov(H_(g), Xa, Ma, Xb, Mb, noises_host, cov_out, (hipStream_t)stream);
 }
 
 int gpmpc_moments(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, double* M_out, double* S_out,
                   double* V_out, void* stream) {
     Range roctx_range("gpmpc_moments");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "moments before prepare / set_factors / mll");
-    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
-        h->err = "moments: D or E beyond the compiled limits";
-        return GPMPC_ERR_LIMIT;
-    }
-    if (D != h->D || E != h->E) return bad(g, "moments: D / E differ from the cached model");
-    if (P < 0) return bad(g, "moments: P < 0");
-    if (P > 0 && (!mu || !M_out)) return bad(g, "null argument");
-    if (P == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_moments(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+    return query_entry(g, "moments", "P", P, D, E, true, mu && M_out, [&](Handle* h) {
+        return run_moments(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_moments_linear(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, double* M_out, double* S_out,
                          double* V_out, void* stream) {
     Range roctx_range("gpmpc_moments_linear");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "moments_linear before prepare / set_factors / mll");
-    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
-        h->err = "moments_linear: D or E beyond the compiled limits";
-        return GPMPC_ERR_LIMIT;
-    }
-    if (D != h->D || E != h->E) return bad(g, "moments_linear: D / E differ from the cached model");
-    if (P < 0) return bad(g, "moments_linear: P < 0");
-    if (P > 0 && !mu) return bad(g, "null argument");
-    if (P == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_moments_linear(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+    return query_entry(g, "moments_linear", "P", P, D, E, true, mu != nullptr, [&](Handle* h) {
+        return run_moments_linear(h, mu, var, P, M_out, S_out, V_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_moments_backward(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, const double* M_bar,
                            const double* S_bar, const double* V_bar, double* mu_bar_out, double* var_bar_out, void* stream) {
     Range roctx_range("gpmpc_moments_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "moments_backward before prepare / set_factors / mll");
-    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
-        h->err = "moments_backward: D or E beyond the compiled limits";
-        return GPMPC_ERR_LIMIT;
-    }
-    if (D != h->D || E != h->E) return bad(g, "moments_backward: D / E differ from the cached model");
-    if (P < 0) return bad(g, "moments_backward: P < 0");
-    if (P > 0 && !mu) return bad(g, "null argument");
-    if (P == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_moments_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
+    return query_entry(g, "moments_backward", "P", P, D, E, true, mu != nullptr, [&](Handle* h) {
+        return run_moments_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_moments_linear_backward(gpmpc_t* g, const double* mu, const double* var, int P, int D, int E, const double* M_bar,
                                   const double* S_bar, const double* V_bar, double* mu_bar_out, double* var_bar_out,
                                   void* stream) {
     Range roctx_range("gpmpc_moments_linear_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    Handle* h = H_(g);
-    if (!h->ready) return bad(g, "moments_linear_backward before prepare / set_factors / mll");
-    if (D > GPMPC_MAX_D || E > GPMPC_MAX_E) {
-        h->err = "moments_linear_backward: D or E beyond the compiled limits";
-        return GPMPC_ERR_LIMIT;
-    }
-    if (D != h->D || E != h->E) return bad(g, "moments_linear_backward: D / E differ from the cached model");
-    if (P < 0) return bad(g, "moments_linear_backward: P < 0");
-    if (P > 0 && !mu) return bad(g, "null argument");
-    if (P == 0) return GPMPC_OK;
-    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
-    return run_moments_linear_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
+    return query_entry(g, "moments_linear_backward", "P", P, D, E, true, mu != nullptr, [&](Handle* h) {
+        return run_moments_linear_backward(h, mu, var, P, M_bar, S_bar, V_bar, mu_bar_out, var_bar_out, (hipStream_t)stream);
+    });
 }
 
 int gpmpc_mll(gpmpc_t* g, const double* X, const double* Y, const double* ls, const double* os, const double* noise,
@@ -455,50 +419,45 @@ static int fill_args(gpmpc_t* g, RolloutArgs& a, const double* actions, const do
     return GPMPC_OK;
 }
 
+// The body of the three forward rollout entries: `linear` false is moment matching (no gains), true the linearised step, in closed
+// loop where `gains` is given.  The trajectory alone (predict_trajectory, gp_model.py:60-110) needs no cost settings.
+static int rollout_entry(gpmpc_t* g, bool linear, const double* actions, const double* gains, int gains_per_candidate,
+                         const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0, double* mu_out,
+                         double* Sig_out, double* cm_out, double* cv_out, double* J_out, void* stream) {
+    if (!g) return GPMPC_ERR_ARG;
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
+    if (rc) return rc;
+    if (gains && A < 1) return bad(g, "feedback gains need A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
+    if (!linear) return launch_rollout(H_(g), a, (hipStream_t)stream);
+    return run_rollout_linear(H_(g), a, (hipStream_t)stream, gains, gains && gains_per_candidate != 0);
+}
+
 int gpmpc_rollout(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
                   int include_time, double time0, double* mu_out, double* Sig_out, double* cm_out, double* cv_out,
                   double* J_out, void* stream) {
     Range roctx_range("gpmpc_rollout");
-    if (!g) return GPMPC_ERR_ARG;
-    RolloutArgs a;
-    // the trajectory alone (predict_trajectory, gp_model.py:60-110) needs no cost settings
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
-    if (rc) return rc;
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
-    return launch_rollout(H_(g), a, (hipStream_t)stream);
+    return rollout_entry(g, false, actions, nullptr, 0, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out, cv_out, J_out,
+                         stream);
 }
 
 int gpmpc_rollout_linear(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
                          int include_time, double time0, double* mu_out, double* Sig_out, double* cm_out, double* cv_out,
                          double* J_out, void* stream) {
     Range roctx_range("gpmpc_rollout_linear");
-    if (!g) return GPMPC_ERR_ARG;
-    RolloutArgs a;
-    // as gpmpc_rollout: the trajectory alone needs no cost settings
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
-    if (rc) return rc;
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
-    return run_rollout_linear(H_(g), a, (hipStream_t)stream);
+    return rollout_entry(g, true, actions, nullptr, 0, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out, cv_out, J_out,
+                         stream);
 }
 
 int gpmpc_rollout_linear_feedback(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate,
                                   const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
                                   double* mu_out, double* Sig_out, double* cm_out, double* cv_out, double* J_out, void* stream) {
-    // without gains the call IS gpmpc_rollout_linear: the same launches, the same bits
-    if (!gains)
-        return gpmpc_rollout_linear(g, actions, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out, cv_out, J_out,
-                                    stream);
-    Range roctx_range("gpmpc_rollout_linear_feedback");
-    if (!g) return GPMPC_ERR_ARG;
-    RolloutArgs a;
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
-    if (rc) return rc;
-    if (A < 1) return bad(g, "feedback gains need A >= 1");
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
-    return run_rollout_linear(H_(g), a, (hipStream_t)stream, gains, gains_per_candidate != 0);
+    // without gains the call IS gpmpc_rollout_linear: the same launches, the same bits, the same range
+    Range roctx_range(gains ? "gpmpc_rollout_linear_feedback" : "gpmpc_rollout_linear");
+    return rollout_entry(g, true, actions, gains, gains_per_candidate, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out,
+                         cv_out, J_out, stream);
 }
 
 int gpmpc_lqr_gains(gpmpc_t* g, const double* actions, const double* mu0, int B, int H, int A, int include_time, double time0,
@@ -535,21 +494,34 @@ int gpmpc_rollout_grad(gpmpc_t* g, const double* actions, const double* mu0, con
     return launch_rollout_grad(H_(g), a, grad_out, (hipStream_t)stream);
 }
 
+// The body of the three backward rollout entries, `linear` and `gains` as in rollout_entry.  The trajectory's cotangents alone need
+// no cost settings; a cost or objective seed needs gpmpc_set_cost for this (D, A).
+static int rollout_backward_entry(gpmpc_t* g, bool linear, const double* actions, const double* gains, int gains_per_candidate,
+                                  const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
+                                  const double* mu_bar, const double* Sig_bar, const double* cm_bar, const double* cv_bar,
+                                  const double* J_bar, double* actions_bar_out, double* gains_bar_out, double* mu0_bar_out,
+                                  double* S0_bar_out, void* stream) {
+    if (!g) return GPMPC_ERR_ARG;
+    if (!actions_bar_out) return bad(g, "null argument");
+    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "gradient needs A >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!linear) return launch_rollout_grad(H_(g), a, actions_bar_out, s, &sd);
+    if (!gains) return run_rollout_linear_backward(H_(g), a, sd, actions_bar_out, s);
+    return run_rollout_linear_feedback_backward(H_(g), a, sd, gains, gains_per_candidate != 0, actions_bar_out, gains_bar_out, s);
+}
+
 int gpmpc_rollout_backward(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
                            int include_time, double time0, const double* mu_bar, const double* Sig_bar, const double* cm_bar,
                            const double* cv_bar, const double* J_bar, double* actions_bar_out, double* mu0_bar_out,
                            double* S0_bar_out, void* stream) {
     Range roctx_range("gpmpc_rollout_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    if (!actions_bar_out) return bad(g, "null argument");
-    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
-    RolloutArgs a;
-    // the trajectory's cotangents alone need no cost settings; a cost or objective seed needs gpmpc_set_cost for this (D, A)
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
-    if (rc) return rc;
-    if (A < 1) return bad(g, "gradient needs A >= 1");
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    return launch_rollout_grad(H_(g), a, actions_bar_out, (hipStream_t)stream, &sd);
+    return rollout_backward_entry(g, false, actions, nullptr, 0, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar, cm_bar, cv_bar,
+                                  J_bar, actions_bar_out, nullptr, mu0_bar_out, S0_bar_out, stream);
 }
 
 int gpmpc_rollout_linear_backward(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,
@@ -557,16 +529,8 @@ int gpmpc_rollout_linear_backward(gpmpc_t* g, const double* actions, const doubl
                                   const double* cm_bar, const double* cv_bar, const double* J_bar, double* actions_bar_out,
                                   double* mu0_bar_out, double* S0_bar_out, void* stream) {
     Range roctx_range("gpmpc_rollout_linear_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    if (!actions_bar_out) return bad(g, "null argument");
-    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
-    RolloutArgs a;
-    // as gpmpc_rollout_backward: the trajectory's cotangents alone need no cost settings
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
-    if (rc) return rc;
-    if (A < 1) return bad(g, "gradient needs A >= 1");
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    return run_rollout_linear_backward(H_(g), a, sd, actions_bar_out, (hipStream_t)stream);
+    return rollout_backward_entry(g, true, actions, nullptr, 0, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar, cm_bar, cv_bar,
+                                  J_bar, actions_bar_out, nullptr, mu0_bar_out, S0_bar_out, stream);
 }
 
 int gpmpc_rollout_linear_feedback_backward(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate,
@@ -574,24 +538,11 @@ int gpmpc_rollout_linear_feedback_backward(gpmpc_t* g, const double* actions, co
                                            double time0, const double* mu_bar, const double* Sig_bar, const double* cm_bar,
                                            const double* cv_bar, const double* J_bar, double* actions_bar_out,
                                            double* gains_bar_out, double* mu0_bar_out, double* S0_bar_out, void* stream) {
-    if (!gains) {
-        if (!g) return GPMPC_ERR_ARG;
-        if (gains_bar_out) return bad(g, "gains_bar_out without gains");
-        // without gains the call IS gpmpc_rollout_linear_backward: the same launches, the same bits
-        return gpmpc_rollout_linear_backward(g, actions, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar, cm_bar, cv_bar,
-                                             J_bar, actions_bar_out, mu0_bar_out, S0_bar_out, stream);
-    }
-    Range roctx_range("gpmpc_rollout_linear_feedback_backward");
-    if (!g) return GPMPC_ERR_ARG;
-    if (!actions_bar_out) return bad(g, "null argument");
-    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
-    RolloutArgs a;
-    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
-    if (rc) return rc;
-    if (A < 1) return bad(g, "gradient needs A >= 1");
-    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
-    return run_rollout_linear_feedback_backward(H_(g), a, sd, gains, gains_per_candidate != 0, actions_bar_out, gains_bar_out,
-                                                (hipStream_t)stream);
+    if (g && !gains && gains_bar_out) return bad(g, "gains_bar_out without gains");
+    // without gains the call IS gpmpc_rollout_linear_backward: the same launches, the same bits, the same range
+    Range roctx_range(gains ? "gpmpc_rollout_linear_feedback_backward" : "gpmpc_rollout_linear_backward");
+    return rollout_backward_entry(g, true, actions, gains, gains_per_candidate, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar,
+                                  cm_bar, cv_bar, J_bar, actions_bar_out, gains_bar_out, mu0_bar_out, S0_bar_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -19,6 +19,11 @@ def _hp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr(t):
+    """The address of a device tensor, None (NULL) for None."""
+    return t.data_ptr() if t is not None else None
+
+
 def feedback_gains_layout(shape, B, H, A, D):
     """How a feedback-gain array of `shape` reaches gpmpc_rollout_linear_feedback: (per_candidate, every_step).  (A, D) is one
     gain for every step (every_step: broadcast over H, passed as shared), (H, A, D) a shared sequence, (B, H, A, D) one sequence
@@ -101,6 +106,13 @@ class HipEngine:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _rows(self, X, what, rows):
+        """X on the device, checked to be a matrix: (`rows`, E) `what`."""
+        X = self._dev(X)
+        if X.dim() != 2:
+            raise ValueError(f"expected {what} of shape ({rows}, E), got {tuple(X.shape)}")
+        return X
 
     def set_option(self, name, value):
         self._check(self.lib.gpmpc_set_option(self._h, name.encode(), int(value)))
@@ -291,9 +303,7 @@ class HipEngine:
         """GP posterior at the query inputs Xq (M, E) from the cached model: dict(mean (M, D), var (M, D)) of device tensors
         (only the requested ones).  `noises` (D,): added to the variance, as likelihood(model(x)) does.  Asynchronous on the
         current stream."""
-        Xq = self._dev(Xq)
-        if Xq.dim() != 2:
-            raise ValueError(f"expected query inputs of shape (M, E), got {tuple(Xq.shape)}")
+        Xq = self._rows(Xq, "query inputs", "M")
         M, E = Xq.shape
         D = self.D
         nz = _host(noises, (D,)) if noises is not None else None
@@ -303,8 +313,7 @@ class HipEngine:
         if var:
             out["var"] = torch.empty((M, D), dtype=torch.float64, device=self.device)
         self._check(self.lib.gpmpc_predict(self._h, Xq.data_ptr(), M, D, E, _hp(nz) if nz is not None else None,
-                                           out["mean"].data_ptr() if mean else None,
-                                           out["var"].data_ptr() if var else None, self._stream()))
+                                           _ptr(out.get("mean")), _ptr(out.get("var")), self._stream()))
         self._keep_predict = Xq              # alive until the asynchronous call has read it
         return out
 
@@ -313,16 +322,13 @@ class HipEngine:
         gradients mean_bar (M, D) and var_bar (M, D), each None for zero -> Xq_bar (M, E), a device tensor.  The noise added
         by `predict` is a constant and takes no part.  Without var_bar no matrix product runs.  Asynchronous on the current
         stream."""
-        Xq = self._dev(Xq)
-        if Xq.dim() != 2:
-            raise ValueError(f"expected query inputs of shape (M, E), got {tuple(Xq.shape)}")
+        Xq = self._rows(Xq, "query inputs", "M")
         M, E = Xq.shape
         D = self.D
         mb = self._dev(mean_bar, (M, D)) if mean_bar is not None else None
         vb = self._dev(var_bar, (M, D)) if var_bar is not None else None
         out = torch.empty((M, E), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_predict_backward(self._h, Xq.data_ptr(), M, D, E, ptr(mb), ptr(vb), out.data_ptr(),
+        self._check(self.lib.gpmpc_predict_backward(self._h, Xq.data_ptr(), M, D, E, _ptr(mb), _ptr(vb), out.data_ptr(),
                                                     self._stream()))
         self._keep_predict_backward = (Xq, mb, vb)   # alive until the asynchronous call has read them
         return out
@@ -333,9 +339,7 @@ class HipEngine:
         `noises` must be None.  Joint form, Xb None: (D, Ma, Ma), the exactly symmetric covariance matrix of the set, whose
         diagonal is `predict`'s variance; `noises` (D,) is added to the diagonal, as likelihood(model(x)) does.  Not clamped,
         no jitter.  Asynchronous on the current stream."""
-        Xa = self._dev(Xa)
-        if Xa.dim() != 2:
-            raise ValueError(f"expected query inputs of shape (Ma, E), got {tuple(Xa.shape)}")
+        Xa = self._rows(Xa, "query inputs", "Ma")
         Ma, E = Xa.shape
         D = self.D
         Mb = Ma
@@ -348,18 +352,14 @@ class HipEngine:
         out = torch.empty((D, Ma, Mb), dtype=torch.float64, device=self.device)
         if Xb is not None and Mb == 0:       # an empty tensor has no address: the library would read the NULL as the joint form
             return out
-        self._check(self.lib.gpmpc_predict_cov(self._h, Xa.data_ptr(), Ma, Xb.data_ptr() if Xb is not None else None, Mb, D, E,
+        self._check(self.lib.gpmpc_predict_cov(self._h, Xa.data_ptr(), Ma, _ptr(Xb), Mb, D, E,
                                                _hp(nz) if nz is not None else None, out.data_ptr(), self._stream()))
         self._keep_predict_cov = (Xa, Xb)    # alive until the asynchronous call has read them
         return out
 
-    def moments(self, mu, var=None, S=True, V=True):
-        """Moment-matched one-step prediction (predict_next_state_change, gp_model.py:112-180) at P Gaussian inputs from the
-        cached model: mu (P, E), var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D), V (P, E, D)) of device tensors
-        (S / V only when requested).  Asynchronous on the current stream."""
-        mu = self._dev(mu)
-        if mu.dim() != 2:
-            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
+    def _moments(self, name, mu, var, S, V):
+        """`moments` and `moments_linear`: the arguments and the dict are the same, `name` picks the library's entry."""
+        mu = self._rows(mu, "input means", "P")
         P, E = mu.shape
         D = self.D
         vr = self._dev(var, (P, E, E)) if var is not None else None
@@ -368,11 +368,35 @@ class HipEngine:
             out["S"] = torch.empty((P, D, D), dtype=torch.float64, device=self.device)
         if V:
             out["V"] = torch.empty((P, E, D), dtype=torch.float64, device=self.device)
-        self._check(self.lib.gpmpc_moments(self._h, mu.data_ptr(), vr.data_ptr() if vr is not None else None, P, D, E,
-                                           out["M"].data_ptr(), out["S"].data_ptr() if S else None,
-                                           out["V"].data_ptr() if V else None, self._stream()))
-        self._keep_moments = (mu, vr)        # alive until the asynchronous call has read them
+        self._check(getattr(self.lib, "gpmpc_" + name)(self._h, mu.data_ptr(), _ptr(vr), P, D, E, out["M"].data_ptr(),
+                                                       _ptr(out.get("S")), _ptr(out.get("V")), self._stream()))
+        setattr(self, "_keep_" + name, (mu, vr))             # alive until the asynchronous call has read them
         return out
+
+    def _moments_backward(self, name, mu, var, M_bar, S_bar, V_bar, mu_bar, var_bar):
+        """`moments_backward` and `moments_linear_backward`: as `_moments`."""
+        mu = self._rows(mu, "input means", "P")
+        P, E = mu.shape
+        D = self.D
+        vr = self._dev(var, (P, E, E)) if var is not None else None
+        Mb = self._dev(M_bar, (P, D)) if M_bar is not None else None
+        Sb = self._dev(S_bar, (P, D, D)) if S_bar is not None else None
+        Vb = self._dev(V_bar, (P, E, D)) if V_bar is not None else None
+        out = {}
+        if mu_bar:
+            out["mu_bar"] = torch.empty((P, E), dtype=torch.float64, device=self.device)
+        if var_bar:
+            out["var_bar"] = torch.empty((P, E, E), dtype=torch.float64, device=self.device)
+        self._check(getattr(self.lib, "gpmpc_" + name)(self._h, mu.data_ptr(), _ptr(vr), P, D, E, _ptr(Mb), _ptr(Sb), _ptr(Vb),
+                                                       _ptr(out.get("mu_bar")), _ptr(out.get("var_bar")), self._stream()))
+        setattr(self, "_keep_" + name, (mu, vr, Mb, Sb, Vb))   # alive until the asynchronous call has read them
+        return out
+
+    def moments(self, mu, var=None, S=True, V=True):
+        """Moment-matched one-step prediction (predict_next_state_change, gp_model.py:112-180) at P Gaussian inputs from the
+        cached model: mu (P, E), var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D), V (P, E, D)) of device tensors
+        (S / V only when requested).  Asynchronous on the current stream."""
+        return self._moments("moments", mu, var, S, V)
 
     def moments_linear(self, mu, var=None, S=True, V=True):
         """First-order (linearised) one-step prediction at P Gaussian inputs from the cached model (gpmpc_moments_linear): the
@@ -380,72 +404,21 @@ class HipEngine:
         var (P, E, E) or None (zero) -> dict(M (P, D), S (P, D, D) = V^T var V + diag(posterior variance), V (P, E, D) =
         dM/dmu) of device tensors (S / V only when requested).  Without S no matrix product runs: M and the whole mean
         Jacobian in one GEMV-class pass.  Asynchronous on the current stream."""
-        mu = self._dev(mu)
-        if mu.dim() != 2:
-            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
-        P, E = mu.shape
-        D = self.D
-        vr = self._dev(var, (P, E, E)) if var is not None else None
-        out = {"M": torch.empty((P, D), dtype=torch.float64, device=self.device)}
-        if S:
-            out["S"] = torch.empty((P, D, D), dtype=torch.float64, device=self.device)
-        if V:
-            out["V"] = torch.empty((P, E, D), dtype=torch.float64, device=self.device)
-        self._check(self.lib.gpmpc_moments_linear(self._h, mu.data_ptr(), vr.data_ptr() if vr is not None else None, P, D, E,
-                                                  out["M"].data_ptr(), out["S"].data_ptr() if S else None,
-                                                  out["V"].data_ptr() if V else None, self._stream()))
-        self._keep_moments_linear = (mu, vr)     # alive until the asynchronous call has read them
-        return out
+        return self._moments("moments_linear", mu, var, S, V)
 
     def moments_backward(self, mu, var=None, M_bar=None, S_bar=None, V_bar=None, mu_bar=True, var_bar=True):
         """Reverse-mode product of `moments` (autograd through predict_next_state_change, gp_model.py:112-180): mu (P, E),
         var (P, E, E) or None (zero), upstream gradients M_bar (P, D), S_bar (P, D, D), V_bar (P, E, D), each None for zero ->
         dict(mu_bar (P, E), var_bar (P, E, E)) of device tensors (each only when requested).  var_bar is the symmetric part of
         the covariance gradient.  Without S_bar the pairwise pass is skipped.  Asynchronous on the current stream."""
-        mu = self._dev(mu)
-        if mu.dim() != 2:
-            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
-        P, E = mu.shape
-        D = self.D
-        vr = self._dev(var, (P, E, E)) if var is not None else None
-        Mb = self._dev(M_bar, (P, D)) if M_bar is not None else None
-        Sb = self._dev(S_bar, (P, D, D)) if S_bar is not None else None
-        Vb = self._dev(V_bar, (P, E, D)) if V_bar is not None else None
-        out = {}
-        if mu_bar:
-            out["mu_bar"] = torch.empty((P, E), dtype=torch.float64, device=self.device)
-        if var_bar:
-            out["var_bar"] = torch.empty((P, E, E), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_moments_backward(self._h, mu.data_ptr(), ptr(vr), P, D, E, ptr(Mb), ptr(Sb), ptr(Vb),
-                                                    ptr(out.get("mu_bar")), ptr(out.get("var_bar")), self._stream()))
-        self._keep_moments_backward = (mu, vr, Mb, Sb, Vb)   # alive until the asynchronous call has read them
-        return out
+        return self._moments_backward("moments_backward", mu, var, M_bar, S_bar, V_bar, mu_bar, var_bar)
 
     def moments_linear_backward(self, mu, var=None, M_bar=None, S_bar=None, V_bar=None, mu_bar=True, var_bar=True):
         """Reverse-mode product of `moments_linear` (gpmpc_moments_linear_backward): mu (P, E), var (P, E, E) or None (zero),
         upstream gradients M_bar (P, D), S_bar (P, D, D), V_bar (P, E, D), each None for zero -> dict(mu_bar (P, E),
         var_bar (P, E, E)) of device tensors (each only when requested).  var_bar is the symmetric part of the covariance
         gradient, exactly symmetric.  Without S_bar no matrix product runs.  Asynchronous on the current stream."""
-        mu = self._dev(mu)
-        if mu.dim() != 2:
-            raise ValueError(f"expected input means of shape (P, E), got {tuple(mu.shape)}")
-        P, E = mu.shape
-        D = self.D
-        vr = self._dev(var, (P, E, E)) if var is not None else None
-        Mb = self._dev(M_bar, (P, D)) if M_bar is not None else None
-        Sb = self._dev(S_bar, (P, D, D)) if S_bar is not None else None
-        Vb = self._dev(V_bar, (P, E, D)) if V_bar is not None else None
-        out = {}
-        if mu_bar:
-            out["mu_bar"] = torch.empty((P, E), dtype=torch.float64, device=self.device)
-        if var_bar:
-            out["var_bar"] = torch.empty((P, E, E), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_moments_linear_backward(self._h, mu.data_ptr(), ptr(vr), P, D, E, ptr(Mb), ptr(Sb), ptr(Vb),
-                                                           ptr(out.get("mu_bar")), ptr(out.get("var_bar")), self._stream()))
-        self._keep_moments_linear_backward = (mu, vr, Mb, Sb, Vb)   # alive until the asynchronous call has read them
-        return out
+        return self._moments_backward("moments_linear_backward", mu, var, M_bar, S_bar, V_bar, mu_bar, var_bar)
 
     # -- a6 ----------------------------------------------------------------------------
     def set_cost(self, target, W, W_T, kappa, clip_to_zero=False, state_min=None, state_max=None):
@@ -463,14 +436,8 @@ class HipEngine:
         self._cost = (D, A)
 
     # -- a3-a5 -------------------------------------------------------------------------
-    def rollout(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None):
-        """actions (B,H,A) -> dict(J (B,), [mu (B,H+1,D), Sig (B,H+1,D,D)], [cost_mu, cost_var (B,H+1)]).
-        `out` = the dict of a previous call with the same shapes: its tensors are overwritten (no allocation)."""
-        actions = self._dev(actions)
-        B, H, A = actions.shape
-        D = self.D
-        mu0 = _host(mu0, (D,))
-        S0 = _host(S0, (D, D))
+    def _trajectory_out(self, out, B, H, D, A, trajectories, stage_costs):
+        """The dict a forward rollout fills: allocated as asked for, or the caller's `out` once its shapes are checked."""
         if out is None:
             out = {}
             # the objective needs gpmpc_set_cost FOR THIS (D, A); a trajectory-only call passes no cost pointer at all
@@ -484,42 +451,48 @@ class HipEngine:
                 out["cost_var"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
         elif ("J" in out and out["J"].shape != (B,)) or ("mu" in out and out["mu"].shape != (B, H + 1, D)):
             raise ValueError("`out` does not match the batch shape")
-
-        def ptr(k):
-            return out[k].data_ptr() if k in out else None
-        self._check(self.lib.gpmpc_rollout(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
-                                           float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"), ptr("cost_var"),
-                                           ptr("J"), self._stream()))
         return out
 
-    def rollout_linear(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None):
-        """`rollout` with the linearised step (gpmpc_rollout_linear) in place of moment matching: the same arguments, the same
-        dict.  Asynchronous on the current stream."""
+    def _gains(self, gains, B, H, A, D):
+        """Feedback gains as the closed-loop entries take them: (device tensor (H, A, D) or (B, H, A, D), per_candidate), or
+        (None, False)."""
+        if gains is None:
+            return None, False
+        gains = torch.as_tensor(gains, dtype=torch.float64)
+        per_candidate, every_step = feedback_gains_layout(gains.shape, B, H, A, D)
+        if every_step:
+            gains = gains.expand(H, A, D)
+        return self._dev(gains), per_candidate
+
+    def _rollout(self, name, actions, mu0, S0, include_time, time0, trajectories, stage_costs, out, closed_loop=False, gains=None):
+        """`rollout`, `rollout_linear` and `rollout_linear_feedback`: `name` picks the library's entry; the closed-loop one takes
+        (gains, per_candidate) behind the actions."""
         actions = self._dev(actions)
         B, H, A = actions.shape
         D = self.D
         mu0 = _host(mu0, (D,))
         S0 = _host(S0, (D, D))
-        if out is None:
-            out = {}
-            if stage_costs or self._cost == (D, A):
-                out["J"] = torch.empty(B, dtype=torch.float64, device=self.device)
-            if trajectories:
-                out["mu"] = torch.empty((B, H + 1, D), dtype=torch.float64, device=self.device)
-                out["Sig"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
-            if stage_costs:
-                out["cost_mu"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
-                out["cost_var"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
-        elif ("J" in out and out["J"].shape != (B,)) or ("mu" in out and out["mu"].shape != (B, H + 1, D)):
-            raise ValueError("`out` does not match the batch shape")
-
-        def ptr(k):
-            return out[k].data_ptr() if k in out else None
-        self._check(self.lib.gpmpc_rollout_linear(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A,
-                                                  int(bool(include_time)), float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"),
-                                                  ptr("cost_var"), ptr("J"), self._stream()))
-        self._keep_rollout_linear = actions      # alive until the asynchronous call has read it
+        gain_args = ()
+        if closed_loop:
+            gains, per_candidate = self._gains(gains, B, H, A, D)
+            gain_args = (_ptr(gains), int(per_candidate))
+        out = self._trajectory_out(out, B, H, D, A, trajectories, stage_costs)
+        self._check(getattr(self.lib, "gpmpc_" + name)(
+            self._h, actions.data_ptr(), *gain_args, _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)), float(time0),
+            _ptr(out.get("mu")), _ptr(out.get("Sig")), _ptr(out.get("cost_mu")), _ptr(out.get("cost_var")), _ptr(out.get("J")),
+            self._stream()))
+        setattr(self, "_keep_" + name, (actions, gains))      # alive until the asynchronous call has read them
         return out
+
+    def rollout(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None):
+        """actions (B,H,A) -> dict(J (B,), [mu (B,H+1,D), Sig (B,H+1,D,D)], [cost_mu, cost_var (B,H+1)]).
+        `out` = the dict of a previous call with the same shapes: its tensors are overwritten (no allocation)."""
+        return self._rollout("rollout", actions, mu0, S0, include_time, time0, trajectories, stage_costs, out)
+
+    def rollout_linear(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None):
+        """`rollout` with the linearised step (gpmpc_rollout_linear) in place of moment matching: the same arguments, the same
+        dict.  Asynchronous on the current stream."""
+        return self._rollout("rollout_linear", actions, mu0, S0, include_time, time0, trajectories, stage_costs, out)
 
     def rollout_linear_feedback(self, actions, gains, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True,
                                 out=None):
@@ -527,39 +500,8 @@ class HipEngine:
         Sig and the stage costs are those of that policy; mu is `rollout_linear`'s.  `gains` (model space): (A, D) one gain for
         every step and candidate, (H, A, D) one sequence shared by the candidates, or (B, H, A, D); None: `rollout_linear`.
         The same dict.  Asynchronous on the current stream."""
-        actions = self._dev(actions)
-        B, H, A = actions.shape
-        D = self.D
-        mu0 = _host(mu0, (D,))
-        S0 = _host(S0, (D, D))
-        per_candidate = False
-        if gains is not None:
-            gains = torch.as_tensor(gains, dtype=torch.float64)
-            per_candidate, every_step = feedback_gains_layout(gains.shape, B, H, A, D)
-            if every_step:
-                gains = gains.expand(H, A, D)
-            gains = self._dev(gains)
-        if out is None:
-            out = {}
-            if stage_costs or self._cost == (D, A):
-                out["J"] = torch.empty(B, dtype=torch.float64, device=self.device)
-            if trajectories:
-                out["mu"] = torch.empty((B, H + 1, D), dtype=torch.float64, device=self.device)
-                out["Sig"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
-            if stage_costs:
-                out["cost_mu"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
-                out["cost_var"] = torch.empty((B, H + 1), dtype=torch.float64, device=self.device)
-        elif ("J" in out and out["J"].shape != (B,)) or ("mu" in out and out["mu"].shape != (B, H + 1, D)):
-            raise ValueError("`out` does not match the batch shape")
-
-        def ptr(k):
-            return out[k].data_ptr() if k in out else None
-        self._check(self.lib.gpmpc_rollout_linear_feedback(
-            self._h, actions.data_ptr(), gains.data_ptr() if gains is not None else None, int(per_candidate), _hp(mu0), _hp(S0),
-            B, H, A, int(bool(include_time)), float(time0), ptr("mu"), ptr("Sig"), ptr("cost_mu"), ptr("cost_var"), ptr("J"),
-            self._stream()))
-        self._keep_rollout_linear_feedback = (actions, gains)      # alive until the asynchronous call has read them
-        return out
+        return self._rollout("rollout_linear_feedback", actions, mu0, S0, include_time, time0, trajectories, stage_costs, out,
+                             closed_loop=True, gains=gains)
 
     def lqr_gains(self, actions, mu0, include_time=False, time0=0.0, reg=0.0, want_cost_to_go=False, want_flags=False):
         """The LQR feedback gains of the linearisation along each candidate's nominal trajectory on the loaded quadratic cost
@@ -576,11 +518,9 @@ class HipEngine:
             out["P"] = torch.empty((B, H + 1, D, D), dtype=torch.float64, device=self.device)
         if want_flags:
             out["flags"] = torch.empty(B, dtype=torch.int32, device=self.device)
-
-        def ptr(k):
-            return out[k].data_ptr() if k in out else None
         self._check(self.lib.gpmpc_lqr_gains(self._h, actions.data_ptr(), _hp(mu0), B, H, A, int(bool(include_time)), float(time0),
-                                             float(reg), ptr("gains"), ptr("P"), ptr("flags"), self._stream()))
+                                             float(reg), out["gains"].data_ptr(), _ptr(out.get("P")), _ptr(out.get("flags")),
+                                             self._stream()))
         self._keep_lqr_gains = actions           # alive until the asynchronous call has read it
         return out
 
@@ -624,6 +564,42 @@ class HipEngine:
                                                 out["cost_var"].data_ptr() if trajectories else None, self._stream()))
         return out
 
+    def _seeds(self, B, H, D, mu_bar, Sig_bar, cost_mu_bar, cost_var_bar, J_bar):
+        """The upstream gradients of a trajectory dict on the device, in the order the backward entries take them; None stays."""
+        return (self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None,
+                self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None,
+                self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None,
+                self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None,
+                self._dev(J_bar, (B,)) if J_bar is not None else None)
+
+    def _rollout_backward(self, name, actions, mu0, S0, include_time, time0, seeds, want_initial, closed_loop=False, gains=None,
+                          want_gains=False):
+        """`rollout_backward`, `rollout_linear_backward` and `rollout_linear_feedback_backward`: `name` picks the library's entry;
+        the closed-loop one takes (gains, per_candidate) behind the actions and gains_bar behind actions_bar."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        gain_args = ()
+        if closed_loop:
+            gains, per_candidate = self._gains(gains, B, H, A, D)
+            gain_args = (_ptr(gains), int(per_candidate))
+        seeds = self._seeds(B, H, D, *seeds)
+        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
+        if want_gains and gains is not None:
+            out["gains_bar"] = torch.empty((B, H, A, D), dtype=torch.float64, device=self.device)
+        if want_initial:
+            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
+            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
+        gains_bar_arg = (_ptr(out.get("gains_bar")),) if closed_loop else ()
+        self._check(getattr(self.lib, "gpmpc_" + name)(
+            self._h, actions.data_ptr(), *gain_args, _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)), float(time0),
+            *map(_ptr, seeds), out["actions_bar"].data_ptr(), *gains_bar_arg, _ptr(out.get("mu0_bar")), _ptr(out.get("S0_bar")),
+            self._stream()))
+        setattr(self, "_keep_" + name, (actions, gains) + seeds)   # alive until the asynchronous call has read them
+        return out
+
     def rollout_backward(self, actions, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None, cost_mu_bar=None,
                          cost_var_bar=None, J_bar=None, want_initial=True):
         """Reverse-mode product of `rollout` (autograd through predict_trajectory + get_rewards_trajectory, gp_model.py:60-110,
@@ -632,27 +608,8 @@ class HipEngine:
         dict of device tensors actions_bar (B,H,A) and, with `want_initial`, mu0_bar (B,D) and S0_bar (B,D,D) per candidate
         (S0_bar the symmetric part).  The forward is recomputed inside the call (gpmpc_rollout_backward).  Cost / J seeds need
         set_cost; shapes outside the gradient kernels raise GpmpcError(GPMPC_ERR_LIMIT).  Asynchronous on the current stream."""
-        actions = self._dev(actions)
-        B, H, A = actions.shape
-        D = self.D
-        mu0 = _host(mu0, (D,))
-        S0 = _host(S0, (D, D))
-        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
-        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
-        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
-        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
-        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
-        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
-        if want_initial:
-            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
-            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_rollout_backward(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
-                                                    float(time0), ptr(mb), ptr(Sb), ptr(cmb), ptr(cvb), ptr(Jb),
-                                                    out["actions_bar"].data_ptr(), ptr(out.get("mu0_bar")),
-                                                    ptr(out.get("S0_bar")), self._stream()))
-        self._keep_rollout_backward = (actions, mb, Sb, cmb, cvb, Jb)   # alive until the asynchronous call has read them
-        return out
+        return self._rollout_backward("rollout_backward", actions, mu0, S0, include_time, time0,
+                                      (mu_bar, Sig_bar, cost_mu_bar, cost_var_bar, J_bar), want_initial)
 
     def rollout_linear_backward(self, actions, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None,
                                 cost_mu_bar=None, cost_var_bar=None, J_bar=None, want_initial=True):
@@ -660,27 +617,8 @@ class HipEngine:
         `rollout_backward`: dict of device tensors actions_bar (B,H,A) and, with `want_initial`, mu0_bar (B,D) and S0_bar (B,D,D)
         per candidate (S0_bar the symmetric part).  The forward is recomputed inside the call.  Cost / J seeds need set_cost.
         Asynchronous on the current stream."""
-        actions = self._dev(actions)
-        B, H, A = actions.shape
-        D = self.D
-        mu0 = _host(mu0, (D,))
-        S0 = _host(S0, (D, D))
-        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
-        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
-        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
-        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
-        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
-        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
-        if want_initial:
-            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
-            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_rollout_linear_backward(self._h, actions.data_ptr(), _hp(mu0), _hp(S0), B, H, A,
-                                                           int(bool(include_time)), float(time0), ptr(mb), ptr(Sb), ptr(cmb),
-                                                           ptr(cvb), ptr(Jb), out["actions_bar"].data_ptr(),
-                                                           ptr(out.get("mu0_bar")), ptr(out.get("S0_bar")), self._stream()))
-        self._keep_rollout_linear_backward = (actions, mb, Sb, cmb, cvb, Jb)   # alive until the asynchronous call has read them
-        return out
+        return self._rollout_backward("rollout_linear_backward", actions, mu0, S0, include_time, time0,
+                                      (mu_bar, Sig_bar, cost_mu_bar, cost_var_bar, J_bar), want_initial)
 
     def rollout_linear_grad(self, actions, mu0, S0, include_time=False, time0=0.0):
         """Objective of the linearised rollout and its analytic gradient: dict(J (B,), grad (B,H,A) = dJ/d(actions)) of device
@@ -702,36 +640,9 @@ class HipEngine:
         whatever the layout of `gains`: reduce it as the gains were broadcast -- `gains_bar.sum(0)` for a shared (H, A, D)
         sequence, `gains_bar.sum((0, 1))` for one (A, D) gain.  gains None: `rollout_linear_backward` (no gains_bar).  The
         forward is recomputed inside the call.  Cost / J seeds need set_cost.  Asynchronous on the current stream."""
-        actions = self._dev(actions)
-        B, H, A = actions.shape
-        D = self.D
-        mu0 = _host(mu0, (D,))
-        S0 = _host(S0, (D, D))
-        per_candidate = False
-        if gains is not None:
-            gains = torch.as_tensor(gains, dtype=torch.float64)
-            per_candidate, every_step = feedback_gains_layout(gains.shape, B, H, A, D)
-            if every_step:
-                gains = gains.expand(H, A, D)
-            gains = self._dev(gains)
-        mb = self._dev(mu_bar, (B, H + 1, D)) if mu_bar is not None else None
-        Sb = self._dev(Sig_bar, (B, H + 1, D, D)) if Sig_bar is not None else None
-        cmb = self._dev(cost_mu_bar, (B, H + 1)) if cost_mu_bar is not None else None
-        cvb = self._dev(cost_var_bar, (B, H + 1)) if cost_var_bar is not None else None
-        Jb = self._dev(J_bar, (B,)) if J_bar is not None else None
-        out = {"actions_bar": torch.empty((B, H, A), dtype=torch.float64, device=self.device)}
-        if want_gains and gains is not None:
-            out["gains_bar"] = torch.empty((B, H, A, D), dtype=torch.float64, device=self.device)
-        if want_initial:
-            out["mu0_bar"] = torch.empty((B, D), dtype=torch.float64, device=self.device)
-            out["S0_bar"] = torch.empty((B, D, D), dtype=torch.float64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._check(self.lib.gpmpc_rollout_linear_feedback_backward(
-            self._h, actions.data_ptr(), ptr(gains), int(per_candidate), _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)),
-            float(time0), ptr(mb), ptr(Sb), ptr(cmb), ptr(cvb), ptr(Jb), out["actions_bar"].data_ptr(), ptr(out.get("gains_bar")),
-            ptr(out.get("mu0_bar")), ptr(out.get("S0_bar")), self._stream()))
-        self._keep_rollout_linear_feedback_backward = (actions, gains, mb, Sb, cmb, cvb, Jb)   # alive until the call has read them
-        return out
+        return self._rollout_backward("rollout_linear_feedback_backward", actions, mu0, S0, include_time, time0,
+                                      (mu_bar, Sig_bar, cost_mu_bar, cost_var_bar, J_bar), want_initial, closed_loop=True, gains=gains,
+                                      want_gains=want_gains)
 
     def rollout_linear_feedback_grad(self, actions, gains, mu0, S0, include_time=False, time0=0.0):
         """Objective of the closed-loop linearised rollout and its analytic gradients: dict(J (B,), grad (B,H,A) = dJ/d(actions),

@@ -79,13 +79,19 @@ SIGNATURES = {
     "gpmpc_lbfgs_init": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_lbfgs_step": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
     "gpmpc_lbfgs_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_ilqr_state_size": (C.c_longlong, [_I, _I, _I, _I, _I]),
+    "gpmpc_ilqr_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_ilqr_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
+    "gpmpc_ilqr_init": (C.c_int, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
+    "gpmpc_ilqr_step": (C.c_int, [_P, _P, _I, _I, _I, _I, _D, _I, _D, _D, _D, _D, _P, _P]),
+    "gpmpc_ilqr_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _D, _D, _D, _D, _P, _P, _P, _P]),
     "gpmpc_argmin_async": (C.c_int, [_P, _P, _I, C.c_longlong, _P, _I, _P, _P]),
     "gpmpc_argmin_export": (C.c_int, [_P, _P, _I, C.c_longlong, _P, _I, _P, _P, _P]),
     "gpmpc_argmin": (C.c_int, [_P, _P, _I, C.c_longlong, C.POINTER(_D), C.POINTER(C.c_longlong), _P]),
 }
 
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 
 def load(path=LIB_PATH):

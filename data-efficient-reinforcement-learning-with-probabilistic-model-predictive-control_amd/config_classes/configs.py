@@ -103,13 +103,18 @@ class ControllerConfig:
     loop, wall time of the longest restart) or `"lbfgs_device"` (a box-constrained L-BFGS whose whole loop stays on the
     GPU, gpmpc_lbfgs_search: `lbfgs_candidates` starts in lockstep, one objective + gradient launch and one trial point per
     restart and iteration, `lbfgs_device_iterations` of them with `lbfgs_device_history` curvature pairs; also the one
-    gradient search of the linearised propagation)."""
+    gradient search of the linearised propagation) or `"ilqr_device"` (a clamped iLQR on the mean dynamics of the linearised
+    propagation whose whole loop stays on the GPU, gpmpc_ilqr_search: `ilqr_candidates` starts in lockstep, `ilqr_iterations`
+    iterations of a backward Riccati sweep and a line search over `ilqr_line_search_steps` step sizes, regularisation
+    `ilqr_reg`; certainty-equivalent design, the winner chosen by the LCB objective; linearised propagation, open loop and the
+    normalisation mapper only)."""
 
     def __init__(self, len_horizon=15, actions_optimizer_params=None, init_from_previous_actions=True,
                  restarts_optim=1, optimize=True, num_repeat_actions=1,
                  candidate_optimizer=None, cem_candidates=256, cem_iterations=4, cem_elite_fraction=0.1,
                  lbfgs_candidates=None, shard_over_ranks=False, feedback_gain=None, feedback_lqr_reg=0.0,
-                 lbfgs_device_iterations=30, lbfgs_device_history=10):
+                 lbfgs_device_iterations=30, lbfgs_device_history=10,
+                 ilqr_candidates=None, ilqr_iterations=8, ilqr_reg=1e-3, ilqr_line_search_steps=8):
         self.len_horizon = len_horizon
         self.actions_optimizer_params = dict(_DEFAULT_OPTIMIZER if actions_optimizer_params is None
                                              else actions_optimizer_params)
@@ -125,6 +130,12 @@ class ControllerConfig:
         # "lbfgs_device": evaluations per restart (mirrors maxfun = 30 of the scipy solver) and pairs of the L-BFGS memory
         self.lbfgs_device_iterations = lbfgs_device_iterations
         self.lbfgs_device_history = lbfgs_device_history
+        # "ilqr_device": starts (None: restarts_optim), iterations, the initial (and smallest) regularisation of Huu and the step
+        # sizes 1, 1/2, ... of the line search
+        self.ilqr_candidates = ilqr_candidates
+        self.ilqr_iterations = ilqr_iterations
+        self.ilqr_reg = ilqr_reg
+        self.ilqr_line_search_steps = ilqr_line_search_steps
         # one process per GPU (torch.distributed initialised by the launcher): split the candidates / restarts over the ranks.
         # Opt-in: every rank must then call get_action with the same observation (checked inside the exchange)
         self.shard_over_ranks = shard_over_ranks

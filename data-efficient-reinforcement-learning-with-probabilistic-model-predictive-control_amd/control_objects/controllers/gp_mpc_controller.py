@@ -69,7 +69,7 @@ class GpMpcController(BaseControllerObject):
         self._check_propagation_supported()
 
     LINEARIZED_OPTIMIZERS = ("optimize=False (random shooting), candidate_optimizer='cem' or, in open loop, "
-                             "candidate_optimizer='lbfgs_device'")
+                             "candidate_optimizer='lbfgs_device' or candidate_optimizer='ilqr_device'")
 
     def _check_propagation_supported(self, what=None):
         """ModelConfig.uncertainty_propagation = "linearized" has objective values only (gpmpc_rollout_linear): the searches
@@ -77,7 +77,20 @@ class GpMpcController(BaseControllerObject):
         drives gpmpc_rollout_linear and its backward itself) in open loop; the device-side cross-entropy search, the batched
         L-BFGS and the scipy L-BFGS-B loop need host-side gradient plumbing the linearised path does not have.
         ControllerConfig.feedback_gain (closed-loop planning, gpmpc_rollout_linear_feedback) exists for the linearised
-        propagation only, and not for "lbfgs_device" (its objective is the open-loop one)."""
+        propagation only, and not for "lbfgs_device" (its objective is the open-loop one).  The device-resident iLQR
+        ("ilqr_device": gpmpc_ilqr_search) exists under "linearized" only, in open loop, with the normalisation mapper."""
+        if getattr(self.config.controller, "candidate_optimizer", None) == "ilqr_device" and self.config.controller.optimize:
+            if self.transition_model.propagation() != "linearized":
+                raise ValueError("candidate_optimizer='ilqr_device' needs ModelConfig.uncertainty_propagation='linearized': the "
+                                 "iLQR runs on the mean dynamics of the linearised propagation, moment matching has none")
+            if getattr(self.config.controller, "feedback_gain", None) is not None:
+                raise ValueError("candidate_optimizer='ilqr_device' plans in open loop: it does not support "
+                                 "ControllerConfig.feedback_gain")
+            if isinstance(self.actions_mapper, DerivativeActionMapper):
+                raise ValueError("candidate_optimizer='ilqr_device' optimises the model actions themselves: it needs the "
+                                 "normalisation action mapper, not the DerivativeActionMapper")
+            if what is None:
+                return
         if self.transition_model.propagation() != "linearized":
             if getattr(self.config.controller, "feedback_gain", None) is not None:
                 raise ValueError("ControllerConfig.feedback_gain needs ModelConfig.uncertainty_propagation='linearized': "
@@ -376,6 +389,8 @@ class GpMpcController(BaseControllerObject):
             return self._batched_lbfgs_search(state_mu, state_var)
         if getattr(cc, "candidate_optimizer", None) == "lbfgs_device":
             return self._device_lbfgs_search(state_mu, state_var)
+        if getattr(cc, "candidate_optimizer", None) == "ilqr_device":
+            return self._device_ilqr_search(state_mu, state_var)
         opt_fun, best = np.inf, None
         for idx_restart in range(cc.restarts_optim):
             if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and idx_restart == 0:
@@ -742,6 +757,47 @@ class GpMpcController(BaseControllerObject):
             raise FloatingPointError("no finite objective among the restarts")
         self.num_rollouts += B * iterations
         self.lbfgs_evaluations = iterations
+        self.candidates_final_J, self.candidates_final_status = J_all, status
+        best_i = int(np.flatnonzero(J_all == best_J)[0])          # the first strict minimum: gpmpc_argmin's rule
+        self.best_candidate_index, self.best_candidate_J = best_i, float(best_J)
+        out = self.evaluate_candidates(best_x[None], state_mu, state_var, trajectories=True)
+        self._cache_trajectory(out, 0)
+        self.actions_mpc_previous_iter = best_x.copy()
+        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
+
+    def _device_ilqr_search(self, state_mu, state_var):
+        """candidate_optimizer = "ilqr_device": a clamped iLQR on the mean dynamics of the linearised propagation from
+        `ilqr_candidates` starts whose whole loop stays on the GPU (gpmpc_ilqr_search: per iteration a backward Riccati sweep along
+        each candidate's nominal trajectory, a closed-loop forward pass for every step size of the line search, an accept rule;
+        nothing is read back until the winner).  The design is certainty-equivalent; the winner is chosen by the LCB objective of
+        gpmpc_rollout_linear.  The starts are those `_device_lbfgs_search` draws (same generator order, the shifted previous
+        solution in slot 0).  Two host synchronisations per control step: the winner, then its trajectory for the logging caches.
+        Linearised propagation, open loop and the normalisation mapper only; the starts are not sharded over ranks."""
+        cc = self.config.controller
+        world, _ = self._ranks()
+        if world > 1:                                  # every rank raises here, before any collective
+            raise ValueError("candidate_optimizer='ilqr_device' does not shard its starts over ranks: switch "
+                             "ControllerConfig.shard_over_ranks off (every rank then runs the whole search)")
+        H, A = cc.len_horizon, self.actions_mapper.dim_action
+        B = int(cc.ilqr_candidates or cc.restarts_optim)
+        iterations = int(cc.ilqr_iterations)
+        x0s = []
+        for b in range(B):
+            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and b == 0:
+                x0s.append(generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A))
+            else:
+                x0s.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
+        self.ilqr_device_starts = np.stack(x0s).astype(np.float64).reshape(B, H * A)
+        tm = self.transition_model
+        tm.set_cost(self.config.reward)
+        best_x, best_J, J_all, status = tm.engine.ilqr_search_host(
+            self.ilqr_device_starts, np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), H, A,
+            iterations, line_search_steps=int(cc.ilqr_line_search_steps), reg0=float(cc.ilqr_reg),
+            include_time=tm.config.include_time_model, time0=float(self.iter_ctrl))
+        if not np.isfinite(best_J):
+            raise FloatingPointError("no finite objective among the starts")
+        self.num_rollouts += B * iterations * (1 + int(cc.ilqr_line_search_steps))
+        self.ilqr_iterations_run = iterations
         self.candidates_final_J, self.candidates_final_status = J_all, status
         best_i = int(np.flatnonzero(J_all == best_J)[0])          # the first strict minimum: gpmpc_argmin's rule
         self.best_candidate_index, self.best_candidate_J = best_i, float(best_J)

@@ -8,6 +8,7 @@
 #include "gpmpc_internal.h"
 #include "lqr_gains_plan.h"
 #include "lbfgs_state.h"
+#include "ilqr_state.h"
 
 // ROCTx ranges around the entry points (tracing row): visible in `rocprofv3 --marker-trace` timelines
 // as gpmpc_prepare / gpmpc_rollout / gpmpc_rollout_grad / gpmpc_argmin.  The marker library is looked up at first use
@@ -90,6 +91,7 @@ const Option kOptions[] = {
     {"moments_linear_backward_chunk_points", &Handle::opt_moments_linear_bwd_chunk, 0, kChunkMax, 1,
      "moments_linear_backward_chunk_points: 0 (auto) or a number of points"},
     {"lqr_gains_chunk_points", &Handle::opt_lqr_gains_chunk, 0, kChunkMax, 1, "lqr_gains_chunk_points: 0 (auto) or a number of candidates"},
+    {"ilqr_chunk_points", &Handle::opt_ilqr_chunk, 0, kChunkMax, 1, "ilqr_chunk_points: 0 (auto) or a number of candidates"},
     {"sparse_chunk_points", &Handle::opt_sparse_chunk, 0, kChunkMax, 64, "sparse_chunk_points: 0 (auto) or a multiple of 64"},
     {"select_inducing_max_mb", nullptr, 1, LLONG_MAX, 1, "select_inducing_max_mb: a number of MiB >= 1", &Handle::opt_select_max_mb},
     {"incremental", &Handle::opt_incremental},
@@ -147,7 +149,7 @@ static int query_entry(gpmpc_t* g, const char* name, const char* count_name, int
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 25; }
+int gpmpc_abi_version(void) { return 26; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -175,7 +177,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -760,6 +762,90 @@ int gpmpc_lbfgs_search(gpmpc_t* g, const double* mu0, const double* S0, int B, i
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_lbfgs_search(h, a, propagation, first_iteration, iterations, history, c1, pgtol, mp, x0_dev, state_dev, best_out_dev,
                             (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Device-resident iLQR (ilqr.hip).  The one argument-check body of the five entries that take a handle: each names what it needs
+// (`ptrs_ok`: its own required pointers; `params`: reg0 / reg_factor / reg_max / tol are its arguments; iterations: 1 where it has none).
+struct IlqrParams { double reg0, reg_factor, reg_max, tol; };
+static int ilqr_entry_checks(gpmpc_t* g, bool ptrs_ok, int B, int H, int A, int include_time, int L, int iterations,
+                             const double* reg0, const IlqrParams* params) {
+    if (!g) return GPMPC_ERR_ARG;
+    Handle* h = H_(g);
+    if (!h->ready) return bad(g, "ilqr before prepare / set_factors");
+    if (!ptrs_ok) return bad(g, "null argument");
+    bool limit = false;
+    if (const char* msg = ilqr_check_shape(B, H, A, L, limit)) {
+        h->err = msg;
+        return limit ? GPMPC_ERR_LIMIT : GPMPC_ERR_ARG;
+    }
+    if (h->D + A + (include_time ? 1 : 0) != h->E) return bad(g, "D + A (+1 with time) must equal the model's input dim E");
+    if (iterations < 1) return bad(g, "ilqr: need iterations >= 1");
+    if (reg0)
+        if (const char* msg = ilqr_check_reg0(*reg0)) return bad(g, msg);
+    if (params)
+        if (const char* msg = ilqr_check_step(params->reg0, params->reg_factor, params->reg_max, params->tol)) return bad(g, msg);
+    if (h->cost_D != h->D || h->cost_A != A) return bad(g, "gpmpc_set_cost not called for this (D, A)");
+    GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
+    return GPMPC_OK;
+}
+
+long long gpmpc_ilqr_state_size(int B, int H, int A, int D, int L) {
+    bool limit = false;
+    if (ilqr_check_shape(B, H, A, L, limit) || D < 1 || D > kMaxD) return -1;
+    return (long long)make_ilqr_layout(B, H, A, D, L).total;
+}
+
+int gpmpc_ilqr_backward(gpmpc_t* g, const double* actions, const double* mu0, int B, int H, int A, int include_time, double time0,
+                        const double* reg_dev, double* gains_out, double* ff_out, double* mu_out, double* info_out, void* stream) {
+    Range roctx_range("gpmpc_ilqr_backward");
+    int rc = ilqr_entry_checks(g, actions && mu0 && reg_dev && gains_out && ff_out && mu_out && info_out, B, H, A, include_time, 1, 1,
+                               nullptr, nullptr);
+    if (rc) return rc;
+    return run_ilqr_backward(H_(g), actions, mu0, B, H, A, include_time, time0, reg_dev, gains_out, ff_out, mu_out, info_out,
+                             (hipStream_t)stream);
+}
+
+int gpmpc_ilqr_forward(gpmpc_t* g, const double* actions, const double* gains, const double* ff, const double* mu_nom,
+                       const double* mu0, int B, int H, int A, int include_time, double time0, const double* alphas, int L,
+                       double* trial_actions_out, double* trial_cost_out, double* trial_mu_out, void* stream) {
+    Range roctx_range("gpmpc_ilqr_forward");
+    int rc = ilqr_entry_checks(g, actions && gains && ff && mu_nom && mu0 && alphas && trial_actions_out && trial_cost_out, B, H, A,
+                               include_time, L, 1, nullptr, nullptr);
+    if (rc) return rc;
+    return run_ilqr_forward(H_(g), actions, gains, ff, mu_nom, mu0, B, H, A, include_time, time0, alphas, L, trial_actions_out,
+                            trial_cost_out, trial_mu_out, (hipStream_t)stream);
+}
+
+int gpmpc_ilqr_init(gpmpc_t* g, const double* x0_dev, int B, int H, int A, int L, double reg0, double* state_dev, void* stream) {
+    Range roctx_range("gpmpc_ilqr_init");
+    int rc = ilqr_entry_checks(g, x0_dev && state_dev, B, H, A, g && H_(g)->E - H_(g)->D - A == 1, L, 1, &reg0, nullptr);
+    if (rc) return rc;
+    return run_ilqr_init(H_(g), x0_dev, B, H, A, L, reg0, state_dev, (hipStream_t)stream);
+}
+
+int gpmpc_ilqr_step(gpmpc_t* g, const double* mu0, int B, int H, int A, int include_time, double time0, int L, double reg0,
+                    double reg_factor, double reg_max, double tol, double* state_dev, void* stream) {
+    Range roctx_range("gpmpc_ilqr_step");
+    const IlqrParams pr{reg0, reg_factor, reg_max, tol};
+    int rc = ilqr_entry_checks(g, mu0 && state_dev, B, H, A, include_time, L, 1, nullptr, &pr);
+    if (rc) return rc;
+    return run_ilqr_step(H_(g), mu0, B, H, A, include_time, time0, L, reg0, reg_factor, reg_max, tol, state_dev, (hipStream_t)stream);
+}
+
+int gpmpc_ilqr_search(gpmpc_t* g, const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
+                      int iterations, int L, double reg0, double reg_factor, double reg_max, double tol, const double* x0_dev,
+                      double* state_dev, double* best_out_dev, void* stream) {
+    Range roctx_range("gpmpc_ilqr_search");
+    const IlqrParams pr{reg0, reg_factor, reg_max, tol};
+    int rc = ilqr_entry_checks(g, mu0 && S0 && x0_dev && state_dev, B, H, A, include_time, L, iterations, nullptr, &pr);
+    if (rc) return rc;
+    // fill_args wants an actions pointer; the search points it at the state's actions afterwards
+    RolloutArgs a;
+    rc = fill_args(g, a, state_dev, mu0, S0, B, H, A, include_time, time0);
+    if (rc) return rc;
+    return run_ilqr_search(H_(g), a, iterations, L, reg0, reg_factor, reg_max, tol, x0_dev, state_dev, best_out_dev,
+                           (hipStream_t)stream);
 }
 
 int gpmpc_rollout_timed(gpmpc_t* g, const double* actions, const double* mu0, const double* S0, int B, int H, int A,

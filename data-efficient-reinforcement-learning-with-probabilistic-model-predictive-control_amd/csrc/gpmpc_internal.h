@@ -214,6 +214,7 @@ struct Handle {
     Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward / gpmpc_rollout_linear_feedback_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
     Buf lqrws;    // gpmpc_lqr_gains: model inputs | M of the step at hand | every step's V of one chunk of candidates
     Buf lbfgsws;  // gpmpc_lbfgs_search: J (B) | dJ/d(model actions) (B, H, A) | ones (B), the J_bar of the linearised gradient
+    Buf ilqrws;   // gpmpc_ilqr_*: model inputs | M of the step at hand | every step's V of the nominal | trial trajectories of one chunk of candidates (ilqr_plan.h)
     struct SepTable* septab = nullptr;   // monomial bands of the separable evaluation (point_pass_kernel.h), device copy
     Buf sepw;                            // their weights 1 / alpha!
     int septab_D = -1, sep_ks = 0, sep_cmax = 0;
@@ -313,6 +314,7 @@ struct Handle {
     int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_moments_linear_bwd_chunk = 0;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: the same for their chunks
     int opt_lqr_gains_chunk = 0;     // gpmpc_lqr_gains: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
+    int opt_ilqr_chunk = 0;          // gpmpc_ilqr_*: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int lds_limit = 160 * 1024;
     int num_cu = 256;
     Buf sprec;    // gpmpc_sparse_append / gpmpc_sparse_forget: the record of the last gpmpc_prepare_sparse (Yb | w | noises; sparse_update_plan.h)
@@ -591,6 +593,21 @@ int run_lbfgs_step(Handle* h, const double* J_dev, const double* grad_model_dev,
 int run_lbfgs_search(Handle* h, RolloutArgs& a, int propagation, int first_iteration, int iterations, int history, double c1,
                      double pgtol, const LbfgsMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
                      hipStream_t s);
+// ilqr.hip: clamped iLQR on the mean dynamics of the linearised propagation, B candidates in lockstep (ilqr_state.h: the state buffer
+// and the argument checks; validated by the entry points).  backward: gains (B, H, A, D), feed-forward (B, H, A), nominal trajectory
+// (B, H + 1, D) and info (B, 5) = [cost | dV | step | flags | 0] at `actions` with the per-candidate reg_dev (B); forward: the trial
+// actions (B, L, H, A), costs (B, L) and, where wanted, trajectories (B, L, H + 1, D) of the L step sizes alphas_host
+int run_ilqr_backward(Handle* h, const double* actions, const double* mu0_host, int B, int H, int A, int include_time, double time0,
+                      const double* reg_dev, double* gains_out, double* ff_out, double* mu_out, double* info_out, hipStream_t s);
+int run_ilqr_forward(Handle* h, const double* actions, const double* gains, const double* ff, const double* mu_nom,
+                     const double* mu0_host, int B, int H, int A, int include_time, double time0, const double* alphas_host, int L,
+                     double* trial_actions_out, double* trial_cost_out, double* trial_mu_out, hipStream_t s);
+int run_ilqr_init(Handle* h, const double* x0_dev, int B, int H, int A, int L, double reg0, double* state_dev, hipStream_t s);
+int run_ilqr_step(Handle* h, const double* mu0_host, int B, int H, int A, int include_time, double time0, int L, double reg0,
+                  double reg_factor, double reg_max, double tol, double* state_dev, hipStream_t s);
+// ... `a` as fill_args leaves it (actions / J_out are set inside); best_out_dev [J | restart | actions (H A)] or NULL
+int run_ilqr_search(Handle* h, RolloutArgs& a, int iterations, int L, double reg0, double reg_factor, double reg_max, double tol,
+                    const double* x0_dev, double* state_dev, double* best_out_dev, hipStream_t s);
 // prepare_small.hip: the single-launch paths of a plan (PreparePath::small_whole / small_cholesky)
 int launch_prepare_small(Handle* h, const PreparePlan& pp, const double* X, const double* Y, const double* ls, const double* os,
                          const double* noise, int N, int D, int E, hipStream_t s);

@@ -846,6 +846,116 @@ class HipEngine:
         host = out.cpu().numpy()                                # the one synchronisation
         return host[2:2 + n].copy(), float(host[0]), host[2 + n:2 + n + B].copy(), host[2 + n + B:].astype(np.int64)
 
+    # -- device-resident iLQR (gpmpc_ilqr_*) --------------------------------------------------------
+    def ilqr_backward(self, actions, mu0, reg, include_time=False, time0=0.0):
+        """gpmpc_ilqr_backward at `actions` (B, H, A) with the regularisation `reg` (a scalar or (B,)): dict of device tensors
+        `gains` (B, H, A, D), `ff` (B, H, A), `mu` (B, H + 1, D), `info` (B, 5) = [cost | dV | step | flags | 0] and its columns
+        `cost`, `dV`, `step`, `flags` as views.  Certainty-equivalent cost (needs set_cost).  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        reg = torch.as_tensor(reg, dtype=torch.float64).to(self.device)
+        reg = reg.expand(B).contiguous() if reg.dim() == 0 else self._dev(reg, (B,))
+        new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=self.device)       # noqa: E731
+        out = {"gains": new(B, H, A, D), "ff": new(B, H, A), "mu": new(B, H + 1, D), "info": new(B, 5)}
+        self._check(self.lib.gpmpc_ilqr_backward(self._h, actions.data_ptr(), _hp(mu0), B, H, A, int(bool(include_time)),
+                                                 float(time0), reg.data_ptr(), out["gains"].data_ptr(), out["ff"].data_ptr(),
+                                                 out["mu"].data_ptr(), out["info"].data_ptr(), self._stream()))
+        for i, k in enumerate(("cost", "dV", "step", "flags")):
+            out[k] = out["info"][:, i]
+        self._keep_ilqr = (actions, reg)
+        return out
+
+    def ilqr_forward(self, actions, gains, ff, mu_nom, mu0, alphas, include_time=False, time0=0.0, trajectories=True):
+        """gpmpc_ilqr_forward: the closed-loop forward pass on the mean for the step sizes `alphas` (L,): dict of device tensors
+        `trial_actions` (B, L, H, A), `trial_cost` (B, L) and, with `trajectories`, `trial_mu` (B, L, H + 1, D).  Asynchronous."""
+        actions = self._dev(actions)
+        B, H, A = actions.shape
+        D = self.D
+        gains, ff, mu_nom = self._dev(gains, (B, H, A, D)), self._dev(ff, (B, H, A)), self._dev(mu_nom, (B, H + 1, D))
+        mu0 = _host(mu0, (D,))
+        alphas = _host(alphas)
+        L_ = int(alphas.size)
+        new = lambda *sh: torch.empty(sh, dtype=torch.float64, device=self.device)       # noqa: E731
+        out = {"trial_actions": new(B, L_, H, A), "trial_cost": new(B, L_)}
+        if trajectories:
+            out["trial_mu"] = new(B, L_, H + 1, D)
+        self._check(self.lib.gpmpc_ilqr_forward(self._h, actions.data_ptr(), gains.data_ptr(), ff.data_ptr(), mu_nom.data_ptr(),
+                                                _hp(mu0), B, H, A, int(bool(include_time)), float(time0), _hp(alphas), L_,
+                                                out["trial_actions"].data_ptr(), out["trial_cost"].data_ptr(),
+                                                _ptr(out.get("trial_mu")), self._stream()))
+        self._keep_ilqr = (actions, gains, ff, mu_nom)
+        return out
+
+    def ilqr_state(self, B, H, A, L):
+        """The caller-owned state of the device iLQR for B candidates and L line-search steps: dict of named views (actions
+        (B, H, A); cost, reg, status, accepts, chosen, dV, step, flags, J (B); trial_cost (B, L); gains (B, H, A, D); ff (B, H, A);
+        mu (B, H + 1, D); trial_actions (B, L, H, A)) into ONE device buffer (`buffer`), laid out as include/gpmpc.h documents."""
+        B, H, A, L_, D = int(B), int(H), int(A), int(L), int(self.D)
+        size = int(self.lib.gpmpc_ilqr_state_size(B, H, A, D, L_))
+        if size < 0:
+            raise ValueError("ilqr_state: need 1 <= B <= 4096, H >= 1, 1 <= A <= 8, 1 <= L <= 16 and a prepared model")
+        buf = torch.zeros(size, dtype=torch.float64, device=self.device)
+        st, off = {"buffer": buf, "B": B, "H": H, "A": A, "L": L_}, 0
+        for k, sh in (("actions", (B, H, A)), ("cost", (B,)), ("reg", (B,)), ("status", (B,)), ("accepts", (B,)), ("chosen", (B,)),
+                      ("dV", (B,)), ("step", (B,)), ("flags", (B,)), ("J", (B,)), ("trial_cost", (B, L_)), ("gains", (B, H, A, D)),
+                      ("ff", (B, H, A)), ("mu", (B, H + 1, D)), ("trial_actions", (B, L_, H, A))):
+            cnt = int(np.prod(sh))
+            st[k] = buf[off:off + cnt].view(sh)
+            off += cnt
+        assert off == size
+        return st
+
+    def ilqr_init(self, state, x0, reg0=1e-3):
+        """gpmpc_ilqr_init: actions = clip(x0 (B, H, A)), reg = reg0, chosen = -1, everything else 0.  No synchronisation."""
+        B, H, A, L_ = state["B"], state["H"], state["A"], state["L"]
+        x0 = self._dev(x0).reshape(B, H, A)
+        self._check(self.lib.gpmpc_ilqr_init(self._h, x0.data_ptr(), B, H, A, L_, float(reg0), state["buffer"].data_ptr(),
+                                             self._stream()))
+        self._keep_ilqr = (x0, state["buffer"])
+
+    def ilqr_step(self, state, mu0, reg0=1e-3, reg_factor=10.0, reg_max=1e6, tol=1e-9, include_time=False, time0=0.0):
+        """gpmpc_ilqr_step: one iteration (backward, line search over alpha = 2^-l, accept rule) on the state.  No synchronisation."""
+        B, H, A, L_ = state["B"], state["H"], state["A"], state["L"]
+        mu0 = _host(mu0, (self.D,))
+        self._check(self.lib.gpmpc_ilqr_step(self._h, _hp(mu0), B, H, A, int(bool(include_time)), float(time0), L_, float(reg0),
+                                             float(reg_factor), float(reg_max), float(tol), state["buffer"].data_ptr(),
+                                             self._stream()))
+
+    def ilqr_search(self, state, mu0, S0, iterations, x0, reg0=1e-3, reg_factor=10.0, reg_max=1e6, tol=1e-9, include_time=False,
+                    time0=0.0, best_out=None):
+        """gpmpc_ilqr_search: init from x0 (B, H, A), `iterations` steps, the LCB objective J of the final sequences
+        (gpmpc_rollout_linear) into the state's J.  Returns the device record [best J | candidate | its actions (H*A)] (`best_out`,
+        or a new tensor).  No synchronisation."""
+        B, H, A, L_ = state["B"], state["H"], state["A"], state["L"]
+        D = self.D
+        mu0 = _host(mu0, (D,))
+        S0 = _host(S0, (D, D))
+        x0 = self._dev(x0).reshape(B, H, A)
+        if best_out is None:
+            best_out = torch.empty(2 + H * A, dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_ilqr_search(self._h, _hp(mu0), _hp(S0), B, H, A, int(bool(include_time)), float(time0),
+                                               int(iterations), L_, float(reg0), float(reg_factor), float(reg_max), float(tol),
+                                               x0.data_ptr(), state["buffer"].data_ptr(), best_out.data_ptr(), self._stream()))
+        self._keep_ilqr = (x0, state["buffer"], best_out)
+        return best_out
+
+    def ilqr_search_host(self, x0, mu0, S0, H, A, iterations, line_search_steps=8, reg0=1e-3, reg_factor=10.0, reg_max=1e6,
+                         tol=1e-9, include_time=False, time0=0.0):
+        """The device iLQR from the starts x0 (B, H*A) -> (best actions (H*A,), best J, per-candidate J (B,), per-candidate status
+        (B,)) as numpy, with ONE host synchronisation (a single copy of the winner record and the per-candidate values)."""
+        x0 = np.asarray(x0, dtype=np.float64)
+        B, n = x0.shape[0], H * A
+        st = self.ilqr_state(B, H, A, line_search_steps)
+        out = torch.empty(2 + n + 2 * B, dtype=torch.float64, device=self.device)
+        self.ilqr_search(st, mu0, S0, iterations, x0.reshape(B, H, A), reg0=reg0, reg_factor=reg_factor, reg_max=reg_max, tol=tol,
+                         include_time=include_time, time0=time0, best_out=out[:2 + n])
+        out[2 + n:2 + n + B].copy_(st["J"])
+        out[2 + n + B:].copy_(st["status"])
+        host = out.cpu().numpy()                                # the one synchronisation
+        return host[2:2 + n].copy(), float(host[0]), host[2 + n:2 + n + B].copy(), host[2 + n + B:].astype(np.int64)
+
     # -- a8 ----------------------------------------------------------------------------
     # sharding.select_best_async looks for this attribute: argmin_async can deliver the record to pinned host memory itself
     argmin_exports_host = True

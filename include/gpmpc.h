@@ -396,6 +396,7 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
  * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
+ * "ilqr_chunk_points" (candidates of gpmpc_ilqr_* per internal chunk: 0 auto),
  * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64),
  * "select_inducing_max_mb" (cap on the workspace of gpmpc_select_inducing in MiB, >= 1; 4096 unless set).
  * Measurement (A/B) switches of single
@@ -748,6 +749,78 @@ int gpmpc_lbfgs_search(gpmpc_t* h, const double* mu0_host, const double* S0_host
                        int propagation, int first_iteration, int iterations, int history, double c1, double pgtol, int mapper,
                        const double* max_change_host, const double* action_prev_host, const double* x0_dev, double* state_dev,
                        double* best_out_dev, void* stream);
+
+/*
+ * Second-order candidate optimisation whose loop stays on the device: a clamped iLQR on the MEAN dynamics of the linearised
+ * propagation, for B candidates in lockstep -- the trajectory optimiser beside gpmpc_cem_search and gpmpc_lbfgs_search.  Per
+ * candidate, with ubar (H,A) in [0,1]:
+ *   dynamics  x_{t+1} = x_t + M([x_t | u_t | time0 + t]), x_0 = mu0 (M: the posterior mean of gpmpc_moments_linear);
+ *   cost      W_s = (W + W^T) / 2 = (Q | N ; N^T | R), P_H = (W_T + W_T^T) / 2, e_t = [x_t | u_t] - target, e_H = x_H - target[:D],
+ *             c = (sum_{t<H} e_t^T W_s e_t + e_H^T P_H e_H) / (H + 1)    on the block loaded by gpmpc_set_cost for this (D, A).
+ * The design is CERTAINTY-EQUIVALENT: kappa, the variance terms of the LCB, clipping of the cost and the state constraints do NOT
+ * enter.  It is CLAMPED iLQR: the box [0,1] is honoured by clipping the realised action of the forward pass, not by a box QP in
+ * the sweep.
+ *
+ * gpmpc_ilqr_backward: at actions_dev (B,H,A) with the per-candidate regularisation reg_dev (B, a DEVICE array: the loop never
+ * reads it back).  A_t, B_t, F, Huu (+ reg I), Hux, the Cholesky factorisation, K_t and P_t are exactly gpmpc_lqr_gains's; beside
+ * them, for t = H-1 .. 0,
+ *   p_H = P_H e_H,   q = W_s e_t = [q_x ; q_u],   g_x = q_x + A_t^T p_{t+1},   g_u = q_u + B_t^T p_{t+1},
+ *   k_t = -Huu^-1 g_u (the same factor as K_t),   p_t = g_x + Hux^T k_t,
+ *   dV = sum_t g_u^T k_t / (H + 1)  (<= 0; the model predicts a change of (2 alpha - alpha^2) dV for the step size alpha),
+ *   step = max_{t,a} |clip(ubar_t + k_t, 0, 1) - ubar_t|.
+ * A lost pivot (<= 0 or not finite) is handled as in gpmpc_lqr_gains: the step gets K_t = 0, k_t = 0, p_t = g_x, and the
+ * candidate's flag counts it.  Outputs (all required): gains_out_dev (B,H,A,D), ff_out_dev (B,H,A) = k_t, mu_out_dev (B,H+1,D) the
+ * nominal trajectory, info_out_dev (B,5) = [cost | dV | step | flags | reserved 0] (flags a whole number stored as a double).
+ * mu_out is gpmpc_rollout_linear's mu bit for bit; the gains are gpmpc_lqr_gains's bit for bit for the same reg.
+ *
+ * gpmpc_ilqr_forward: for the L step sizes alphas_host, x_0 = mu0, u_t = clip(ubar_t + alpha k_t + K_t (x_t - xbar_t), 0, 1),
+ * x_{t+1} = x_t + M(.): trial_actions_out_dev (B,L,H,A) (the clipped actions), trial_cost_out_dev (B,L) = c(alpha), and
+ * trial_mu_out_dev (B,L,H+1,D) or NULL.  All B L rows run in the same launches.  With nominal actions in the box and finite gains,
+ * alpha = 0 returns the nominal actions, the nominal mu and gpmpc_ilqr_backward's cost bit for bit, whatever the gains are: the
+ * nominal and every trial cost come from one kernel, so equal trajectories get equal bits.
+ *
+ * state_dev is the CALLER's buffer of gpmpc_ilqr_state_size(B, H, A, D, L) doubles (< 0: bad arguments):
+ *   actions (B,H,A) | cost (B) | reg (B) | status (B) | accepts (B) | chosen (B) | dV (B) | step (B) | flags (B) | J (B)
+ *   | trial_cost (B,L) | gains (B,H,A,D) | ff (B,H,A) | mu (B,H+1,D) | trial_actions (B,L,H,A)
+ * Whole numbers are stored as doubles.  status: 0 running, 1 converged (step <= tol: in the interior, or resting on the box with
+ * the feed-forward pointing outward), 2 regularisation above reg_max, 3 non-finite cost.
+ *
+ * gpmpc_ilqr_init: actions = clip(x0_dev (B,H,A)), reg = reg0, chosen = -1, everything else 0.  gpmpc_ilqr_step: one iteration.
+ * Candidates whose status != 0 are still evaluated (lockstep) and their state no longer changes.  In order:
+ *   1. backward at the state's actions with the candidate's reg: gains, ff, mu, cost, dV, step, flags;
+ *   2. cost not finite: status 3;   3. else step <= tol: status 1;
+ *   4. forward for the ladder alpha_l = 2^-l, l = 0 .. L-1: trial_actions, trial_cost;
+ *   5. l* = the finite trial of lowest cost, ties to the smallest l; accept iff trial_cost[l*] < cost (strict):
+ *        accept: actions <- trial_actions[l*], cost <- trial_cost[l*], reg <- max(reg / reg_factor, reg0), accepts += 1, chosen = l*;
+ *        else:   chosen = -1, reg <- reg reg_factor, and status 2 once reg > reg_max.
+ * cost never increases.  gpmpc_ilqr_search: init from x0_dev, `iterations` steps, then one gpmpc_rollout_linear launch sequence
+ * over the B final sequences with mu0, S0 (J only) into the state's J -- the library's LCB objective, so the winner composes with
+ * the other optimisers -- and the winner by gpmpc_argmin's rule to best_out_dev (2 + H A) = [J | restart | actions] (may be NULL).
+ * gpmpc_ilqr_search(iterations = k) leaves the state of gpmpc_ilqr_init plus k gpmpc_ilqr_step calls (J aside).
+ *
+ * All entries are asynchronous on `stream`: no host synchronisation, no read-back, a launch sequence fixed by the arguments; host
+ * arrays are read before the call returns.  Plain kernels: no atomics, no waits between workgroups; every sum runs in an order
+ * fixed by N, E, D, A, H and L alone -- a candidate's results are bitwise the same alone, at any place of any batch and whatever
+ * "ilqr_chunk_points" / "moments_linear_chunk_points" are.  Workspace of its own (a chunk's model inputs, M, the nominal V of all
+ * H steps and the trial trajectories), within 16 MB or one chunk's need, beside those of gpmpc_moments_linear /
+ * gpmpc_rollout_linear; no gpmpc_last_* state is touched.
+ * GPMPC_ERR_ARG: no cached model, a NULL required pointer, B < 1 or B > 4096, H < 1, A < 1, D + A (+1) != E, L < 1 or L > 16,
+ * iterations < 1, reg0 not finite or < 0, reg_factor not > 1, reg_max < reg0, tol < 0, no gpmpc_set_cost for this (D, A).
+ * GPMPC_ERR_LIMIT: A > 8.  Every such error is reported before anything is enqueued or written.
+ */
+long long gpmpc_ilqr_state_size(int B, int H, int A, int D, int L);
+int gpmpc_ilqr_backward(gpmpc_t* h, const double* actions_dev, const double* mu0_host, int B, int H, int A, int include_time,
+                        double time0, const double* reg_dev, double* gains_out_dev, double* ff_out_dev, double* mu_out_dev,
+                        double* info_out_dev, void* stream);
+int gpmpc_ilqr_forward(gpmpc_t* h, const double* actions_dev, const double* gains_dev, const double* ff_dev, const double* mu_nom_dev,
+                       const double* mu0_host, int B, int H, int A, int include_time, double time0, const double* alphas_host, int L,
+                       double* trial_actions_out_dev, double* trial_cost_out_dev, double* trial_mu_out_dev, void* stream);
+int gpmpc_ilqr_init(gpmpc_t* h, const double* x0_dev, int B, int H, int A, int L, double reg0, double* state_dev, void* stream);
+int gpmpc_ilqr_step(gpmpc_t* h, const double* mu0_host, int B, int H, int A, int include_time, double time0, int L, double reg0,
+                    double reg_factor, double reg_max, double tol, double* state_dev, void* stream);
+int gpmpc_ilqr_search(gpmpc_t* h, const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time, double time0,
+                      int iterations, int L, double reg0, double reg_factor, double reg_max, double tol, const double* x0_dev,
+                      double* state_dev, double* best_out_dev, void* stream);
 
 /* bench.py: `reps` rollouts back to back bracketed by HIP events recorded on `stream`; average ms per launch in *ms_host. */
 int gpmpc_rollout_timed(gpmpc_t* h, const double* actions_dev, const double* mu0_host, const double* S0_host, int B, int H, int A,

@@ -79,6 +79,8 @@ SIGNATURES = {
     "gpmpc_lbfgs_init": (C.c_int, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "gpmpc_lbfgs_step": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P]),
     "gpmpc_lbfgs_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_mll_batch": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "gpmpc_train_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P]),
     "gpmpc_ilqr_state_size": (C.c_longlong, [_I, _I, _I, _I, _I]),
     "gpmpc_ilqr_backward": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_ilqr_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
@@ -91,7 +93,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 def load(path=LIB_PATH):

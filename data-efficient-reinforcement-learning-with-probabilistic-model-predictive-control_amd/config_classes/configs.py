@@ -76,7 +76,7 @@ class MemoryConfig:
 
 class TrainingConfig:
     def __init__(self, lr_train=7e-3, iter_train=15, training_frequency=25, clip_grad_value=1e-3, print_train=False,
-                 step_print_train=5, device="auto"):
+                 step_print_train=5, device="auto", optimizer="lbfgs", restarts=16, device_iterations=30, device_history=10):
         self.lr_train = lr_train
         self.iter_train = iter_train
         self.training_frequency = training_frequency
@@ -89,6 +89,20 @@ class TrainingConfig:
         if device not in ("auto", "hip"):
             raise ValueError(f"TrainingConfig.device={device!r}: the training loss runs on the GPU only ('auto' or 'hip')")
         self.device = device
+        # how the hyper-parameters are searched: "lbfgs" = the reference's loop (one random restart per GP, torch LBFGS on the
+        # host, every loss a gpmpc_mll call); "lbfgs_device" = `restarts` starts per GP in lockstep on the GPU
+        # (gpmpc_train_search: `device_iterations` iterations of one trial point each, `device_history` curvature pairs), for
+        # memories of up to 256 points -- larger ones take the "lbfgs" loop
+        if optimizer not in ("lbfgs", "lbfgs_device"):
+            raise ValueError(f"TrainingConfig.optimizer={optimizer!r}: 'lbfgs' or 'lbfgs_device'")
+        for name, value, top in (("restarts", restarts, 4096), ("device_iterations", device_iterations, None),
+                                 ("device_history", device_history, 32)):
+            if isinstance(value, bool) or not isinstance(value, int) or value < 1 or (top is not None and value > top):
+                raise ValueError(f"TrainingConfig.{name}={value!r}: an integer >= 1" + (f" and <= {top}" if top else ""))
+        self.optimizer = optimizer
+        self.restarts = restarts
+        self.device_iterations = device_iterations
+        self.device_history = device_history
 
 
 _DEFAULT_OPTIMIZER = {"disp": None, "maxcor": 30, "ftol": 1e-99, "gtol": 1e-99, "eps": 1e-2, "maxfun": 30,

@@ -274,7 +274,10 @@ class GpMpcController(BaseControllerObject):
         self.p_train = self.ctx.Process(target=GpStateTransitionModel.train,
                                         args=(self.queue_train, saved_state, tc.lr_train, tc.iter_train,
                                               tc.clip_grad_value, tc.print_train, tc.step_print_train,
-                                              getattr(tc, "device", "auto")))
+                                              getattr(tc, "device", "auto")),
+                                        kwargs=dict(optimizer=getattr(tc, "optimizer", "lbfgs"), restarts=getattr(tc, "restarts", 16),
+                                                    device_iterations=getattr(tc, "device_iterations", 30),
+                                                    device_history=getattr(tc, "device_history", 10)))
         self.p_train.start()
 
     def check_and_close_processes(self):

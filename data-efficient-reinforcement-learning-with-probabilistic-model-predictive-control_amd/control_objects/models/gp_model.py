@@ -237,6 +237,9 @@ class TrainingFailed(list):
         return (TrainingFailed, (list(self), self.reason))
 
 
+_DEVICE_SEARCH_MAX_N = 256          # memory points one workgroup of gpmpc_mll_batch holds
+
+
 class _LockstepMll:
     """Rendezvous of the per-GP optimiser threads of `train`: a thread asks for the loss of its GP and waits; when every
     unfinished GP is waiting, the last one to arrive evaluates ALL pending GPs with one gpmpc_mll call (the kernels
@@ -710,8 +713,40 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         self.prepare_inference(_t(saved_state.inputs), _t(saved_state.states_change))
 
     @staticmethod
+    def _device_search(engine, X, Y, lo, hi, start, incoming, restarts, iterations, history):
+        """The "lbfgs_device" search of `train`: the list of parameter dicts from one train_search_host call."""
+        n_gp, E = len(start), X.shape[1]
+        n = E + 2
+        K0, K1, K2 = GpHyperParameters.KEYS
+
+        def rows(parts):
+            return np.stack([np.concatenate([np.broadcast_to(np.asarray(p["ls"], dtype=np.float64).reshape(-1), (E,)),
+                                             np.asarray(p["os"], dtype=np.float64).reshape(1),
+                                             np.asarray(p["nz"], dtype=np.float64).reshape(1)]) for p in parts])
+        lo_b, hi_b = rows(lo), rows(hi)
+        theta_in = np.clip(rows(start), lo_b, hi_b)
+        log_scale = bool(np.all(lo_b > 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x_in = np.log(theta_in / lo_b) / np.log(hi_b / lo_b) if log_scale else (theta_in - lo_b) / (hi_b - lo_b)
+        x0 = np.empty((restarts, n_gp, n))
+        x0[0] = np.clip(np.where(np.isfinite(x_in), x_in, 0.0), 0.0, 1.0)
+        if restarts > 1:
+            x0[1:] = torch.rand((restarts - 1, n_gp, n), dtype=F64).numpy()
+        res = engine.train_search_host(torch.as_tensor(X, dtype=F64), torch.as_tensor(Y, dtype=F64), x0, lo_b, hi_b, iterations,
+                                       history=history, log_scale=log_scale)
+        out = []
+        for a in range(n_gp):
+            if int(res["restart"][a]) < 0:             # every start of this GP had a non-finite loss: the incoming parameters stay
+                th = [incoming[a][K0], incoming[a][K1], incoming[a][K2]]
+            else:
+                th = [res["theta"][a, :E], res["theta"][a, E], res["theta"][a, E + 1]]
+            out.append({K0: np.array(th[0], dtype=np.float64).reshape(1, E), K1: np.array(th[1], dtype=np.float64).reshape(()),
+                        K2: np.array(th[2], dtype=np.float64).reshape(1)})
+        return out
+
+    @staticmethod
     def train(queue, saved_state, lr_train, num_iter_train, clip_grad_value, print_train=False, step_print_train=25,
-              device="auto", loss_evaluator=None):
+              device="auto", loss_evaluator=None, optimizer="lbfgs", restarts=16, device_iterations=30, device_history=10):
         """Exact-MLL hyper-parameter search (reference :193-306): per GP a random restart inside the constraint box
         (drawn in the reference's order: outputscale, lengthscale, noise; GP after GP), LBFGS(strong_wolfe), keep the
         best, never return something worse than the incoming parameters.  Runs in the spawned training process, fp64.
@@ -723,6 +758,14 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         them one after the other, :233-290).  Each GP sees the values its own sequential run would see.
         `loss_evaluator(X, y, ls, os, nz)` replaces the device loss in tests (the oracle's torch expression, as the
         checker of the driver logic); it is called per GP.
+
+        optimizer="lbfgs_device" (TrainingConfig.optimizer) replaces that loop by ONE HipEngine.train_search_host call: `restarts`
+        starts per GP advanced in lockstep on the GPU (gpmpc_train_search: `device_iterations` iterations of one trial point per
+        start, `device_history` curvature pairs) over x in [0, 1]^(E + 2), mapped geometrically into the constraint box (linearly
+        where a lower bound is not positive).  Start 0 of every GP is the incoming parameters, clipped into the box -- so the
+        winner is never worse than them -- and starts 1 .. restarts - 1 are one torch.rand((restarts - 1, D, E + 2)) draw.  A GP
+        whose every start has a non-finite loss keeps its incoming parameters.  The device search holds memories of up to 256
+        points; a larger one takes the loop above on gpmpc_mll (a dispatch on size; with print_train it says so).
 
         Whatever happens in here, exactly ONE answer is put on the queue: the list of parameter dicts, or a
         `TrainingFailed` (a list holding the INCOMING parameters, with the reason attached) when the engine cannot be
@@ -739,11 +782,19 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
             N, E = X.shape
             n_gp = len(saved_state.parameters)
             shared = None
+            if optimizer not in ("lbfgs", "lbfgs_device"):
+                raise ValueError(f"training optimizer {optimizer!r}: 'lbfgs' or 'lbfgs_device'")
+            if optimizer == "lbfgs_device" and loss_evaluator is not None:
+                raise ValueError("loss_evaluator replaces the device loss of the 'lbfgs' loop only")
+            device_search = optimizer == "lbfgs_device" and N <= _DEVICE_SEARCH_MAX_N
+            if optimizer == "lbfgs_device" and not device_search and print_train:
+                print(f"training: {N} memory points > {_DEVICE_SEARCH_MAX_N}: the host L-BFGS loop on gpmpc_mll instead of the device search")
             if loss_evaluator is None:
                 if device not in ("auto", "hip"):
                     raise ValueError(f"training device {device!r}: the loss runs on the GPU only ('auto' or 'hip')")
                 from ...engine import HipEngine       # raises without a GPU / without the HIP library
                 engine = HipEngine(0)
+            if loss_evaluator is None and not device_search:
                 shared = _LockstepMll(engine, torch.as_tensor(X, dtype=F64).to(engine.device).contiguous(),
                                       torch.as_tensor(Y, dtype=F64).to(engine.device).contiguous(), n_gp)
             K0, K1, K2 = GpHyperParameters.KEYS
@@ -755,10 +806,13 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                      for p in saved_state.parameters]
             # the restarts, drawn up front in the order the reference's sequential loop consumes the generator (:236-252)
             raws = []
-            for a in range(n_gp):
+            for a in range(0 if device_search else n_gp):          # (the device search draws its own starts, below)
                 raws.append({k: torch.logit(torch.rand(start[a][k].shape, dtype=F64).clamp(1e-6, 1 - 1e-6)).requires_grad_(True)
                              for k in ("os", "ls", "nz")})
             results = [None] * n_gp
+            if device_search:
+                results = GpStateTransitionModel._device_search(engine, X, Y, lo, hi, start, incoming, restarts, device_iterations,
+                                                                device_history)
 
             def search(a):
                 y = Y[:, a]
@@ -805,7 +859,9 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
                     if shared is not None:
                         shared.finished(a)
 
-            if shared is not None and n_gp > 1:
+            if device_search:
+                pass
+            elif shared is not None and n_gp > 1:
                 threads = [threading.Thread(target=worker, args=(a,), daemon=True) for a in range(n_gp)]
                 for th in threads:
                     th.start()

@@ -92,6 +92,7 @@ const Option kOptions[] = {
      "moments_linear_backward_chunk_points: 0 (auto) or a number of points"},
     {"lqr_gains_chunk_points", &Handle::opt_lqr_gains_chunk, 0, kChunkMax, 1, "lqr_gains_chunk_points: 0 (auto) or a number of candidates"},
     {"ilqr_chunk_points", &Handle::opt_ilqr_chunk, 0, kChunkMax, 1, "ilqr_chunk_points: 0 (auto) or a number of candidates"},
+    {"mll_batch_chunk", &Handle::opt_mll_batch_chunk, 1, kChunkMax, 1, "mll_batch_chunk: a number of problems >= 1"},
     {"sparse_chunk_points", &Handle::opt_sparse_chunk, 0, kChunkMax, 64, "sparse_chunk_points: 0 (auto) or a multiple of 64"},
     {"select_inducing_max_mb", nullptr, 1, LLONG_MAX, 1, "select_inducing_max_mb: a number of MiB >= 1", &Handle::opt_select_max_mb},
     {"incremental", &Handle::opt_incremental},
@@ -149,7 +150,7 @@ static int query_entry(gpmpc_t* g, const char* name, const char* count_name, int
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 26; }
+int gpmpc_abi_version(void) { return 27; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -177,7 +178,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->mllbws, &h->trainws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -762,6 +763,55 @@ int gpmpc_lbfgs_search(gpmpc_t* g, const double* mu0, const double* S0, int B, i
     GPMPC_HIP_CHECK(h, hipSetDevice(h->device));
     return run_lbfgs_search(h, a, propagation, first_iteration, iterations, history, c1, pgtol, mp, x0_dev, state_dev, best_out_dev,
                             (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Batched training loss and the multi-restart search on it (mll_batch.hip).  The checks the two entries share, in their order:
+// pointers and counts (GPMPC_ERR_ARG), then the compiled limits (GPMPC_ERR_LIMIT).
+static int mll_batch_checks(gpmpc_t* g, bool ptrs_ok, const double* lo, const double* hi, bool need_box, int N, int D, int E, int R,
+                            int log_scale) {
+    if (!ptrs_ok) return bad(g, "null argument");
+    if ((lo == nullptr) != (hi == nullptr)) return bad(g, "mll_batch: lo and hi must both be given or both be NULL");
+    if (need_box && !lo) return bad(g, "train_search: the box (lo, hi) is required");
+    if (N < 1 || R < 1 || D < 1 || E < 1) return bad(g, "mll_batch: need N >= 1, R >= 1, D >= 1, E >= 1");
+    if (log_scale != 0 && log_scale != 1) return bad(g, "mll_batch: log_scale must be 0 (linear map) or 1 (log map)");
+    const char* over = nullptr;
+    if (N > 256) over = "mll_batch: at most 256 memory points (one workgroup per problem)";
+    else if (D > kMaxD || E > kMaxE) over = "shape outside compiled limits (D <= 16, E <= 24)";
+    else if ((long long)R * D > kLbfgsMaxB) over = "mll_batch: at most 4096 problems (R * D)";
+    if (over) { g->h.err = over; return GPMPC_ERR_LIMIT; }
+    return GPMPC_OK;
+}
+
+int gpmpc_mll_batch(gpmpc_t* g, const double* X, const double* Y, int N, int D, int E, const double* params, int R,
+                    const double* lo, const double* hi, int log_scale, double* loss_out, double* grad_out, double* theta_out,
+                    int* info_out, void* stream) {
+    Range roctx_range("gpmpc_mll_batch");
+    if (!g) return GPMPC_ERR_ARG;
+    int rc = mll_batch_checks(g, X && Y && params && loss_out && grad_out, lo, hi, false, N, D, E, R, log_scale);
+    if (rc) return rc;
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_mll_batch(H_(g), X, Y, N, D, E, params, R, lo, hi, log_scale, loss_out, grad_out, theta_out, info_out,
+                         (hipStream_t)stream);
+}
+
+int gpmpc_train_search(gpmpc_t* g, const double* X, const double* Y, int N, int D, int E, int R, const double* lo, const double* hi,
+                       int log_scale, int first_iteration, int iterations, int history, double c1, double pgtol,
+                       const double* x0_dev, double* state_dev, double* best_out_dev, void* stream) {
+    Range roctx_range("gpmpc_train_search");
+    if (!g) return GPMPC_ERR_ARG;
+    int rc = mll_batch_checks(g, X && Y && state_dev && (first_iteration != 0 || x0_dev), lo, hi, true, N, D, E, R, log_scale);
+    if (rc) return rc;
+    bool limit = false;
+    if (const char* msg = lbfgs_check_shape((long long)R * D, 1, E + 2, history, limit)) {
+        g->h.err = msg;
+        return limit ? GPMPC_ERR_LIMIT : GPMPC_ERR_ARG;
+    }
+    if (const char* msg = lbfgs_check_step(first_iteration, c1, pgtol)) return bad(g, msg);
+    if (iterations < 1) return bad(g, "lbfgs: need iterations >= 1");
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    return run_train_search(H_(g), X, Y, N, D, E, R, lo, hi, log_scale, first_iteration, iterations, history, c1, pgtol, x0_dev,
+                            state_dev, best_out_dev, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

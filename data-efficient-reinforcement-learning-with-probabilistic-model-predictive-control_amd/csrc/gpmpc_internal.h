@@ -202,6 +202,8 @@ struct Handle {
     Buf xrange;   // (2, E) min / max of the inputs
     Buf gradws;   // gradient workspace: pair moments | mean sums | cost variances
     Buf mllws;    // marginal-likelihood workspace: tile partial sums | results
+    Buf mllbws;   // gpmpc_mll_batch: per problem of one chunk K -> L | L^-1 | iK (N, N each) | z | beta (N each) (mll_batch.hip)
+    Buf trainws;  // gpmpc_train_search: loss (R D) | d loss / d x (R D, E + 2) of the trial points
     Buf cemws;    // cross-entropy search workspace: optimiser vectors | model actions | J | mean | std | warm start | mapper
     Buf tilews;   // batch-major path: step records of the candidates | per-tile partial sums | hand-over flags
     Buf tgradws;  // gradient's tile pass: records of a block of (candidate, step) items | per-tile partial moments
@@ -314,6 +316,7 @@ struct Handle {
     int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_moments_linear_bwd_chunk = 0;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: the same for their chunks
     int opt_lqr_gains_chunk = 0;     // gpmpc_lqr_gains: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
+    int opt_mll_batch_chunk = 0;     // gpmpc_mll_batch / gpmpc_train_search: problems per launch and in the workspace (0: one per CU; results do not depend on it)
     int opt_ilqr_chunk = 0;          // gpmpc_ilqr_*: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int lds_limit = 160 * 1024;
     int num_cu = 256;
@@ -608,6 +611,15 @@ int run_ilqr_step(Handle* h, const double* mu0_host, int B, int H, int A, int in
 // ... `a` as fill_args leaves it (actions / J_out are set inside); best_out_dev [J | restart | actions (H A)] or NULL
 int run_ilqr_search(Handle* h, RolloutArgs& a, int iterations, int L, double reg0, double reg_factor, double reg_max, double tol,
                     const double* x0_dev, double* state_dev, double* best_out_dev, hipStream_t s);
+// mll_batch.hip: the training loss and gradient of R hyper-parameter sets per GP, left on the device (validated by the entry
+// points; lo / hi both NULL: params is theta itself), and the multi-restart search built on it and on run_lbfgs_step; both are
+// asynchronous on s and neither read nor write the cached model
+int run_mll_batch(Handle* h, const double* X, const double* Y, int N, int D, int E, const double* params, int R, const double* lo,
+                  const double* hi, int log_scale, double* loss_out, double* grad_out, double* theta_out, int* info_out,
+                  hipStream_t s);
+int run_train_search(Handle* h, const double* X, const double* Y, int N, int D, int E, int R, const double* lo, const double* hi,
+                     int log_scale, int first_iteration, int iterations, int history, double c1, double pgtol, const double* x0_dev,
+                     double* state_dev, double* best_out_dev, hipStream_t s);
 // prepare_small.hip: the single-launch paths of a plan (PreparePath::small_whole / small_cholesky)
 int launch_prepare_small(Handle* h, const PreparePlan& pp, const double* X, const double* Y, const double* ls, const double* os,
                          const double* noise, int N, int D, int E, hipStream_t s);

@@ -846,6 +846,97 @@ class HipEngine:
         host = out.cpu().numpy()                                # the one synchronisation
         return host[2:2 + n].copy(), float(host[0]), host[2 + n:2 + n + B].copy(), host[2 + n + B:].astype(np.int64)
 
+    # -- batched training loss and the multi-restart search on it (gpmpc_mll_batch, gpmpc_train_search) ---------------------
+    def _training_data(self, X, Y):
+        X = self._rows(X, "inputs", "N")
+        N, E = X.shape
+        Y = self._dev(Y)
+        if Y.dim() != 2 or Y.shape[0] != N:
+            raise ValueError(f"expected targets of shape ({N}, D), got {tuple(Y.shape)}")
+        return X, Y, N, int(Y.shape[1]), E
+
+    def _box(self, lo, hi, D, n, log_scale, required):
+        """The box (lo, hi) of shape (D, n) on the device, checked: both or neither, lo <= hi, lo > 0 under the log map."""
+        if lo is None and hi is None:
+            if required:
+                raise ValueError("train_search: the box (lo, hi) is required")
+            return None, None
+        if lo is None or hi is None:
+            raise ValueError("lo and hi must both be given or both be None")
+        lo_h, hi_h = _host(lo, (D, n)), _host(hi, (D, n))
+        if not np.all(lo_h <= hi_h):
+            raise ValueError("the box needs lo <= hi in every coordinate")
+        if log_scale and not np.all(lo_h > 0.0):
+            raise ValueError("the log map needs lo > 0 in every coordinate")
+        return self._dev(lo_h), self._dev(hi_h)
+
+    def mll_batch(self, X, Y, params, lo=None, hi=None, log_scale=True, out=None):
+        """gpmpc_mll_batch: training loss and gradient of R hyper-parameter sets per GP, params (R, D, E + 2) rows
+        [lengthscale (E) | outputscale | noise] -- or, with the box lo / hi (D, E + 2), x in [0, 1] mapped linearly or (log_scale)
+        geometrically into it, the gradient then wrt x.  Returns dict of device tensors loss (R, D), grad (R, D, E + 2),
+        theta (R, D, E + 2), info (R, D) int32 (0, or the order of the leading minor that is not positive definite: loss +inf,
+        gradient 0).  No synchronisation; the cached model is neither read nor written."""
+        X, Y, N, D, E = self._training_data(X, Y)
+        n = E + 2
+        params = self._dev(params)
+        if params.dim() != 3 or tuple(params.shape[1:]) != (D, n):
+            raise ValueError(f"expected parameters of shape (R, {D}, {n}), got {tuple(params.shape)}")
+        R = int(params.shape[0])
+        lo_d, hi_d = self._box(lo, hi, D, n, log_scale, False)
+        if out is None:
+            out = {"loss": torch.empty((R, D), dtype=torch.float64, device=self.device),
+                   "grad": torch.empty((R, D, n), dtype=torch.float64, device=self.device),
+                   "theta": torch.empty((R, D, n), dtype=torch.float64, device=self.device),
+                   "info": torch.empty((R, D), dtype=torch.int32, device=self.device)}
+        self._check(self.lib.gpmpc_mll_batch(self._h, X.data_ptr(), Y.data_ptr(), N, D, E, params.data_ptr(), R, _ptr(lo_d),
+                                             _ptr(hi_d), int(bool(log_scale)), out["loss"].data_ptr(), out["grad"].data_ptr(),
+                                             _ptr(out.get("theta")), _ptr(out.get("info")), self._stream()))
+        self._keep_train = (X, Y, params, lo_d, hi_d, out)
+        return out
+
+    def train_search(self, state, X, Y, lo, hi, iterations, x0=None, first_iteration=0, c1=1e-4, pgtol=1e-5, log_scale=True,
+                     best_out=None):
+        """gpmpc_train_search: the whole multi-restart hyper-parameter search on the device -- with first_iteration == 0 the init
+        from x0 (R, D, E + 2) in [0, 1], then `iterations` x [mll_batch of the state's actions with the box, lbfgs step].  `state`
+        is lbfgs_state(R * D, E + 2, history).  Returns the device record (D, 3 + E + 2) = [loss | restart | status | theta] per GP
+        (`best_out`, or a new tensor).  No synchronisation."""
+        X, Y, N, D, E = self._training_data(X, Y)
+        n, m = E + 2, state["history"]
+        if state["n"] != n or state["B"] % D:
+            raise ValueError("the state was made for another number of coordinates or of GPs")
+        R = state["B"] // D
+        lo_d, hi_d = self._box(lo, hi, D, n, log_scale, True)
+        x0 = self._dev(x0, (R, D, n)) if x0 is not None else None
+        if best_out is None:
+            best_out = torch.empty((D, 3 + n), dtype=torch.float64, device=self.device)
+        self._check(self.lib.gpmpc_train_search(self._h, X.data_ptr(), Y.data_ptr(), N, D, E, R, lo_d.data_ptr(), hi_d.data_ptr(),
+                                                int(bool(log_scale)), int(first_iteration), int(iterations), m, float(c1),
+                                                float(pgtol), _ptr(x0), state["buffer"].data_ptr(), best_out.data_ptr(),
+                                                self._stream()))
+        self._keep_train = (X, Y, lo_d, hi_d, x0, state["buffer"], best_out)
+        return best_out
+
+    def train_search_host(self, X, Y, x0, lo, hi, iterations, history=10, c1=1e-4, pgtol=1e-5, log_scale=True):
+        """The device search from the starts x0 (R, D, E + 2) -> dict of numpy arrays theta (D, E + 2), loss (D,), restart (D,)
+        (-1: every restart of that GP started non-finite), J (R, D), status (R, D), with ONE host synchronisation (a single copy
+        of the winner records and the per-restart values)."""
+        x0 = np.asarray(x0, dtype=np.float64)
+        if x0.ndim != 3:
+            raise ValueError(f"expected starts of shape (R, D, E + 2), got {x0.shape}")
+        R, D, n = x0.shape
+        P = R * D
+        st = self.lbfgs_state(P, n, history)
+        out = torch.empty(D * (3 + n) + 2 * P, dtype=torch.float64, device=self.device)
+        nb = D * (3 + n)
+        self.train_search(st, X, Y, lo, hi, iterations, x0=x0, c1=c1, pgtol=pgtol, log_scale=log_scale,
+                          best_out=out[:nb].view(D, 3 + n))
+        out[nb:nb + P].copy_(st["J"])
+        out[nb + P:].copy_(st["status"])
+        host = out.cpu().numpy()                                # the one synchronisation
+        best = host[:nb].reshape(D, 3 + n)
+        return {"theta": best[:, 3:].copy(), "loss": best[:, 0].copy(), "restart": best[:, 1].astype(np.int64),
+                "J": host[nb:nb + P].reshape(R, D).copy(), "status": host[nb + P:].reshape(R, D).astype(np.int64)}
+
     # -- device-resident iLQR (gpmpc_ilqr_*) --------------------------------------------------------
     def ilqr_backward(self, actions, mu0, reg, include_time=False, time0=0.0):
         """gpmpc_ilqr_backward at `actions` (B, H, A) with the regularisation `reg` (a scalar or (B,)): dict of device tensors

@@ -751,6 +751,43 @@ int gpmpc_lbfgs_search(gpmpc_t* h, const double* mu0_host, const double* S0_host
                        double* best_out_dev, void* stream);
 
 /*
+ * Hyper-parameter training whose loop stays on the device: the training loss of gpmpc_mll for R hyper-parameter sets per GP in one
+ * launch per chunk, left on the device, and a multi-restart search built on it and on gpmpc_lbfgs_step.  n = E + 2; a parameter
+ * row is [lengthscale (E) | outputscale | noise]; problem p = r D + a is restart r of GP a, P = R D.
+ *
+ * gpmpc_mll_batch: per problem loss_out_dev[p] = -log p(y_a | X, theta_p) / N and grad_out_dev[p] (n), gpmpc_mll's definition.
+ * Without a box (lo_dev = hi_dev = NULL) params_dev (R, D, n) is theta itself and the gradient is wrt theta.  With a box (D, n)
+ * params_dev is x in [0,1]^n, theta = lo + (hi - lo) x (log_scale 0) or theta = lo (hi / lo)^x (log_scale 1), and the gradient is
+ * wrt x (times hi - lo, or theta ln(hi / lo)).  theta_out_dev (R, D, n), may be NULL: the theta that was used.  Box validity
+ * (lo <= hi; lo > 0 under the log map) is the caller's to check.  A K_p + noise I that is not positive definite is a RESULT, not an
+ * error: loss = +inf, gradient = 0 and info_out_dev[p] (may be NULL) = the order of the first leading minor whose pivot is not
+ * positive and finite; otherwise info = 0.  gpmpc_lbfgs_step rejects a non-finite trial value and gives a non-finite start status 3.
+ * One workgroup per problem, N <= 256; every sum in a fixed order without atomics: two calls agree bit for bit, and a problem's
+ * result depends neither on R, nor on its position, nor on the chunk.  The workspace is the handle's, for option "mll_batch_chunk"
+ * problems at a time (default: one per CU), launched chunk after chunk on `stream`.
+ *
+ * gpmpc_train_search: with first_iteration == 0 gpmpc_lbfgs_init from x0_dev (R, D, n) (mapper 0, H = 1, A = n), then `iterations`
+ * times [gpmpc_mll_batch of the state's `actions` with the box; gpmpc_lbfgs_step k = first_iteration + i], then per GP a
+ * best_out_dev[a] (3 + n, may be NULL) = [loss | restart | status | theta]: the lowest state J over the restarts whose status != 3,
+ * ties to the lowest restart, theta = the box map of that restart's x; [+inf | -1 | 3 | theta of restart 0's x] where every restart
+ * has status 3.  state_dev: the caller's gpmpc_lbfgs_state_size(R D, n, history) doubles, laid out as for gpmpc_lbfgs_search.
+ * first_iteration > 0 continues a state (x0_dev unused).  The box is required.
+ *
+ * Both are asynchronous on `stream` without host synchronisation or a copy to the host, and neither read nor write the cached
+ * model, its record or the gpmpc_last_* state: a gpmpc_rollout after the call returns the bits it returned before.  Errors are
+ * reported before anything is enqueued or written.  GPMPC_ERR_ARG: NULL X / Y / params / loss / grad (train_search: state, x0 with
+ * first_iteration == 0, the box), only one of lo and hi, N < 1, R < 1, log_scale not 0 or 1, and for train_search history < 1,
+ * iterations < 1, first_iteration < 0, c1 outside (0, 1), pgtol < 0.  GPMPC_ERR_LIMIT: N > 256, D > GPMPC_MAX_D, E > GPMPC_MAX_E,
+ * R D > 4096, history > 32.
+ */
+int gpmpc_mll_batch(gpmpc_t* h, const double* X_dev, const double* Y_dev, int N, int D, int E, const double* params_dev, int R,
+                    const double* lo_dev, const double* hi_dev, int log_scale, double* loss_out_dev, double* grad_out_dev,
+                    double* theta_out_dev, int* info_dev, void* stream);
+int gpmpc_train_search(gpmpc_t* h, const double* X_dev, const double* Y_dev, int N, int D, int E, int R, const double* lo_dev,
+                       const double* hi_dev, int log_scale, int first_iteration, int iterations, int history, double c1,
+                       double pgtol, const double* x0_dev, double* state_dev, double* best_out_dev, void* stream);
+
+/*
  * Second-order candidate optimisation whose loop stays on the device: a clamped iLQR on the MEAN dynamics of the linearised
  * propagation, for B candidates in lockstep -- the trajectory optimiser beside gpmpc_cem_search and gpmpc_lbfgs_search.  Per
  * candidate, with ubar (H,A) in [0,1]:

@@ -64,6 +64,7 @@ SIGNATURES = {
     "gpmpc_rollout": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear_feedback": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout_feedback": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "gpmpc_lqr_gains": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P]),
     "gpmpc_rollout_grad": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -93,7 +94,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 def load(path=LIB_PATH):

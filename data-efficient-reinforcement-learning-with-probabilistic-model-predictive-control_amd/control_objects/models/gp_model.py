@@ -565,7 +565,8 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         dict, no autograd (NotImplementedError when grad mode is on and an input requires grad).
         `feedback_gains` (model space; (A, D), (H, A, D) or (B, H, A, D)): the linearised rollout in closed loop under
         u = actions_t + K_t (x - mu_t) (gpmpc_rollout_linear_feedback) -- Sig and the stage costs are the closed-loop ones, mu
-        is unchanged.  Only with "linearized" (ValueError with moment matching), and without autograd like it.
+        is unchanged.  Only with "linearized" (ValueError with moment matching, whose closed-loop rollout is
+        predict_trajectory_feedback_batch), and without autograd like it.
         `feedback_gains="lqr"`: every candidate's own LQR gains, designed on the device along its nominal trajectory on the
         loaded cost (gpmpc_lqr_gains, `lqr_reg` added to the diagonal of Huu) and handed to the closed-loop rollout without
         leaving it; the dict then also holds "gains" (B, H, A, D).  Any other string is a ValueError."""
@@ -574,7 +575,8 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         if isinstance(feedback_gains, str) and feedback_gains != "lqr":
             raise ValueError(f"feedback_gains must be an array or 'lqr', got {feedback_gains!r}")
         if feedback_gains is not None and self.propagation(propagation) != "linearized":
-            raise ValueError("feedback_gains need propagation='linearized': moment matching has no closed-loop rollout")
+            raise ValueError("feedback_gains need propagation='linearized' here; the closed-loop rollout under moment matching "
+                             "is predict_trajectory_feedback / predict_trajectory_feedback_batch")
         if self.propagation(propagation) == "linearized":
             _no_linearized_autograd("predict_trajectory", actions, obs_mu, obs_var, feedback_gains)
             actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
@@ -637,6 +639,41 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         out = self.predict_trajectory_batch(_t(actions)[None], obs_mu, obs_var, len_horizon, current_time_idx,
                                             trajectories=True, stage_costs=False, propagation=propagation,
                                             feedback_gains=feedback_gains, lqr_reg=lqr_reg)
+        return out["mu"][0].cpu(), out["Sig"][0].cpu()
+
+    def predict_trajectory_feedback_batch(self, actions, feedback_gains, obs_mu, obs_var, len_horizon=None, current_time_idx=0,
+                                          trajectories=True, stage_costs=True, lqr_reg=0.0):
+        """The moment-matched rollout in closed loop under u = actions_t + K_t (x - mu_t) (gpmpc_rollout_feedback): the dict of
+        predict_trajectory_batch, with mu, Sig and the stage costs those of the policy -- under moment matching the gains move
+        mu as well.  Always moment-matched, whatever ModelConfig.uncertainty_propagation is.  `feedback_gains` (model space):
+        (A, D), (H, A, D), (B, H, A, D), or "lqr": every candidate's own LQR gains (gpmpc_lqr_gains on the loaded cost, `lqr_reg`
+        added to the diagonal of Huu), kept on the device; the dict then also holds "gains" (B, H, A, D).  No autograd
+        (NotImplementedError when grad mode is on and an input requires grad); the realised action is not clipped."""
+        if self._cost_key is None and stage_costs:
+            raise RuntimeError("call set_cost(reward_config) before predicting costs")
+        if feedback_gains is None or (isinstance(feedback_gains, str) and feedback_gains != "lqr"):
+            raise ValueError(f"feedback_gains must be an array or 'lqr', got {feedback_gains!r}")
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for t in (actions, obs_mu, obs_var, feedback_gains)):
+            raise NotImplementedError("predict_trajectory_feedback: the closed-loop moment-matched rollout has no autograd; "
+                                      "detach the inputs or run under torch.no_grad()")
+        actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
+        if len_horizon is not None and actions.shape[1] != len_horizon:
+            raise ValueError("actions.shape[1] != len_horizon")
+        args = (_t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model, float(current_time_idx), trajectories,
+                stage_costs)
+        if isinstance(feedback_gains, str):               # "lqr"
+            if self._cost_key is None:
+                raise RuntimeError("call set_cost(reward_config) before feedback_gains='lqr': the gains are designed on it")
+            return self.engine.rollout_feedback_lqr(actions, *args, reg=float(lqr_reg))
+        gains = feedback_gains if isinstance(feedback_gains, torch.Tensor) else np.asarray(feedback_gains)
+        return self.engine.rollout_feedback(actions, torch.as_tensor(gains, dtype=F64), *args)
+
+    def predict_trajectory_feedback(self, actions, feedback_gains, obs_mu, obs_var, len_horizon, current_time_idx, lqr_reg=0.0):
+        """ONE action sequence (H, A) -> ((H+1,D), (H+1,D,D)) CPU tensors of the closed-loop moment-matched trajectory:
+        predict_trajectory's shapes, predict_trajectory_feedback_batch's policy (`feedback_gains` (A, D), (H, A, D) or "lqr")."""
+        out = self.predict_trajectory_feedback_batch(_t(actions)[None], feedback_gains, obs_mu, obs_var, len_horizon,
+                                                     current_time_idx, trajectories=True, stage_costs=False, lqr_reg=lqr_reg)
         return out["mu"][0].cpu(), out["Sig"][0].cpu()
 
     def predict(self, inputs, include_noise=True):

@@ -90,6 +90,8 @@ const Option kOptions[] = {
      "moments_linear_chunk_points: 0 (auto) or a number of points"},
     {"moments_linear_backward_chunk_points", &Handle::opt_moments_linear_bwd_chunk, 0, kChunkMax, 1,
      "moments_linear_backward_chunk_points: 0 (auto) or a number of points"},
+    {"rollout_feedback_chunk_points", &Handle::opt_rollout_feedback_chunk, 0, kChunkMax, 1,
+     "rollout_feedback_chunk_points: 0 (auto) or a number of candidates"},
     {"lqr_gains_chunk_points", &Handle::opt_lqr_gains_chunk, 0, kChunkMax, 1, "lqr_gains_chunk_points: 0 (auto) or a number of candidates"},
     {"ilqr_chunk_points", &Handle::opt_ilqr_chunk, 0, kChunkMax, 1, "ilqr_chunk_points: 0 (auto) or a number of candidates"},
     {"mll_batch_chunk", &Handle::opt_mll_batch_chunk, 1, kChunkMax, 1, "mll_batch_chunk: a number of problems >= 1"},
@@ -150,7 +152,7 @@ static int query_entry(gpmpc_t* g, const char* name, const char* count_name, int
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 27; }
+int gpmpc_abi_version(void) { return 28; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -178,7 +180,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->mllbws, &h->trainws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->mllbws, &h->trainws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->fbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -461,6 +463,25 @@ int gpmpc_rollout_linear_feedback(gpmpc_t* g, const double* actions, const doubl
     Range roctx_range(gains ? "gpmpc_rollout_linear_feedback" : "gpmpc_rollout_linear");
     return rollout_entry(g, true, actions, gains, gains_per_candidate, mu0, S0, B, H, A, include_time, time0, mu_out, Sig_out, cm_out,
                          cv_out, J_out, stream);
+}
+
+int gpmpc_rollout_feedback(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate, const double* mu0,
+                           const double* S0, int B, int H, int A, int include_time, double time0, double* mu_out, double* Sig_out,
+                           double* cm_out, double* cv_out, double* J_out, void* stream) {
+    Range roctx_range("gpmpc_rollout_feedback");
+    if (!g) return GPMPC_ERR_ARG;
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, cm_out || cv_out || J_out);
+    if (rc) return rc;
+    if (gains && A < 1) return bad(g, "feedback gains need A >= 1");
+    if (a.D > GPMPC_MAX_D || a.E > GPMPC_MAX_E) {
+        g->h.err = "rollout_feedback: D or E beyond the compiled limits";
+        return GPMPC_ERR_LIMIT;
+    }
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    a.mu_out = mu_out; a.Sig_out = Sig_out; a.cm_out = cm_out; a.cv_out = cv_out; a.J_out = J_out;
+    // without gains: the all-zero policy through the closed-loop kernels (gpmpc_rollout to rounding, not bit for bit)
+    return run_rollout_feedback(H_(g), a, (hipStream_t)stream, gains, gains && gains_per_candidate != 0);
 }
 
 int gpmpc_lqr_gains(gpmpc_t* g, const double* actions, const double* mu0, int B, int H, int A, int include_time, double time0,

@@ -465,8 +465,8 @@ class HipEngine:
         return self._dev(gains), per_candidate
 
     def _rollout(self, name, actions, mu0, S0, include_time, time0, trajectories, stage_costs, out, closed_loop=False, gains=None):
-        """`rollout`, `rollout_linear` and `rollout_linear_feedback`: `name` picks the library's entry; the closed-loop one takes
-        (gains, per_candidate) behind the actions."""
+        """`rollout`, `rollout_linear`, `rollout_linear_feedback` and `rollout_feedback`: `name` picks the library's entry; the
+        closed-loop ones take (gains, per_candidate) behind the actions."""
         actions = self._dev(actions)
         B, H, A = actions.shape
         D = self.D
@@ -532,6 +532,27 @@ class HipEngine:
         actions = self._dev(actions)
         gains = self.lqr_gains(actions, mu0, include_time, time0, reg)["gains"]
         res = self.rollout_linear_feedback(actions, gains, mu0, S0, include_time, time0, trajectories, stage_costs, out)
+        res["gains"] = gains
+        return res
+
+    def rollout_feedback(self, actions, gains, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True,
+                         out=None):
+        """`rollout` -- moment matching -- in closed loop (gpmpc_rollout_feedback): the policy is u = actions_t + K_t (x - mu_t),
+        every step's moments are gpmpc_moments' at the policy's full input covariance, and mu, Sig and the stage costs are those
+        of that policy (unlike `rollout_linear_feedback`, the gains move mu too).  `gains` (model space): (A, D), (H, A, D) or
+        (B, H, A, D) as there; None: the all-zero gains through the same kernels (`rollout` to rounding, not bit for bit).  The
+        same dict.  Asynchronous on the current stream."""
+        return self._rollout("rollout_feedback", actions, mu0, S0, include_time, time0, trajectories, stage_costs, out,
+                             closed_loop=True, gains=gains)
+
+    def rollout_feedback_lqr(self, actions, mu0, S0, include_time=False, time0=0.0, trajectories=True, stage_costs=True, out=None,
+                             reg=0.0):
+        """`rollout_feedback` under each candidate's own LQR gains: `lqr_gains`, then the moment-matched closed-loop rollout with
+        those (B, H, A, D) gains, which never leave the device.  That call's dict plus "gains"; bit for bit the two calls made
+        separately.  Asynchronous on the current stream."""
+        actions = self._dev(actions)
+        gains = self.lqr_gains(actions, mu0, include_time, time0, reg)["gains"]
+        res = self.rollout_feedback(actions, gains, mu0, S0, include_time, time0, trajectories, stage_costs, out)
         res["gains"] = gains
         return res
 

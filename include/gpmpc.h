@@ -395,7 +395,8 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * chunk: 0 auto), "moments_backward_chunk_points" (the same for gpmpc_moments_backward),
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
- * gpmpc_rollout_linear_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
+ * gpmpc_rollout_linear_feedback_backward), "rollout_feedback_chunk_points" (candidates of gpmpc_rollout_feedback per internal
+ * chunk: 0 auto), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
  * "ilqr_chunk_points" (candidates of gpmpc_ilqr_* per internal chunk: 0 auto),
  * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64),
  * "select_inducing_max_mb" (cap on the workspace of gpmpc_select_inducing in MiB, >= 1; 4096 unless set).
@@ -481,6 +482,45 @@ int gpmpc_rollout_linear_feedback(gpmpc_t* h, const double* actions_dev, const d
                                   const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time,
                                   double time0, double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev,
                                   double* cost_var_out_dev, double* J_out_dev, void* stream);
+
+/*
+ * gpmpc_rollout_feedback: gpmpc_rollout -- moment matching, the reference's own propagation -- in closed loop under the policy of
+ * gpmpc_rollout_linear_feedback,
+ *   u = ubar_t + K_t (x - mu_t),  x ~ N(mu_t, Sigma_t),  ubar = actions_dev,  K_t (A, D) in model space.
+ * Arguments, layouts, output nullability and asynchrony are those of gpmpc_rollout_linear_feedback: gains_dev is (B,H,A,D) when
+ * gains_per_candidate != 0, else (H,A,D) shared by all candidates.  Per step t, with G_t = [I_D ; K_t ; 0] (E x D, the time row
+ * zero): the model input mean is [mu_t | ubar_t | time0 + t], the model input covariance Sigma_in = G_t Sigma_t G_t^T, formed by
+ * blocks (Sigma_t, K_t Sigma_t, its transpose, K_t Sigma_t K_t^T) for i <= j and mirrored -- exactly symmetric, the time row and
+ * column exactly zero.  With M, S, V of gpmpc_moments (its kernels) at that input,
+ *   C = (first D rows of Sigma_in) V = Sigma_t (V_s + K_t^T V_u),
+ *   mu_{t+1} = mu_t + M,   Sigma_{t+1} = Sigma_t + S + C + C^T
+ * computed for a <= b and mirrored: Sigma_t (t >= 1) is exactly symmetric; index 0 of the outputs is the input state.  This is the
+ * recurrence of predict_trajectory (gp_model.py:95-108) fed the policy's full input covariance.  UNLIKE the linearised form, the
+ * gains DO move the mean: M depends on Sigma_in, so mu_out differs from gpmpc_rollout's for the same actions.  Sigma_in has rank D
+ * in E dimensions, which is harmless: only I + Lambda Sigma_in forms are factorised, never Sigma_in itself.
+ * Stage costs (t < H): the quadratic cost with the full state-action covariance [I ; K_t] Sigma_t [I ; K_t]^T; the constraint term
+ * (state marginals only), the terminal cost, kappa, clipping and J are those of gpmpc_rollout_linear_feedback (the same cost
+ * kernel, on the stored trajectory).  The cost outputs need gpmpc_set_cost for this (D, A); with all three NULL the call is the
+ * plain trajectory.  NOT modelled, as there: the realised action u is not clipped to [0, 1].
+ * gains_dev == NULL: the all-zero-gain policy through these same kernels (bit for bit the call with a zero gain array).  It equals
+ * gpmpc_rollout to rounding, NOT bit for bit: the moments come from gpmpc_moments' kernels, the costs from the closed-loop kernel.
+ * Batch-major, per chunk of candidates: one init launch; per horizon step the setup / point / pair / finish launches of
+ * gpmpc_moments over the chunk and one step launch (five launches a step); the cost launch.  There is no fused-horizon form.
+ * Workspace of its own (a chunk's model input means and covariances, M, S, V, the trajectory where the caller keeps none, and the
+ * zero gains of a call without gains), within 16 MB or one candidate's need: option "rollout_feedback_chunk_points" (candidates
+ * per chunk, 0 auto).  The call ALSO uses gpmpc_moments' workspace and honours "moments_chunk_points".  It touches no other
+ * workspace and no gpmpc_last_* state.  A candidate's results are bitwise the same alone, at any position of any batch, for any
+ * value of "rollout_feedback_chunk_points" or "moments_chunk_points", and whether its gains arrive shared or per candidate.
+ * Every sum runs in an order fixed by N, E, D and A alone; no atomics.  Reads only the cached factors, so it works unchanged on a
+ * model from gpmpc_prepare_sparse / gpmpc_set_factors.
+ * Errors (no output is written): GPMPC_ERR_ARG for no cached model, NULL actions / mu0 / S0, B < 1, H < 1, A < 0,
+ * D + A (+1) != E, cost outputs without gpmpc_set_cost for this (D, A), a non-NULL gains_dev with A < 1; GPMPC_ERR_LIMIT for
+ * D > GPMPC_MAX_D or E > GPMPC_MAX_E.
+ */
+int gpmpc_rollout_feedback(gpmpc_t* h, const double* actions_dev, const double* gains_dev, int gains_per_candidate,
+                           const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time, double time0,
+                           double* mu_out_dev, double* Sig_out_dev, double* cost_mu_out_dev, double* cost_var_out_dev,
+                           double* J_out_dev, void* stream);
 
 /*
  * gpmpc_lqr_gains: the feedback gains gpmpc_rollout_linear_feedback takes as given -- per candidate, the finite-horizon LQR gains

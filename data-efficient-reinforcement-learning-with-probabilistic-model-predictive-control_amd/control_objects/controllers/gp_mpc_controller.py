@@ -18,20 +18,22 @@ ONE launch of the HIP rollout kernel:
     The reference's two pass-through clamps (action clamp of DerivativeActionMapper, optional clip of
     the UCB at 0) have identity backward; the finite difference is taken where those clamps are
     transparent so the returned gradient has the same meaning.
+
+The candidate searches are functions of candidate_search.py, looked up in its table; this class keeps the skeleton around them
+(`_get_optimal_actions`, `_adopt`) and the objective they evaluate.
 """
 import multiprocessing
 
 import numpy as np
 import torch
-from scipy.optimize import minimize
 
-from ..actions_mappers.action_init_functions import (generate_mpc_action_init_frompreviousiter,
-                                                     generate_mpc_action_init_random)
+from ..actions_mappers.action_init_functions import generate_mpc_action_init_random
 from ..actions_mappers.mappers import DerivativeActionMapper, NormalizationActionMapper
 from ..memories.gp_memory import Memory
 from ..models.gp_model import GpStateTransitionModel, TrainingFailed
 from ..observations_states_mappers.normalization_observation_state_mapper import NormalizationObservationStateMapper
 from ..states_reward_mappers.setpoint_distance_reward_mapper import SetpointStateRewardMapper
+from . import candidate_search
 from .abstract_controller import BaseControllerObject
 from .iteration_info_class import IterationInformation
 from ..._lib import GPMPC_ERR_ARG, GPMPC_ERR_LIMIT, GpmpcError
@@ -68,44 +70,39 @@ class GpMpcController(BaseControllerObject):
         self.process_group = None      # torch.distributed group the candidates shard over (None: the default group)
         self._check_propagation_supported()
 
-    LINEARIZED_OPTIMIZERS = ("optimize=False (random shooting), candidate_optimizer='cem' or, in open loop, "
-                             "candidate_optimizer='lbfgs_device' or candidate_optimizer='ilqr_device'")
+    LINEARIZED_OPTIMIZERS = candidate_search.linearized_optimizers()
 
     def _check_propagation_supported(self, what=None):
-        """ModelConfig.uncertainty_propagation = "linearized" has objective values only (gpmpc_rollout_linear): the searches
-        that go through `evaluate_candidates` work, and so does the device-resident L-BFGS ("lbfgs_device": gpmpc_lbfgs_search
-        drives gpmpc_rollout_linear and its backward itself) in open loop; the device-side cross-entropy search, the batched
-        L-BFGS and the scipy L-BFGS-B loop need host-side gradient plumbing the linearised path does not have.
-        ControllerConfig.feedback_gain (closed-loop planning, gpmpc_rollout_linear_feedback) exists for the linearised
-        propagation only, and not for "lbfgs_device" (its objective is the open-loop one).  The device-resident iLQR
-        ("ilqr_device": gpmpc_ilqr_search) exists under "linearized" only, in open loop, with the normalisation mapper."""
-        if getattr(self.config.controller, "candidate_optimizer", None) == "ilqr_device" and self.config.controller.optimize:
-            if self.transition_model.propagation() != "linearized":
-                raise ValueError("candidate_optimizer='ilqr_device' needs ModelConfig.uncertainty_propagation='linearized': the "
-                                 "iLQR runs on the mean dynamics of the linearised propagation, moment matching has none")
-            if getattr(self.config.controller, "feedback_gain", None) is not None:
-                raise ValueError("candidate_optimizer='ilqr_device' plans in open loop: it does not support "
-                                 "ControllerConfig.feedback_gain")
-            if isinstance(self.actions_mapper, DerivativeActionMapper):
-                raise ValueError("candidate_optimizer='ilqr_device' optimises the model actions themselves: it needs the "
-                                 "normalisation action mapper, not the DerivativeActionMapper")
+        """Refuse what the configured search does not support (the table of candidate_search.py): its
+        uncertainty propagation, closed-loop planning under ControllerConfig.feedback_gain (which exists for the linearised
+        propagation only), the DerivativeActionMapper.  `what` names a gradient-path entry point that asks for itself: the
+        linearised propagation has objective values only, so it refuses them all."""
+        key, search = candidate_search.lookup(self.config.controller)
+        linearized = self.transition_model.propagation() == "linearized"
+        closed_loop = getattr(self.config.controller, "feedback_gain", None) is not None
+
+        def refuse(reason):                          # in the search's own words (no string is built on the way through)
+            raise ValueError(f"{candidate_search.name_of(key)} {reason}")
+        if "moment_matching" not in search.propagations:     # a search of the linearised propagation alone says what it needs first
+            if not linearized:
+                refuse("needs ModelConfig.uncertainty_propagation='linearized': " + search.why_not["propagation"])
+            if closed_loop and not search.feedback:
+                refuse(search.why_not["feedback"] + ": it does not support ControllerConfig.feedback_gain")
+            if not search.derivative and isinstance(self.actions_mapper, DerivativeActionMapper):
+                refuse(search.why_not["derivative"])
             if what is None:
                 return
-        if self.transition_model.propagation() != "linearized":
-            if getattr(self.config.controller, "feedback_gain", None) is not None:
+        if not linearized:
+            if closed_loop:
                 raise ValueError("ControllerConfig.feedback_gain needs ModelConfig.uncertainty_propagation='linearized': "
                                  "moment matching has no closed-loop rollout")
             return
-        cc = self.config.controller
         if what is None:
-            if not cc.optimize or getattr(cc, "candidate_optimizer", None) == "cem":
+            if "linearized" in search.propagations:
+                if closed_loop and not search.feedback:
+                    refuse(search.why_not["feedback"] + ": it does not support ControllerConfig.feedback_gain")
                 return
-            if getattr(cc, "candidate_optimizer", None) == "lbfgs_device":
-                if getattr(cc, "feedback_gain", None) is not None:
-                    raise ValueError("candidate_optimizer='lbfgs_device' searches the open-loop objective: it does not support "
-                                     "ControllerConfig.feedback_gain")
-                return
-            what = f"candidate_optimizer={getattr(cc, 'candidate_optimizer', None)!r} with optimize=True"
+            what = f"{candidate_search.name_of(key)} with optimize=True"
         raise ValueError(f"uncertainty_propagation='linearized' does not support {what}: it has no gradient or device-search "
                          f"kernels; supported optimisers: {self.LINEARIZED_OPTIMIZERS}")
 
@@ -118,19 +115,6 @@ class GpMpcController(BaseControllerObject):
         if not getattr(self.config.controller, "shard_over_ranks", False) or not (dist.is_available() and dist.is_initialized()):
             return 1, 0
         return dist.get_world_size(self.process_group), dist.get_rank(self.process_group)
-
-    @staticmethod
-    def _state_checksum(state_mu, state_var):
-        """One double that differs between ranks whose (state, state variance) differ: travels inside the winner records."""
-        a = np.concatenate([np.asarray(state_mu, dtype=np.float64).ravel(), np.asarray(state_var, dtype=np.float64).ravel()])
-        w = np.cos(np.arange(1, a.size + 1, dtype=np.float64))           # position-dependent weights: permutations differ too
-        return float(np.dot(a, w))
-
-    @staticmethod
-    def _assert_ranks_agree(column, what):
-        if not bool((column == column[0]).all()):
-            raise RuntimeError(f"candidate sharding: the ranks disagree on {what} ({column.tolist()}); every rank must see the "
-                               "same observation and seed numpy identically (or switch ControllerConfig.shard_over_ranks off)")
 
     # ------------------------------------------------------------------------------ public
     def get_action(self, obs_mu, obs_var=None, random=False):
@@ -377,201 +361,31 @@ class GpMpcController(BaseControllerObject):
         self.transition_model.prepare_inference(x_mem, y_mem)
 
     def _get_optimal_actions(self, state_mu, state_var):
-        """Reference :114-153."""
+        """Reference :114-153.  The searches and the table they are looked up in: candidate_search.py."""
         self._check_propagation_supported()
         self._prepare()
-        cc = self.config.controller
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        if not cc.optimize:
-            return self._random_shooting(state_mu, state_var)
-        if getattr(cc, "candidate_optimizer", None) == "cem":
-            return self._cross_entropy_search(state_mu, state_var)
-        if getattr(cc, "candidate_optimizer", None) == "cem_device":
-            return self._device_cross_entropy_search(state_mu, state_var)
-        if getattr(cc, "candidate_optimizer", None) == "lbfgs":
-            return self._batched_lbfgs_search(state_mu, state_var)
-        if getattr(cc, "candidate_optimizer", None) == "lbfgs_device":
-            return self._device_lbfgs_search(state_mu, state_var)
-        if getattr(cc, "candidate_optimizer", None) == "ilqr_device":
-            return self._device_ilqr_search(state_mu, state_var)
-        opt_fun, best = np.inf, None
-        for idx_restart in range(cc.restarts_optim):
-            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and idx_restart == 0:
-                x0 = generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A)
-            else:
-                x0 = generate_mpc_action_init_random(len_horizon=H, dim_action=A)
-            res = minimize(fun=self.compute_mean_lcb_trajectory, x0=x0, jac=True, args=(state_mu, state_var),
-                           method="L-BFGS-B", bounds=self.actions_mapper.bounds, options=cc.actions_optimizer_params)
-            if res.fun < opt_fun or (best is None and np.isnan(res.fun)):
-                opt_fun, best = res.fun, res.x
-        self.actions_mpc_previous_iter = best.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best)
+        _, search = candidate_search.lookup(self.config.controller)
+        return self._adopt(search.run(self, state_mu, state_var))
 
-    def _random_shooting(self, state_mu, state_var):
-        """optimize=False: the reference draws TWO sequences per restart and evaluates the second
-        (:127-130 then :143); reproduced so that a seeded run sees the same candidates."""
-        from ... import sharding
-        cc = self.config.controller
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        cands = []
-        for idx_restart in range(cc.restarts_optim):
-            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and idx_restart == 0:
-                generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A)
-            else:
-                generate_mpc_action_init_random(len_horizon=H, dim_action=A)
-            cands.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
-        cands = np.stack(cands)
-        B = cands.shape[0]
-        world, rank = self._ranks()
-        # Every rank draws the SAME B candidates (the reference's global numpy generator, seeded identically on all
-        # ranks by the launcher; checked below through a checksum inside the records) and evaluates its contiguous slice; a
-        # rank whose slice is empty (B < world) launches nothing and contributes an (inf, -1) record.
-        lo, hi = sharding.shard_bounds(B, world, rank)
-        eng = self.transition_model.engine
-        failure = None
-        try:
-            out = self.evaluate_candidates(cands[lo:hi], state_mu, state_var, trajectories=True) if hi > lo else None
-        except Exception as e:                   # noqa: BLE001 -- world > 1: handed on after the collective, see below
-            if world == 1:
-                raise
-            # this rank must still enter the step's all_gather (its peers would wait in it until the watchdog fires): it
-            # contributes an (inf, -1) record whose error flag every rank reads after the exchange
-            failure, out = e, None
-        local = torch.as_tensor(cands[lo:hi].reshape(hi - lo, H, A), device=eng.device)
-        if failure is not None:
-            local = local[:0]
-        if world == 1:
-            J, best, win = sharding.select_best_on_device(eng, out["J"], local, lo, B, group=sharding.LOCAL)
-            self._cache_trajectory(out, B - 1)       # the reference caches the LAST evaluated trajectory, not the winner's (:279-283)
-        else:
-            # ... and so must every rank here (get_action reads the caches on all of them): the owner of the last
-            # global candidate appends that trajectory to its record, so the step's whole exchange is ONE all_gather.
-            D = self.transition_model.dim_state
-            last_owner = sharding.owner_of(B - 1, B, world)
-            if rank == last_owner and out is not None:
-                extra = torch.cat([out[k][-1].reshape(-1) for k in ("mu", "Sig", "cost_mu", "cost_var")] + [out["J"][-1:]])
-            else:
-                extra = torch.zeros((H + 1) * (D + D * D + 2) + 1, dtype=F64, device=eng.device)
-            # two trailing doubles: checksums of the state and of the drawn candidates (same on every rank, or the union of
-            # the slices is not the single-GPU population)
-            # three trailing doubles: an error flag, and checksums of the state and of the drawn candidates (same on every rank, or
-            # the union of the slices is not the single-GPU population)
-            sums = torch.tensor([0.0 if failure is None else 1.0, self._state_checksum(state_mu, state_var),
-                                 float(np.dot(cands.ravel(), np.cos(np.arange(cands.size))))], dtype=F64, device=eng.device)
-            J, best, win, extras = sharding.select_best_on_device(eng, None if out is None else out["J"], local, lo, B,
-                                                                  extra=torch.cat([extra, sums]), group=self.process_group,
-                                                                  raise_if_none=False)
-            if failure is not None:
-                raise failure
-            failed = [r for r in range(world) if float(extras[r, -3]) != 0.0]
-            if failed:
-                raise RuntimeError(f"random shooting: the slice of rank(s) {failed} failed; no winner this step")
-            self._assert_ranks_agree(extras[:, -2], "the state")
-            self._assert_ranks_agree(extras[:, -1], "the drawn candidates")
-            if win is None:
-                raise FloatingPointError("no selectable candidate (all objectives NaN)")
-            self._cache_packed_trajectory(extras[last_owner][:-3], H, D)
-        self.best_candidate_index, self.best_candidate_J = best, J
-        self.actions_mpc_previous_iter = win.numpy().reshape(-1).copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(self.actions_mpc_previous_iter)
-
-    def _cross_entropy_search(self, state_mu, state_var):
-        """Batched replacement of the sequential scipy restarts: every iteration is ONE
-        rollout launch over `cem_candidates` sequences drawn around the current mean (iteration 0: uniform,
-        plus the shifted previous solution when init_from_previous_actions), the elites refit mean / std of a
-        diagonal Gaussian over the optimiser vector in [0, 1]^(H*A); the best sequence ever evaluated wins."""
-        cc = self.config.controller
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        n, B = H * A, int(cc.cem_candidates)
-        n_elite = max(2, int(round(B * cc.cem_elite_fraction)))
-        rng = np.random                                        # the reference's global generator
-        mean, std = np.full(n, 0.5), np.full(n, 0.5)
-        best_x, best_J = None, np.inf
-        for it in range(int(cc.cem_iterations)):
-            if it == 0:
-                cands = rng.uniform(0.0, 1.0, size=(B, n))
-                if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None:
-                    cands[0] = generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A)
-            else:
-                cands = np.clip(mean + std * rng.standard_normal((B, n)), 0.0, 1.0)
-                cands[0] = best_x                              # keep the incumbent
-            out = self.evaluate_candidates(cands, state_mu, state_var, trajectories=True)
-            J = out["J"].cpu().numpy()
-            J = np.where(np.isnan(J), np.inf, J)
-            order = np.argsort(J, kind="stable")
-            if J[order[0]] < best_J:
-                best_J, best_x = float(J[order[0]]), cands[order[0]].copy()
-                self._cache_trajectory(out, int(order[0]))
-            elites = cands[order[:n_elite]]
-            mean, std = elites.mean(axis=0), elites.std(axis=0) + 1e-3
-        if best_x is None:
-            raise FloatingPointError("no finite objective among the candidates")
-        self.best_candidate_J = best_J
-        self.actions_mpc_previous_iter = best_x.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
-
-    def _device_cross_entropy_search(self, state_mu, state_var):
-        """candidate_optimizer = "cem_device": the cross-entropy search of `_cross_entropy_search` with its whole loop
-        on the GPU (gpmpc_cem_search: sampling, action mapper, rollout, elite selection and refit enqueued back to back,
-        nothing read back between iterations).  Two host synchronisations per control step -- the winner, then its
-        trajectory for the logging caches -- instead of one per iteration; the draws are Philox, keyed by a seed taken
-        from numpy's global generator (so `np.random.seed` still makes a run reproducible)."""
-        cc = self.config.controller
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        B = int(cc.cem_candidates)
-        n_elite = max(2, int(round(B * cc.cem_elite_fraction)))
-        first = None
-        if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None:
-            first = generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A)
-        kw = {}
-        if isinstance(self.actions_mapper, DerivativeActionMapper):
-            kw = dict(max_change=np.asarray(self.config.actions.max_change_action_norm, dtype=np.float64),
-                      action_prev=self.actions_mapper.action_model_previous_iter.numpy())
-        seed = int(np.random.randint(0, 2 ** 62))          # the Philox key (np.random.seed keeps a run reproducible)
-        tm = self.transition_model
-        tm.set_cost(self.config.reward)
-        world, rank = self._ranks()
-        if world > 1:
-            # candidates sharded over the ranks: each draws its slice from the shared Philox key, one elite merge per iteration.
-            # The key, the state and the starting vector are rank 0's on every rank (ONE small broadcast per control step: the
-            # union of the slices is the single-GPU population only if they are identical everywhere; nothing but the launcher
-            # enforced that before).
-            from ... import sharding
-            n = H * A
-            head = np.concatenate([[float(seed >> 31), float(seed & 0x7fffffff), 1.0 if first is not None else 0.0],
-                                   np.zeros(n) if first is None else np.asarray(first, dtype=np.float64).ravel(),
-                                   np.asarray(state_mu, dtype=np.float64).ravel(), np.asarray(state_var, dtype=np.float64).ravel()])
-            mine = self._state_checksum(state_mu, state_var)
-            head = sharding.broadcast_from_first(head, tm.engine.device, self.process_group)
-            # the ranks must sit at the SAME state (the other searches verify it inside their exchange): compared with rank 0's
-            # here, and the verdict is taken by all ranks together (one rank raising alone would leave the others in the search's
-            # collectives)
-            theirs = self._state_checksum(head[3 + n:3 + n + np.asarray(state_mu).size], head[3 + n + np.asarray(state_mu).size:])
-            if sharding.any_rank(mine != theirs, tm.engine.device, self.process_group):
-                raise RuntimeError("candidate sharding: the ranks disagree on the state; every rank must see the same observation "
-                                   "(or switch ControllerConfig.shard_over_ranks off)")
-            seed = (int(head[0]) << 31) | int(head[1])
-            first = head[3:3 + n].copy() if head[2] != 0.0 else None
-            nmu = np.asarray(state_mu).size
-            state_mu = head[3 + n:3 + n + nmu].reshape(np.shape(state_mu))
-            state_var = head[3 + n + nmu:].reshape(np.shape(state_var))
-            best_x, best_J = sharding.sharded_cem_search(
-                tm.engine, np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), B, H, A,
-                int(cc.cem_iterations), n_elite, seed=seed, include_time=tm.config.include_time_model,
-                time0=float(self.iter_ctrl), first_candidate=first, group=self.process_group, **kw)
-        else:
-            best_x, best_J = tm.engine.cem_search(
-                np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), B, H, A,
-                int(cc.cem_iterations), n_elite, seed=seed, include_time=tm.config.include_time_model,
-                time0=float(self.iter_ctrl), first_candidate=first, **kw)
-        if not np.isfinite(best_J):
-            raise FloatingPointError("no finite objective among the candidates")
-        self.num_rollouts += B * int(cc.cem_iterations)
-        out = self.evaluate_candidates(best_x[None], state_mu, state_var, trajectories=True)
-        self._cache_trajectory(out, 0)
-        self.best_candidate_J = best_J
-        self.actions_mpc_previous_iter = best_x.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
+    def _adopt(self, result):
+        """Publish a search's winner (candidate_search.SearchResult): the diagnostics, the logging caches, the warm start of the
+        next step; returns the winning sequence in model space."""
+        for name, value in (result.diagnostics or {}).items():
+            setattr(self, name, value)
+        if result.index is not None:
+            self.best_candidate_index = result.index
+        if result.J is not None:
+            self.best_candidate_J = result.J
+        self.num_rollouts += result.rollouts
+        kind = result.cache[0] if result.cache else None
+        if kind == "evaluate":
+            self._cache_trajectory(self.evaluate_candidates(result.x[None], *result.cache[1:], trajectories=True), 0)
+        elif kind == "out":
+            self._cache_trajectory(*result.cache[1:])
+        elif kind == "packed":
+            self._cache_packed_trajectory(result.cache[1], self.config.controller.len_horizon, self.transition_model.dim_state)
+        self.actions_mpc_previous_iter = result.x.copy()
+        return self.actions_mapper.transform_action_mpc_to_action_model(result.x)
 
     def objective_and_gradient_batch(self, actions_mpc_batch, obs_mu, obs_var):
         """(B, H*A) optimiser vectors -> (J (B,), dJ/d(actions_mpc) (B, H*A)) in one gpmpc_rollout_grad launch."""
@@ -592,222 +406,6 @@ class GpMpcController(BaseControllerObject):
                 return host["J"].numpy(), self.actions_mapper.chain_grad_model_to_mpc_batch(host["grad"].numpy())
         J, g_model, _ = self._objective_and_gradient_by_differences(acts, obs_mu, obs_var)
         return J, self.actions_mapper.chain_grad_model_to_mpc_batch(g_model)
-
-    def _batched_lbfgs_search(self, state_mu, state_var):
-        """All restarts at once.  The reference runs `restarts_optim` scipy L-BFGS-B solves one after
-        the other, every function evaluation a forward + autograd backward of ONE sequence (:125-141).  Here the same
-        scipy solver runs once per restart, each in its own thread, but the threads advance in lockstep: whenever every
-        unfinished restart is waiting for an evaluation, ONE objective + analytic-gradient launch serves them all.  Each
-        restart therefore sees exactly the values the sequential loop would hand it (the kernels are bitwise independent
-        of the batch composition), ends at the same point, and the keep-the-best rule (:146-148) picks the same winner;
-        the wall time is that of the longest restart instead of their sum."""
-        import threading
-        cc = self.config.controller
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        B = int(cc.lbfgs_candidates or cc.restarts_optim)
-        x0s = []
-        for b in range(B):
-            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and b == 0:
-                x0s.append(generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A))
-            else:
-                x0s.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
-        # restarts sharded over the ranks (one process per GPU): every rank drew the SAME B starting points above (numpy's
-        # global generator, seeded identically by the launcher) and solves its contiguous slice; the winners meet in ONE
-        # all_gather of [fun, restart index, solution] below
-        from ... import sharding
-        world, rank = self._ranks()
-        if world > 1:
-            # rank 0's starting points on every rank (one small broadcast per control step instead of trusting the launcher's seeds)
-            x0s = list(sharding.broadcast_from_first(np.stack(x0s), self.transition_model.engine.device, self.process_group))
-        r_lo, r_hi = sharding.shard_bounds(B, world, rank)
-        B_all, x0s, B = B, x0s[r_lo:r_hi], r_hi - r_lo
-        cond = threading.Condition()
-        pending, results, state = {}, {}, {"running": B, "launches": 0, "error": None}
-
-        def flush():                                   # called with the lock held, by the last thread to arrive
-            idx = sorted(pending)
-            J, G = np.full(len(idx), np.nan), np.zeros((len(idx), H * A))
-            try:
-                J, G = self.objective_and_gradient_batch(np.stack([pending[i] for i in idx]), state_mu, state_var)
-            except BaseException as e:                 # every waiting restart is served -- nobody may wait forever ...
-                state["error"] = e if isinstance(e, Exception) else RuntimeError(repr(e))
-                if not isinstance(e, Exception):       # ... and KeyboardInterrupt / SystemExit go on in the flushing thread
-                    raise
-            finally:
-                state["launches"] += 1
-                for k, i in enumerate(idx):
-                    results[i] = (float(J[k]), G[k].copy())
-                pending.clear()
-                cond.notify_all()
-
-        def make_fun(i):
-            def fun(x):
-                with cond:
-                    pending[i] = np.array(x, dtype=np.float64)
-                    if len(pending) == state["running"]:
-                        flush()
-                    waited = 0.0
-                    while i not in results:
-                        # a rendezvous that never completes (a sibling died outside `worker`'s bookkeeping) must not hang the step
-                        if not cond.wait(timeout=5.0):
-                            waited += 5.0
-                            if waited >= 600.0:
-                                pending.pop(i, None)
-                                raise TimeoutError(f"lockstep evaluation of restart {i} not served within 600 s")
-                    out = results.pop(i)
-                if state["error"] is not None:
-                    raise RuntimeError("batched evaluation failed") from state["error"]
-                return out
-            return fun
-
-        solved = [None] * B
-
-        def worker(i):
-            try:
-                solved[i] = minimize(fun=make_fun(i), x0=x0s[i], jac=True, method="L-BFGS-B",
-                                     bounds=self.actions_mapper.bounds, options=cc.actions_optimizer_params)
-            except BaseException as e:
-                solved[i] = e
-            finally:
-                with cond:
-                    state["running"] -= 1
-                    if pending and len(pending) == state["running"]:
-                        flush()
-
-        threads = [threading.Thread(target=worker, args=(i,), daemon=True) for i in range(B)]
-        for th in threads:
-            th.start()
-        for th in threads:
-            th.join()
-        failure = next((r for r in solved if isinstance(r, BaseException)), None)
-        if failure is not None and world == 1:
-            raise failure
-        # world > 1: a rank whose solves failed must still enter the collective below (the others would wait in it until the
-        # watchdog fires); its record carries an error flag and every rank raises after the gather
-        self.lbfgs_evaluations = state["launches"]
-        self.candidates_final_J = None if failure is not None else np.array([r.fun for r in solved])
-        opt_fun, best, best_i = np.inf, None, -1
-        for i, res in enumerate(solved if failure is None else []):     # the reference's keep-the-best rule, in restart order
-            if res.fun < opt_fun or (best is None and np.isnan(res.fun)):
-                opt_fun, best, best_i = res.fun, res.x, r_lo + i
-        if world > 1:
-            # a NaN adopted by a rank whose slice does not start at restart 0 must not win (reference rule: only the FIRST
-            # restart's NaN is adopted) -- such a slice contributes its best finite result, or nothing
-            if best is not None and np.isnan(opt_fun) and best_i != 0:
-                opt_fun, best, best_i = np.inf, None, -1
-                for i, res in enumerate(solved):
-                    if res.fun < opt_fun:
-                        opt_fun, best, best_i = res.fun, res.x, r_lo + i
-            n = H * A
-            rec = torch.zeros(2 + n + 2, dtype=F64)     # [fun | restart | solution | error flag | state checksum]
-            rec[0], rec[1] = (float(opt_fun), float(best_i)) if best is not None else (float("inf"), -1.0)
-            if best is not None:
-                rec[2:2 + n] = torch.as_tensor(np.asarray(best, dtype=np.float64))
-            rec[2 + n] = 0.0 if failure is None else 1.0
-            rec[3 + n] = self._state_checksum(state_mu, state_var)
-            dev = self.transition_model.engine.device
-            _, flat = sharding._gather_records(rec.to(dev), self.process_group)
-            host = flat.cpu().view(world, 4 + n)
-            if failure is not None:
-                raise failure
-            failed = [r for r in range(world) if float(host[r, 2 + n]) != 0.0]
-            if failed:
-                raise RuntimeError(f"lockstep L-BFGS restarts: the solves of rank(s) {failed} failed; no winner this step")
-            self._assert_ranks_agree(host[:, 3 + n], "the state")
-            opt_fun, best_i, win = sharding._winner_of(host, world, n, 1)
-            best = win.numpy().reshape(-1).copy()
-            self.candidates_final_J = None             # only this rank's slice was solved here
-        self.best_candidate_index, self.best_candidate_J = best_i, float(opt_fun)
-        out = self.evaluate_candidates(best[None], state_mu, state_var, trajectories=True)
-        self._cache_trajectory(out, 0)
-        self.actions_mpc_previous_iter = best.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best)
-
-    def _device_lbfgs_search(self, state_mu, state_var):
-        """candidate_optimizer = "lbfgs_device": a box-constrained L-BFGS from `lbfgs_candidates` starts whose whole loop stays on
-        the GPU (gpmpc_lbfgs_search: per iteration one objective + analytic-gradient launch over the restarts' trial points and
-        one step kernel; the line search is spread over iterations, so nothing is read back until the winner).  The starts are
-        those `_batched_lbfgs_search` draws (same generator order, the shifted previous solution in slot 0).  Two host
-        synchronisations per control step: the winner, then its trajectory for the logging caches.  Works for both uncertainty
-        propagations (open loop); the restarts are not sharded over ranks."""
-        cc = self.config.controller
-        world, _ = self._ranks()
-        if world > 1:                                  # every rank raises here, before any collective
-            raise ValueError("candidate_optimizer='lbfgs_device' does not shard its restarts over ranks: switch "
-                             "ControllerConfig.shard_over_ranks off (every rank then runs the whole search)")
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        B = int(cc.lbfgs_candidates or cc.restarts_optim)
-        iterations = int(cc.lbfgs_device_iterations)
-        x0s = []
-        for b in range(B):
-            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and b == 0:
-                x0s.append(generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A))
-            else:
-                x0s.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
-        self.lbfgs_device_starts = np.stack(x0s).astype(np.float64).reshape(B, H * A)
-        kw = {}
-        if isinstance(self.actions_mapper, DerivativeActionMapper):
-            kw = dict(max_change=np.asarray(self.config.actions.max_change_action_norm, dtype=np.float64),
-                      action_prev=self.actions_mapper.action_model_previous_iter.numpy())
-        tm = self.transition_model
-        tm.set_cost(self.config.reward)
-        best_x, best_J, J_all, status = tm.engine.lbfgs_search_host(
-            self.lbfgs_device_starts, np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), H, A,
-            iterations, history=int(cc.lbfgs_device_history),
-            propagation="linearized" if tm.propagation() == "linearized" else "moment",
-            include_time=tm.config.include_time_model, time0=float(self.iter_ctrl), **kw)
-        if not np.isfinite(best_J):
-            raise FloatingPointError("no finite objective among the restarts")
-        self.num_rollouts += B * iterations
-        self.lbfgs_evaluations = iterations
-        self.candidates_final_J, self.candidates_final_status = J_all, status
-        best_i = int(np.flatnonzero(J_all == best_J)[0])          # the first strict minimum: gpmpc_argmin's rule
-        self.best_candidate_index, self.best_candidate_J = best_i, float(best_J)
-        out = self.evaluate_candidates(best_x[None], state_mu, state_var, trajectories=True)
-        self._cache_trajectory(out, 0)
-        self.actions_mpc_previous_iter = best_x.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
-
-    def _device_ilqr_search(self, state_mu, state_var):
-        """candidate_optimizer = "ilqr_device": a clamped iLQR on the mean dynamics of the linearised propagation from
-        `ilqr_candidates` starts whose whole loop stays on the GPU (gpmpc_ilqr_search: per iteration a backward Riccati sweep along
-        each candidate's nominal trajectory, a closed-loop forward pass for every step size of the line search, an accept rule;
-        nothing is read back until the winner).  The design is certainty-equivalent; the winner is chosen by the LCB objective of
-        gpmpc_rollout_linear.  The starts are those `_device_lbfgs_search` draws (same generator order, the shifted previous
-        solution in slot 0).  Two host synchronisations per control step: the winner, then its trajectory for the logging caches.
-        Linearised propagation, open loop and the normalisation mapper only; the starts are not sharded over ranks."""
-        cc = self.config.controller
-        world, _ = self._ranks()
-        if world > 1:                                  # every rank raises here, before any collective
-            raise ValueError("candidate_optimizer='ilqr_device' does not shard its starts over ranks: switch "
-                             "ControllerConfig.shard_over_ranks off (every rank then runs the whole search)")
-        H, A = cc.len_horizon, self.actions_mapper.dim_action
-        B = int(cc.ilqr_candidates or cc.restarts_optim)
-        iterations = int(cc.ilqr_iterations)
-        x0s = []
-        for b in range(B):
-            if cc.init_from_previous_actions and self.actions_mpc_previous_iter is not None and b == 0:
-                x0s.append(generate_mpc_action_init_frompreviousiter(self.actions_mpc_previous_iter, dim_action=A))
-            else:
-                x0s.append(generate_mpc_action_init_random(len_horizon=H, dim_action=A))
-        self.ilqr_device_starts = np.stack(x0s).astype(np.float64).reshape(B, H * A)
-        tm = self.transition_model
-        tm.set_cost(self.config.reward)
-        best_x, best_J, J_all, status = tm.engine.ilqr_search_host(
-            self.ilqr_device_starts, np.asarray(state_mu, dtype=np.float64), np.asarray(state_var, dtype=np.float64), H, A,
-            iterations, line_search_steps=int(cc.ilqr_line_search_steps), reg0=float(cc.ilqr_reg),
-            include_time=tm.config.include_time_model, time0=float(self.iter_ctrl))
-        if not np.isfinite(best_J):
-            raise FloatingPointError("no finite objective among the starts")
-        self.num_rollouts += B * iterations * (1 + int(cc.ilqr_line_search_steps))
-        self.ilqr_iterations_run = iterations
-        self.candidates_final_J, self.candidates_final_status = J_all, status
-        best_i = int(np.flatnonzero(J_all == best_J)[0])          # the first strict minimum: gpmpc_argmin's rule
-        self.best_candidate_index, self.best_candidate_J = best_i, float(best_J)
-        out = self.evaluate_candidates(best_x[None], state_mu, state_var, trajectories=True)
-        self._cache_trajectory(out, 0)
-        self.actions_mpc_previous_iter = best_x.copy()
-        return self.actions_mapper.transform_action_mpc_to_action_model(best_x)
 
     def _get_random_actions(self, state_mu, state_var):
         """Reference :155-163: one random sequence, evaluated only to fill the logging caches."""

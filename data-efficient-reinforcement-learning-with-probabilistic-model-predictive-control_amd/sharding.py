@@ -324,6 +324,121 @@ def select_best_on_device(engine, J, actions_local, lo, num_candidates, group=No
     return bJ, bi, win, host[:, 2 + H * A:].clone()
 
 
+def state_checksum(state_mu, state_var):
+    """One double that differs between ranks whose (state, state variance) differ: travels inside the winner records."""
+    a = np.concatenate([np.asarray(state_mu, dtype=np.float64).ravel(), np.asarray(state_var, dtype=np.float64).ravel()])
+    w = np.cos(np.arange(1, a.size + 1, dtype=np.float64))           # position-dependent weights: permutations differ too
+    return float(np.dot(a, w))
+
+
+def _assert_ranks_agree(column, what):
+    if not bool((column == column[0]).all()):
+        raise RuntimeError(f"candidate sharding: the ranks disagree on {what} ({column.tolist()}); every rank must see the "
+                           "same observation and seed numpy identically (or switch ControllerConfig.shard_over_ranks off)")
+
+
+def keep_best(results, first_index=0, adopt_nan=True):
+    """The reference's keep-the-best rule (gp_mpc_controller.py:146-148) over `results` = [(fun, x), ...] in restart order, the
+    first of them restart `first_index`: (fun, x, restart index) of the lowest fun, the first one on ties; a NaN is adopted only
+    while nothing else has been (and never with adopt_nan=False).  (inf, None, -1) when nothing is selectable."""
+    opt_fun, best, best_i = np.inf, None, -1
+    for i, (fun, x) in enumerate(results):
+        if fun < opt_fun or (adopt_nan and best is None and np.isnan(fun)):
+            opt_fun, best, best_i = fun, x, first_index + i
+    return opt_fun, best, best_i
+
+
+def shooting_exchange(engine, out, local, lo, num_candidates, dim_state, state_mu, state_var, cands, failure=None, group=None):
+    """The whole exchange of a sharded random-shooting step, ONE all_gather.  `out`: the rollout of this rank's slice (None: an
+    empty slice, or the slice failed with `failure`); `local` (n, H, A): the slice's sequences, whose first global index is
+    `lo`; `cands`: all `num_candidates` drawn optimiser vectors.  Every rank's record is
+
+        [best J | global index | winning (H*A) sequence | last trajectory | error flag | state checksum | candidates checksum]
+
+    where "last trajectory" is [mu, Sig, cost_mu, cost_var, J] of the LAST global candidate, filled in by its owner (zeros
+    elsewhere): what the reference leaves in its logging caches (gp_mpc_controller.py:279-283) and get_action reads on every
+    rank.  The two checksums must be the same on every rank, or the union of the slices is not the single-GPU population.
+    A rank that failed locally still enters the collective and raises `failure` after it; the others raise for its flag.
+    Returns (best J, best global index, winning (H, A) host tensor, the packed last trajectory)."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    H, D = local.shape[1], dim_state
+    last_owner = owner_of(num_candidates - 1, num_candidates, world)
+    if rank == last_owner and out is not None:
+        extra = torch.cat([out[k][-1].reshape(-1) for k in ("mu", "Sig", "cost_mu", "cost_var")] + [out["J"][-1:]])
+    else:
+        extra = torch.zeros((H + 1) * (D + D * D + 2) + 1, dtype=torch.float64, device=engine.device)
+    sums = torch.tensor([0.0 if failure is None else 1.0, state_checksum(state_mu, state_var),
+                         float(np.dot(cands.ravel(), np.cos(np.arange(cands.size))))], dtype=torch.float64, device=engine.device)
+    J, best, win, extras = select_best_on_device(engine, None if out is None else out["J"], local, lo, num_candidates,
+                                                 extra=torch.cat([extra, sums]), group=group, raise_if_none=False)
+    if failure is not None:
+        raise failure
+    failed = [r for r in range(world) if float(extras[r, -3]) != 0.0]
+    if failed:
+        raise RuntimeError(f"random shooting: the slice of rank(s) {failed} failed; no winner this step")
+    _assert_ranks_agree(extras[:, -2], "the state")
+    _assert_ranks_agree(extras[:, -1], "the drawn candidates")
+    if win is None:
+        raise FloatingPointError("no selectable candidate (all objectives NaN)")
+    return J, best, win, extras[last_owner][:-3]
+
+
+def restart_winner_exchange(results, first_index, n, state_mu, state_var, device, failure=None, group=None):
+    """The winner of lockstep restarts sharded over the ranks, ONE all_gather.  `results` = [(fun, x), ...] of this rank's
+    restarts in order, the first of them restart `first_index` (empty when its solves failed with `failure`).  Every rank's
+    record is
+
+        [fun | restart index | solution (n) | error flag | state checksum]
+
+    of its slice's best by `keep_best` -- except that a NaN adopted by a slice that does not start at restart 0 must not win
+    (reference rule: only the FIRST restart's NaN is adopted): such a slice contributes its best finite result, or nothing.
+    A rank that failed locally still enters the collective and raises `failure` after it; the others raise for its flag.
+    Returns (fun, restart index, solution (n,) numpy) of the global winner."""
+    opt_fun, best, best_i = keep_best(results, first_index)
+    if best is not None and np.isnan(opt_fun) and best_i != 0:
+        opt_fun, best, best_i = keep_best(results, first_index, adopt_nan=False)
+    rec = torch.zeros(2 + n + 2, dtype=torch.float64)
+    rec[0], rec[1] = (float(opt_fun), float(best_i)) if best is not None else (float("inf"), -1.0)
+    if best is not None:
+        rec[2:2 + n] = torch.as_tensor(np.asarray(best, dtype=np.float64))
+    rec[2 + n] = 0.0 if failure is None else 1.0
+    rec[3 + n] = state_checksum(state_mu, state_var)
+    world, flat = _gather_records(rec.to(device), group)
+    host = flat.cpu().view(world, 4 + n)
+    if failure is not None:
+        raise failure
+    failed = [r for r in range(world) if float(host[r, 2 + n]) != 0.0]
+    if failed:
+        raise RuntimeError(f"lockstep L-BFGS restarts: the solves of rank(s) {failed} failed; no winner this step")
+    _assert_ranks_agree(host[:, 3 + n], "the state")
+    opt_fun, best_i, win = _winner_of(host, world, n, 1)
+    return opt_fun, best_i, win.numpy().reshape(-1).copy()
+
+
+def cem_head_exchange(seed, first, state_mu, state_var, n, device, group=None):
+    """What a sharded "cem_device" step must hold identically on every rank, as rank 0 has it (ONE small broadcast per control
+    step: the union of the slices is the single-GPU population only then):
+
+        [seed >> 31 | seed & 0x7fffffff | 1 if a starting vector follows | starting vector (n; zeros without) | state | state variance]
+
+    The ranks must sit at the SAME state (the other searches verify it inside their exchange): each compares its own with rank
+    0's, and the verdict is taken by all ranks together (one rank raising alone would leave the others in the search's
+    collectives).  Returns (seed, first, state_mu, state_var) of rank 0, in the shapes given."""
+    nmu = np.asarray(state_mu).size
+    head = np.concatenate([[float(seed >> 31), float(seed & 0x7fffffff), 1.0 if first is not None else 0.0],
+                           np.zeros(n) if first is None else np.asarray(first, dtype=np.float64).ravel(),
+                           np.asarray(state_mu, dtype=np.float64).ravel(), np.asarray(state_var, dtype=np.float64).ravel()])
+    mine = state_checksum(state_mu, state_var)
+    head = broadcast_from_first(head, device, group)
+    theirs = state_checksum(head[3 + n:3 + n + nmu], head[3 + n + nmu:])
+    if any_rank(mine != theirs, device, group):
+        raise RuntimeError("candidate sharding: the ranks disagree on the state; every rank must see the same observation "
+                           "(or switch ControllerConfig.shard_over_ranks off)")
+    seed = (int(head[0]) << 31) | int(head[1])
+    first = head[3:3 + n].copy() if head[2] != 0.0 else None
+    return seed, first, head[3 + n:3 + n + nmu].reshape(np.shape(state_mu)), head[3 + n + nmu:].reshape(np.shape(state_var))
+
+
 def sharded_cem_search(engine, mu0, S0, B_total, H, A, iterations, n_elite, seed, group=None, include_time=False, time0=0.0,
                        first_candidate=None, max_change=None, action_prev=None, noise=None):
     """The device-resident cross-entropy search (HipEngine.cem_search) with its candidates sharded over the ranks: per

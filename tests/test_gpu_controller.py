@@ -152,7 +152,7 @@ def test_lbfgsb_path_improves_objective(engine):
 def test_device_resident_search_matches_a_host_loop_on_the_same_draws(engine, deriv):
     """gpmpc_cem_search keeps sampling, action mapper, elite selection and refit on the GPU.  Fed the SAME draws through
     its noise hook, it must reproduce a plain numpy loop around gpmpc_rollout (same keep-the-incumbent, clip, stable
-    elite order, population std + 1e-3, NaN -> inf rules as GpMpcController._cross_entropy_search): same winner, same
+    elite order, population std + 1e-3, NaN -> inf rules as candidate_search.cross_entropy): same winner, same
     objective; mean / std differ only by summation order."""
     g = load("lcb_grad_deriv" if deriv else "lcb_grad_norm")
     w = workload_of(g)

@@ -716,7 +716,7 @@ int gpmpc_cem_merge(gpmpc_t* g, const double* elites_dev, int lists, int n_elite
 // Device-resident L-BFGS (lbfgs_search.hip).  The mapper's parameters travel in the kernels' argument blocks.
 // the checks the three entry points share; on success `mp` holds the mapper's parameters
 static int lbfgs_entry_checks(gpmpc_t* g, int B, int H, int A, int history, int mapper, const double* max_change,
-                              const double* action_prev, LbfgsMapper& mp) {
+                              const double* action_prev, ActionMapper& mp) {
     bool limit = false;
     const char* msg = lbfgs_check_shape(B, H, A, history, limit);
     if (!msg) msg = lbfgs_check_mapper(mapper, A, max_change != nullptr, action_prev != nullptr, limit);
@@ -741,7 +741,7 @@ int gpmpc_lbfgs_init(gpmpc_t* g, const double* x0_dev, int B, int H, int A, int 
     Range roctx_range("gpmpc_lbfgs_init");
     if (!g) return GPMPC_ERR_ARG;
     if (!x0_dev || !state_dev) return bad(g, "null argument");
-    LbfgsMapper mp;
+    ActionMapper mp;
     int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
     if (rc) return rc;
     GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
@@ -754,7 +754,7 @@ int gpmpc_lbfgs_step(gpmpc_t* g, const double* J_dev, const double* grad_model_d
     Range roctx_range("gpmpc_lbfgs_step");
     if (!g) return GPMPC_ERR_ARG;
     if (!J_dev || !grad_model_dev || !state_dev) return bad(g, "null argument");
-    LbfgsMapper mp;
+    ActionMapper mp;
     int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
     if (rc) return rc;
     if (const char* msg = lbfgs_check_step(iteration, c1, pgtol)) return bad(g, msg);
@@ -771,7 +771,7 @@ int gpmpc_lbfgs_search(gpmpc_t* g, const double* mu0, const double* S0, int B, i
     if (!state_dev || (first_iteration == 0 && !x0_dev)) return bad(g, "null argument");
     Handle* h = H_(g);
     if (!h->ready) return bad(g, "search before prepare / set_factors");
-    LbfgsMapper mp;
+    ActionMapper mp;
     int rc = lbfgs_entry_checks(g, B, H, A, history, mapper, max_change, action_prev, mp);
     if (rc) return rc;
     if (const char* msg = lbfgs_check_step(first_iteration, c1, pgtol)) return bad(g, msg);

@@ -1,5 +1,5 @@
 // device_common.h -- device primitives shared by the kernel families: wavefront reductions and the LDS hand-off, the table
-// exponential, the fp64 matrix-instruction helpers and the numbering of upper-triangle entries.
+// exponential, the fp64 matrix-instruction helpers, the searches' clip01 / finite_d and the numbering of upper-triangle entries.
 #pragma once
 #include "gpmpc_internal.h"
 #include <type_traits>
@@ -194,6 +194,11 @@ __device__ inline void mfma_kloop(d4& acc, int pbeg, int pend, int lk, FA loadA,
         for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
     }
 }
+
+// ------------------------------------------------------------------------------------------
+// The searches' scalar helpers.  clip01 sends NaN to 0 (fmax drops it); ilqr_clip01 (ilqr.hip) lets NaN through on purpose.
+__device__ inline double clip01(double v) { return fmin(fmax(v, 0.0), 1.0); }
+__device__ inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
 
 // ------------------------------------------------------------------------------------------
 // Upper-triangle entries (d, e), d <= e < D, numbered row by row: (0,0) (0,1) .. (0,D-1) (1,1) ..

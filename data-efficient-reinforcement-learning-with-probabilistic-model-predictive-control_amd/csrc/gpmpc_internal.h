@@ -173,6 +173,13 @@ struct RolloutArgs {
     double S0[kMaxD * kMaxD];
 };
 
+// the searches' launches: the objective J (B) of `actions` (B, H, A) and nothing else
+inline void rollout_objective_only(RolloutArgs& a, const double* actions, double* J) {
+    a.actions = actions;
+    a.J_out = J;
+    a.mu_out = nullptr; a.Sig_out = nullptr; a.cm_out = nullptr; a.cv_out = nullptr;
+}
+
 // A device buffer that only ever grows.
 struct Buf {
     double* p = nullptr;
@@ -204,7 +211,7 @@ struct Handle {
     Buf mllws;    // marginal-likelihood workspace: tile partial sums | results
     Buf mllbws;   // gpmpc_mll_batch: per problem of one chunk K -> L | L^-1 | iK (N, N each) | z | beta (N each) (mll_batch.hip)
     Buf trainws;  // gpmpc_train_search: loss (R D) | d loss / d x (R D, E + 2) of the trial points
-    Buf cemws;    // cross-entropy search workspace: optimiser vectors | model actions | J | mean | std | warm start | mapper
+    Buf cemws;    // cross-entropy search workspace: optimiser vectors | model actions | J | warm start | mean | std
     Buf tilews;   // batch-major path: step records of the candidates | per-tile partial sums | hand-over flags
     Buf tgradws;  // gradient's tile pass: records of a block of (candidate, step) items | per-tile partial moments
     Buf predws;   // gpmpc_predict: per-(query row, column block) partial sums of one chunk of query rows
@@ -593,13 +600,13 @@ int run_cem_merge(Handle* h, const double* elites_dev, int lists, int n_elite, i
 // lbfgs_search.hip: box-constrained L-BFGS over B restarts in lockstep whose loop stays on the device (lbfgs_state.h: the state
 // buffer and the argument checks).  `a` as fill_args leaves it (actions / J_out are set inside); propagation 0 moment matching,
 // 1 linearised; best_out_dev [J | restart | x (n)] or NULL
-struct LbfgsMapper;
-int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int history, const LbfgsMapper& mp, double* state_dev,
+struct ActionMapper;
+int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int history, const ActionMapper& mp, double* state_dev,
                    hipStream_t s);
 int run_lbfgs_step(Handle* h, const double* J_dev, const double* grad_model_dev, int B, int H, int A, int iteration, int history,
-                   double c1, double pgtol, const LbfgsMapper& mp, double* state_dev, hipStream_t s);
+                   double c1, double pgtol, const ActionMapper& mp, double* state_dev, hipStream_t s);
 int run_lbfgs_search(Handle* h, RolloutArgs& a, int propagation, int first_iteration, int iterations, int history, double c1,
-                     double pgtol, const LbfgsMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
+                     double pgtol, const ActionMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
                      hipStream_t s);
 // ilqr.hip: clamped iLQR on the mean dynamics of the linearised propagation, B candidates in lockstep (ilqr_state.h: the state buffer
 // and the argument checks; validated by the entry points).  backward: gains (B, H, A, D), feed-forward (B, H, A), nominal trajectory

@@ -30,8 +30,6 @@ namespace {
 // NaN stays NaN (fmin / fmax would turn it into a bound): a non-finite start must reach the cost
 __device__ inline double ilqr_clip01(double v) { return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }
 
-__device__ inline bool ilqr_finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
-
 struct IlqrForwardArgs {
     const double* actions;   // (cands, H, A) nominal, of this chunk
     const double* gains;     // (cands, H, A, D)
@@ -121,7 +119,7 @@ __global__ __launch_bounds__(64) void ilqr_accept_kernel(const IlqrAcceptArgs p)
     double* st = p.state;
     if (st[Y.status + b] != 0.0) return;              // (uniform) a finished candidate: its state no longer changes
     const double cost = st[Y.cost + b];
-    if (!ilqr_finite_d(cost)) {
+    if (!finite_d(cost)) {
         if (lane == 0) { st[Y.status + b] = 3.0; st[Y.chosen + b] = -1.0; }
         return;
     }
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(64) void ilqr_accept_kernel(const IlqrAcceptArgs p)
     double bestc = 0.0;
     for (int l = 0; l < p.L; ++l) {                   // the finite trial of lowest cost, ties to the smallest l
         const double c = tc[l];
-        if (ilqr_finite_d(c) && (best < 0 || c < bestc)) { best = l; bestc = c; }
+        if (finite_d(c) && (best < 0 || c < bestc)) { best = l; bestc = c; }
     }
     const double reg = st[Y.reg + b];
     if (best >= 0 && bestc < cost) {
@@ -327,9 +325,7 @@ int run_ilqr_search(Handle* h, RolloutArgs& a, int iterations, int L, double reg
         if (rc) return rc;
     }
     // the library's LCB objective of the final sequences: gpmpc_rollout_linear's launches, J only
-    a.actions = st + Y.actions;
-    a.J_out = st + Y.J;
-    a.mu_out = nullptr; a.Sig_out = nullptr; a.cm_out = nullptr; a.cv_out = nullptr;
+    rollout_objective_only(a, st + Y.actions, st + Y.J);
     rc = run_rollout_linear(h, a, s);
     if (rc) return rc;
     if (best_out_dev) return launch_argmin_to(h, st + Y.J, B, 0, st + Y.actions, H * A, best_out_dev, nullptr, s);

@@ -8,7 +8,7 @@
 //
 // lbfgs_step_kernel: one wavefront per restart, lanes stride over the n coordinates, every dot product is a lane's serial sum over
 // its coordinates followed by wave_sum -- an order fixed by n alone, so a restart's bits depend neither on B nor on its slot.  The
-// mapper's sum over the horizon runs on one lane per action dimension, in the order of cem_map_kernel (search.hip).  No atomics,
+// mapper's sum over the horizon runs on one lane per action dimension (action_mapper.h, shared with search.hip).  No atomics,
 // nothing waits for another workgroup.  LDS: gt (n) | q (n) | the recursion's coefficients (history).
 #include "device_common.h"
 #include "lbfgs_state.h"
@@ -23,39 +23,37 @@ struct LbfgsStepArgs {
     double* state;
     int B, H, A, m, k;
     double c1, pgtol;
-    LbfgsMapper mp;
+    ActionMapper mp;
 };
 
 struct LbfgsInitArgs {
     const double* x0;      // (B, n)
     double* state;
     int B, H, A, m;
-    LbfgsMapper mp;
+    ActionMapper mp;
 };
-
-__device__ inline double clip01(double v) { return fmin(fmax(v, 0.0), 1.0); }
 
 __device__ inline double wave_max(double v) {
     for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
     return v;
 }
 
-__device__ inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
-
-// optimiser vector (LDS) -> model actions; the running sum is not clamped, its output is (cem_map_kernel's order)
-__device__ inline void lbfgs_map(int lane, int H, int A, const LbfgsMapper& mp, const double* xt, double* actions) {
+// optimiser vector (LDS) -> model actions, and the gradient back: one lane per action dimension (action_mapper.h); the identity is
+// a plain copy, which all lanes share
+__device__ inline void lbfgs_map(int lane, int H, int A, const ActionMapper& mp, const double* xt, double* actions) {
     if (mp.mapper == 0) {
         for (int i = lane; i < H * A; i += kWave) actions[i] = xt[i];
         return;
     }
-    for (int a = lane; a < A; a += kWave) {
-        const double mc = mp.max_change[a];
-        double s = mp.action_prev[a];
-        for (int t = 0; t < H; ++t) {
-            s += xt[t * A + a] * 2.0 * mc - mc;
-            actions[t * A + a] = clip01(s);
-        }
+    for (int a = lane; a < A; a += kWave) map_actions(mp, a, H, A, xt + a, actions + a);
+}
+
+__device__ inline void lbfgs_map_backward(int lane, int H, int A, const ActionMapper& mp, const double* G, double* gt) {
+    if (mp.mapper == 0) {
+        for (int i = lane; i < H * A; i += kWave) gt[i] = G[i];
+        return;
     }
+    for (int a = lane; a < A; a += kWave) map_actions_backward(mp, a, H, A, G + a, gt + a);
 }
 
 __global__ __launch_bounds__(64) void lbfgs_init_kernel(const LbfgsInitArgs p) {
@@ -110,19 +108,7 @@ __global__ __launch_bounds__(64) void lbfgs_step_kernel(const LbfgsStepArgs p) {
     double* coef = lds + 2 * (size_t)n;
 
     // 1. chain rule
-    const double* G = p.G + bn;
-    if (p.mp.mapper == 0) {
-        for (int i = lane; i < n; i += kWave) gt[i] = G[i];
-    } else {
-        for (int a = lane; a < A; a += kWave) {
-            const double two_m = 2.0 * p.mp.max_change[a];
-            double acc = 0.0;
-            for (int t = H - 1; t >= 0; --t) {
-                acc += G[t * A + a];
-                gt[t * A + a] = two_m * acc;
-            }
-        }
-    }
+    lbfgs_map_backward(lane, H, A, p.mp, p.G + bn, gt);
     wave_lds_sync();
 
     // 2. accept or reject
@@ -263,7 +249,7 @@ int launch_step(Handle* h, const LbfgsStepArgs& p, hipStream_t s) {
 
 }  // namespace
 
-int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int history, const LbfgsMapper& mp, double* state_dev,
+int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int history, const ActionMapper& mp, double* state_dev,
                    hipStream_t s) {
     LbfgsInitArgs p;
     p.x0 = x0_dev; p.state = state_dev; p.B = B; p.H = H; p.A = A; p.m = history; p.mp = mp;
@@ -273,7 +259,7 @@ int run_lbfgs_init(Handle* h, const double* x0_dev, int B, int H, int A, int his
 }
 
 int run_lbfgs_step(Handle* h, const double* J_dev, const double* grad_model_dev, int B, int H, int A, int iteration, int history,
-                   double c1, double pgtol, const LbfgsMapper& mp, double* state_dev, hipStream_t s) {
+                   double c1, double pgtol, const ActionMapper& mp, double* state_dev, hipStream_t s) {
     LbfgsStepArgs p;
     p.J = J_dev; p.G = grad_model_dev; p.state = state_dev; p.B = B; p.H = H; p.A = A; p.m = history; p.k = iteration;
     p.c1 = c1; p.pgtol = pgtol; p.mp = mp;
@@ -281,7 +267,7 @@ int run_lbfgs_step(Handle* h, const double* J_dev, const double* grad_model_dev,
 }
 
 int run_lbfgs_search(Handle* h, RolloutArgs& a, int propagation, int first_iteration, int iterations, int history, double c1,
-                     double pgtol, const LbfgsMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
+                     double pgtol, const ActionMapper& mp, const double* x0_dev, double* state_dev, double* best_out_dev,
                      hipStream_t s) {
     const int B = a.B, H = a.H, A = a.A, n = H * A;
     // the gradient launch is planned first: a shape outside its kernels is reported before anything is enqueued or written
@@ -314,9 +300,7 @@ int run_lbfgs_search(Handle* h, RolloutArgs& a, int propagation, int first_itera
         hipLaunchKernelGGL(lbfgs_ones_kernel, dim3((B + 255) / 256), dim3(256), 0, s, ones, B);
         GPMPC_HIP_CHECK(h, hipGetLastError());
     }
-    a.actions = state_dev + L.actions;
-    a.J_out = J;
-    a.mu_out = nullptr; a.Sig_out = nullptr; a.cm_out = nullptr; a.cv_out = nullptr;
+    rollout_objective_only(a, state_dev + L.actions, J);
     for (int it = 0; it < iterations; ++it) {
         RolloutArgs ai = a;
         if (propagation == 0) {

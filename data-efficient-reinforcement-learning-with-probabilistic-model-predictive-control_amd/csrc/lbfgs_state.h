@@ -4,25 +4,13 @@
 #pragma once
 #include <cstddef>
 
-#if defined(__HIPCC__)
-#define LBFGS_HD __host__ __device__
-#else
-#define LBFGS_HD
-#endif
+#include "action_mapper.h"
 
 namespace gpmpc_hip {
 
 constexpr int kLbfgsMaxB = 4096;
 constexpr int kLbfgsMaxN = 4096;
 constexpr int kLbfgsMaxHistory = 32;
-constexpr int kLbfgsMaxMapperA = 24;         // the derivative mapper's parameters ride in the kernel argument block
-
-// the derivative mapper's parameters, by value in the kernel argument block (mapper 0: unused)
-struct LbfgsMapper {
-    int mapper;
-    double max_change[kLbfgsMaxMapperA];
-    double action_prev[kLbfgsMaxMapperA];
-};
 
 // Offsets in doubles: x | g | d | xt | actions (B, n each) | J | alpha | status | pushes (B each) | S | Y (B, m, n) | sy | yy (B, m)
 struct LbfgsLayout {
@@ -30,7 +18,7 @@ struct LbfgsLayout {
     size_t x, g, d, xt, actions, J, alpha, status, pushes, S, Y, sy, yy, total;
 };
 
-LBFGS_HD inline LbfgsLayout make_lbfgs_layout(int B, int n, int m) {
+GPMPC_HD inline LbfgsLayout make_lbfgs_layout(int B, int n, int m) {
     LbfgsLayout L;
     L.B = B; L.n = n; L.m = m;
     const size_t Bn = (size_t)B * n, Bm = (size_t)B * m;
@@ -68,7 +56,7 @@ inline const char* lbfgs_check_mapper(int mapper, long long A, bool have_max_cha
     limit = false;
     if (mapper != 0 && mapper != 1) return "lbfgs: mapper must be 0 (identity) or 1 (derivative)";
     if (mapper == 1 && (!have_max_change || !have_action_prev)) return "lbfgs: the derivative mapper needs max_change and the previous action";
-    if (mapper == 1 && A > kLbfgsMaxMapperA) { limit = true; return "lbfgs: the derivative mapper supports A <= 24"; }
+    if (mapper == 1 && A > kMaxMapperA) { limit = true; return "lbfgs: the derivative mapper supports A <= 24"; }
     return nullptr;
 }
 

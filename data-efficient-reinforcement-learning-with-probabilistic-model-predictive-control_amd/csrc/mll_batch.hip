@@ -268,7 +268,7 @@ int run_train_search(Handle* h, const double* X, const double* Y, int N, int D, 
     if (rc) return rc;
     double* J = h->trainws.p;
     double* G = J + P;
-    LbfgsMapper mp;
+    ActionMapper mp;
     mp.mapper = 0;
     const LbfgsLayout L = make_lbfgs_layout(P, n, history);
     if (first_iteration == 0) {

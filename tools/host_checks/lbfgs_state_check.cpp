@@ -1,7 +1,8 @@
 // Stand-alone host check of the state layout and the argument checks of gpmpc_lbfgs_* (csrc/lbfgs_state.h): over a grid of
 // (B, n, history), the limits included, the arrays of the state follow one another without gaps or overlap, and every index the
 // init and step kernels may form for the last restart, the last ring slot and the last coordinate stays inside its array; the
-// checks accept exactly the documented box.  Build with a host sanitizer and run on the CPU:
+// checks accept exactly the documented box; the action mapper they include (csrc/action_mapper.h) stays inside its vectors and its
+// chain rule matches its forward map.  Build with a host sanitizer and run on the CPU:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/host_checks/lbfgs_state_check.cpp -o state_check && ./state_check
 #include <cstdio>
 #include <cstdlib>
@@ -62,7 +63,37 @@ static void one(int B, int n, int m) {
     }
 }
 
+// csrc/action_mapper.h on exactly sized vectors (the sanitizer sees an overrun): the identity copies; the derivative mapper stays in
+// the box, moves by x 2 m - m per step where nothing clamps, and its chain rule is the transpose of that affine map
+static void mapper(int H, int A) {
+    const int n = H * A;
+    ActionMapper mp{};
+    std::vector<double> x(n), out(n, -1.0), G(n), gx(n, -1.0), out2(n);
+    for (int i = 0; i < n; ++i) { x[i] = ((i * 37) % 101) / 100.0; G[i] = ((i * 53) % 17) - 8.0; }
+    for (int a = 0; a < A; ++a) { map_actions(mp, a, H, A, x.data() + a, out.data() + a); map_actions_backward(mp, a, H, A, G.data() + a, gx.data() + a); }
+    CHECK(out == x && gx == G);
+    mp.mapper = 1;
+    for (int a = 0; a < A; ++a) { mp.max_change[a] = 0.4 / H / (a + 1); mp.action_prev[a] = 0.5; }      // |sum of deltas| <= 0.4: no clamp
+    for (int a = 0; a < A; ++a) { map_actions(mp, a, H, A, x.data() + a, out.data() + a); map_actions_backward(mp, a, H, A, G.data() + a, gx.data() + a); }
+    for (int i = 0; i < n; ++i) {
+        const int a = i % A;
+        const double before = i < A ? mp.action_prev[a] : out[i - A], m = mp.max_change[a];
+        CHECK(out[i] > 0.0 && out[i] < 1.0 && std::fabs(out[i] - before - (x[i] * 2.0 * m - m)) < 1e-15);
+        x[i] += 0.125;
+        map_actions(mp, a, H, A, x.data() + a, out2.data() + a);
+        x[i] -= 0.125;
+        double dJ = 0.0;
+        for (int t = 0; t < H; ++t) dJ += G[t * A + a] * (out2[t * A + a] - out[t * A + a]);
+        CHECK(std::fabs(dJ / 0.125 - gx[i]) < 1e-12 * H);
+    }
+    for (int a = 0; a < A; ++a) { mp.max_change[a] = 1.0; mp.action_prev[a] = a % 2; }                   // both clamps
+    for (int a = 0; a < A; ++a) map_actions(mp, a, H, A, x.data() + a, out.data() + a);
+    for (int i = 0; i < n; ++i) CHECK(out[i] >= 0.0 && out[i] <= 1.0);
+}
+
 int main() {
+    for (int H : {1, 3, 13})
+        for (int A : {1, 2, 5, kMaxMapperA}) mapper(H, A);
     const int Bs[] = {1, 2, 65, 4096}, ns[] = {1, 63, 64, 65, 200, 4096}, ms[] = {1, 3, 10, 32};
     int cnt = 0;
     for (int B : Bs)
@@ -95,7 +126,7 @@ int main() {
     for (double c1 : {0.0, 1.0, -0.5, 2.0, nan}) CHECK(lbfgs_check_step(0, c1, 0.0) != nullptr);
     for (double pg : {-1e-300, nan}) CHECK(lbfgs_check_step(0, 1e-4, pg) != nullptr);
     // the mapper's parameters fit the argument block
-    CHECK(sizeof(LbfgsMapper) <= 512);
+    CHECK(sizeof(ActionMapper) <= 512);
     std::printf("%d layouts checked, %d failures\n", cnt, fails);
     return fails ? 1 : 0;
 }

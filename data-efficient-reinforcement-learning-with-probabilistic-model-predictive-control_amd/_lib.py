@@ -71,6 +71,7 @@ SIGNATURES = {
     "gpmpc_rollout_linear_backward": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_rollout_linear_feedback_backward": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P,
                                                          _P, _P]),
+    "gpmpc_rollout_feedback_backward": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_objective_grad_host": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _D, C.POINTER(C.POINTER(_D)), _P]),
     "gpmpc_rollout_timed": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I, C.POINTER(C.c_float), _P]),
     "gpmpc_cem_search": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _D, _I, _I, C.c_ulonglong, _P, _I, _P, _P, _P, _P, _P]),
@@ -94,7 +95,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 def load(path=LIB_PATH):

@@ -620,6 +620,27 @@ class GpStateTransitionModel(AbstractStateTransitionModel):
         return self.engine.rollout_grad(actions, _t(obs_mu).numpy(), _t(obs_var).numpy(), self.config.include_time_model,
                                         float(current_time_idx), trajectories)
 
+    def feedback_objective_and_gradient_batch(self, actions, feedback_gains, obs_mu, obs_var, current_time_idx=0):
+        """The closed-loop counterpart of objective_and_gradient_batch under moment matching (gpmpc_rollout_feedback, then
+        gpmpc_rollout_feedback_backward with J_bar = 1): actions (B,H,A) and `feedback_gains` (model space; (A, D), (H, A, D) or
+        (B, H, A, D)) -> dict of DEVICE tensors J (B,), grad (B,H,A) = dJ/d(actions) and gains_grad = dJ/d(feedback_gains) in the
+        shape of `feedback_gains`: the per-candidate gradients summed the way the gains were broadcast -- over the candidates and
+        steps for (A, D), over the candidates for (H, A, D) (the sum of the candidates' objectives is what such a gain moves).
+        `feedback_gains="lqr"` is a ValueError: no gradient flows through the gain design."""
+        if self._cost_key is None:
+            raise RuntimeError("call set_cost(reward_config) before predicting")
+        if feedback_gains is None or isinstance(feedback_gains, str):
+            raise ValueError(f"feedback_gains must be an array (no gradient flows through a gain design), got {feedback_gains!r}")
+        actions = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions, dtype=F64)
+        gains = torch.as_tensor(feedback_gains if isinstance(feedback_gains, torch.Tensor) else np.asarray(feedback_gains), dtype=F64)
+        out = self.engine.rollout_feedback_grad(actions, gains, _t(obs_mu).numpy(), _t(obs_var).numpy(),
+                                                self.config.include_time_model, float(current_time_idx))
+        if gains.dim() == 2:
+            out["gains_grad"] = out["gains_grad"].sum((0, 1))
+        elif gains.dim() == 3:
+            out["gains_grad"] = out["gains_grad"].sum(0)
+        return out
+
     def objective_and_gradient_host(self, actions, obs_mu, obs_var, current_time_idx=0):
         """ONE sequence (H, A) -> dict of HOST (numpy) arrays J (1,), grad (1,H,A), mu, Sig, cost_mu, cost_var: the shape of call
         scipy's L-BFGS-B makes (gp_mpc_controller.py:133-141, 229-285), served by gpmpc_objective_grad_host with one

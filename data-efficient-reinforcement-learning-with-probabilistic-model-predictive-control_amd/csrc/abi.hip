@@ -92,6 +92,8 @@ const Option kOptions[] = {
      "moments_linear_backward_chunk_points: 0 (auto) or a number of points"},
     {"rollout_feedback_chunk_points", &Handle::opt_rollout_feedback_chunk, 0, kChunkMax, 1,
      "rollout_feedback_chunk_points: 0 (auto) or a number of candidates"},
+    {"rollout_feedback_backward_chunk_points", &Handle::opt_rollout_feedback_bwd_chunk, 0, kChunkMax, 1,
+     "rollout_feedback_backward_chunk_points: 0 (auto) or a number of candidates"},
     {"lqr_gains_chunk_points", &Handle::opt_lqr_gains_chunk, 0, kChunkMax, 1, "lqr_gains_chunk_points: 0 (auto) or a number of candidates"},
     {"ilqr_chunk_points", &Handle::opt_ilqr_chunk, 0, kChunkMax, 1, "ilqr_chunk_points: 0 (auto) or a number of candidates"},
     {"mll_batch_chunk", &Handle::opt_mll_batch_chunk, 1, kChunkMax, 1, "mll_batch_chunk: a number of problems >= 1"},
@@ -152,7 +154,7 @@ static int query_entry(gpmpc_t* g, const char* name, const char* count_name, int
 
 extern "C" {
 
-int gpmpc_abi_version(void) { return 28; }
+int gpmpc_abi_version(void) { return 29; }
 
 int gpmpc_create(gpmpc_t** out, int device_id) {
     if (!out) return GPMPC_ERR_ARG;
@@ -180,7 +182,7 @@ int gpmpc_destroy(gpmpc_t* g) {
     (void)hipSetDevice(h->device);
     Buf* all[] = {&h->Xt, &h->beta, &h->iK, &h->Tm, &h->ils2, &h->var, &h->logvar, &h->gram,
                   &h->linv, &h->zvec, &h->cost, &h->best, &h->xrange, &h->mono_w, &h->traj, &h->Xc, &h->Yc,
-                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->mllbws, &h->trainws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->fbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
+                  &h->hyp, &h->kv, &h->vv, &h->sc, &h->gradws, &h->mllws, &h->mllbws, &h->trainws, &h->cemws, &h->tilews, &h->sepw, &h->tgradws, &h->xch, &h->hio, &h->predws, &h->predbws, &h->covws, &h->momws, &h->mombws, &h->linws, &h->linbws, &h->fbws, &h->fbbws, &h->lqrws, &h->lbfgsws, &h->ilqrws, &h->Xf, &h->Yf, &h->fgws, &h->spws, &h->sprec, &h->selws, &h->spupd};
     for (Buf* b : all) free_buf(*b);
     if (h->hio_host) (void)hipHostFree(h->hio_host);
     if (h->hio_flag) (void)hipHostFree(h->hio_flag);
@@ -567,6 +569,30 @@ int gpmpc_rollout_linear_feedback_backward(gpmpc_t* g, const double* actions, co
     Range roctx_range(gains ? "gpmpc_rollout_linear_feedback_backward" : "gpmpc_rollout_linear_backward");
     return rollout_backward_entry(g, true, actions, gains, gains_per_candidate, mu0, S0, B, H, A, include_time, time0, mu_bar, Sig_bar,
                                   cm_bar, cv_bar, J_bar, actions_bar_out, gains_bar_out, mu0_bar_out, S0_bar_out, stream);
+}
+
+int gpmpc_rollout_feedback_backward(gpmpc_t* g, const double* actions, const double* gains, int gains_per_candidate,
+                                    const double* mu0, const double* S0, int B, int H, int A, int include_time, double time0,
+                                    const double* mu_bar, const double* Sig_bar, const double* cm_bar, const double* cv_bar,
+                                    const double* J_bar, double* actions_bar_out, double* gains_bar_out, double* mu0_bar_out,
+                                    double* S0_bar_out, void* stream) {
+    Range roctx_range("gpmpc_rollout_feedback_backward");
+    if (!g) return GPMPC_ERR_ARG;
+    if (!actions_bar_out) return bad(g, "null argument");
+    if (!gains && gains_bar_out) return bad(g, "gains_bar_out without gains");
+    RolloutSeeds sd{mu_bar, Sig_bar, cm_bar, cv_bar, J_bar, mu0_bar_out, S0_bar_out, cm_bar || cv_bar || J_bar};
+    RolloutArgs a;
+    int rc = fill_args(g, a, actions, mu0, S0, B, H, A, include_time, time0, sd.cost);
+    if (rc) return rc;
+    if (A < 1) return bad(g, "gradient needs A >= 1");
+    if (a.D > GPMPC_MAX_D || a.E > GPMPC_MAX_E) {
+        g->h.err = "rollout_feedback_backward: D or E beyond the compiled limits";
+        return GPMPC_ERR_LIMIT;
+    }
+    GPMPC_HIP_CHECK(H_(g), hipSetDevice(g->h.device));
+    // without gains: the all-zero policy through the closed-loop kernels (gpmpc_rollout_backward to rounding, not bit for bit)
+    return run_rollout_feedback_backward(H_(g), a, sd, gains, gains && gains_per_candidate != 0, actions_bar_out, gains_bar_out,
+                                         (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

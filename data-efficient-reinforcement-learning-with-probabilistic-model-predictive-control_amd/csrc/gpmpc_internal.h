@@ -222,6 +222,7 @@ struct Handle {
     Buf linws;    // gpmpc_moments_linear / gpmpc_rollout_linear: per-(output, column block, row) partial sums | model inputs | trajectory of one chunk
     Buf linbws;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward / gpmpc_rollout_linear_feedback_backward: partial sums | coefficients | model inputs | recomputed trajectory, step results and adjoints of one chunk
     Buf fbws;     // gpmpc_rollout_feedback: model inputs (means | covariances) | M | S | V of the step at hand | trajectory | zero gains of one chunk of candidates (rollout_feedback_plan.h)
+    Buf fbbws;    // gpmpc_rollout_feedback_backward: model inputs | M | S | recomputed trajectory | every step's V | cost variances | adjoints | cotangents and results of the moment gradient | zero gains of one chunk of candidates (rollout_feedback_backward_plan.h)
     Buf lqrws;    // gpmpc_lqr_gains: model inputs | M of the step at hand | every step's V of one chunk of candidates
     Buf lbfgsws;  // gpmpc_lbfgs_search: J (B) | dJ/d(model actions) (B, H, A) | ones (B), the J_bar of the linearised gradient
     Buf ilqrws;   // gpmpc_ilqr_*: model inputs | M of the step at hand | every step's V of the nominal | trial trajectories of one chunk of candidates (ilqr_plan.h)
@@ -323,6 +324,7 @@ struct Handle {
     int opt_moments_bwd_chunk = 0;   // gpmpc_moments_backward: the same for its chunks
     int opt_moments_linear_chunk = 0;   // gpmpc_moments_linear / gpmpc_rollout_linear: points / candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_moments_linear_bwd_chunk = 0;   // gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward: the same for their chunks
+    int opt_rollout_feedback_bwd_chunk = 0; // gpmpc_rollout_feedback_backward: the same for its chunks
     int opt_rollout_feedback_chunk = 0; // gpmpc_rollout_feedback: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_lqr_gains_chunk = 0;     // gpmpc_lqr_gains: candidates per chunk (0: as many as a 16 MB workspace holds; tests set small ones)
     int opt_mll_batch_chunk = 0;     // gpmpc_mll_batch / gpmpc_train_search: problems per launch and in the workspace (0: one per CU; results do not depend on it)
@@ -571,6 +573,10 @@ int launch_traj_cost_feedback(Handle* h, const RolloutArgs& a, int rows, const d
 // rollout_feedback.hip: the moment-matched horizon rollout in closed loop under u = ubar_t + K_t (x - mu_t) (`a` as fill_args leaves
 // it plus the outputs; gains (B, H, A, D) when per_candidate, else (H, A, D) shared, or NULL = all zero): run_moments per step
 int run_rollout_feedback(Handle* h, const RolloutArgs& a, hipStream_t s, const double* gains, bool per_candidate);
+// rollout_feedback_backward.hip: gradients of run_rollout_feedback wrt the actions, the gains (gains_bar (B, H, A, D) per candidate,
+// or NULL) and the initial state for the cotangents `sd` (forward recomputed inside; gains as there, NULL = all zero)
+int run_rollout_feedback_backward(Handle* h, const RolloutArgs& a, const RolloutSeeds& sd, const double* gains, bool per_candidate,
+                                  double* actions_bar, double* gains_bar, hipStream_t s);
 // lqr_gains.hip: the LQR gains (B, H, A, D) of the linearisation along each candidate's nominal trajectory on the loaded quadratic
 // cost (validated by the entry point: model, cost for this (D, A), 1 <= A <= kLqrMaxA, reg >= 0); P_out (B, H + 1, D, D) and
 // flags_out (B) may be NULL

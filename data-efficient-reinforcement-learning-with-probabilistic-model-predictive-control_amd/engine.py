@@ -595,8 +595,8 @@ class HipEngine:
 
     def _rollout_backward(self, name, actions, mu0, S0, include_time, time0, seeds, want_initial, closed_loop=False, gains=None,
                           want_gains=False):
-        """`rollout_backward`, `rollout_linear_backward` and `rollout_linear_feedback_backward`: `name` picks the library's entry;
-        the closed-loop one takes (gains, per_candidate) behind the actions and gains_bar behind actions_bar."""
+        """`rollout_backward`, `rollout_linear_backward`, `rollout_linear_feedback_backward` and `rollout_feedback_backward`: `name`
+        picks the library's entry; the closed-loop ones take (gains, per_candidate) behind the actions and gains_bar behind actions_bar."""
         actions = self._dev(actions)
         B, H, A = actions.shape
         D = self.D
@@ -676,6 +676,30 @@ class HipEngine:
                                      out={"J": J})
         ones = torch.ones(B, dtype=torch.float64, device=self.device)
         back = self.rollout_linear_feedback_backward(actions, gains, mu0, S0, include_time, time0, J_bar=ones, want_initial=False)
+        return {"J": J, "grad": back["actions_bar"], "gains_grad": back.get("gains_bar")}
+
+    def rollout_feedback_backward(self, actions, gains, mu0, S0, include_time=False, time0=0.0, mu_bar=None, Sig_bar=None,
+                                  cost_mu_bar=None, cost_var_bar=None, J_bar=None, want_initial=True, want_gains=True):
+        """Reverse-mode product of `rollout_feedback` (gpmpc_rollout_feedback_backward): the arguments and the dict of
+        `rollout_linear_feedback_backward` -- actions_bar (B,H,A), with `want_gains` gains_bar (B,H,A,D), with `want_initial`
+        mu0_bar (B,D) and S0_bar (B,D,D) per candidate (S0_bar the symmetric part).  Under moment matching the gains move the mean
+        as well, so gains_bar carries that path too.  gains_bar is per candidate and per step whatever the layout of `gains`:
+        reduce it as the gains were broadcast.  gains None: the zero-gain policy through the same kernels (no gains_bar).  The
+        forward is recomputed inside the call.  Cost / J seeds need set_cost.  Asynchronous on the current stream."""
+        return self._rollout_backward("rollout_feedback_backward", actions, mu0, S0, include_time, time0,
+                                      (mu_bar, Sig_bar, cost_mu_bar, cost_var_bar, J_bar), want_initial, closed_loop=True, gains=gains,
+                                      want_gains=want_gains)
+
+    def rollout_feedback_grad(self, actions, gains, mu0, S0, include_time=False, time0=0.0):
+        """Objective of the closed-loop moment-matched rollout and its analytic gradients: dict(J (B,), grad (B,H,A) =
+        dJ/d(actions), gains_grad (B,H,A,D) = dJ/d(gains), per candidate: see `rollout_feedback_backward`) of device tensors,
+        from `rollout_feedback` followed by `rollout_feedback_backward` with J_bar = 1."""
+        actions = self._dev(actions)
+        B = actions.shape[0]
+        J = torch.empty(B, dtype=torch.float64, device=self.device)
+        self.rollout_feedback(actions, gains, mu0, S0, include_time, time0, trajectories=False, stage_costs=False, out={"J": J})
+        ones = torch.ones(B, dtype=torch.float64, device=self.device)
+        back = self.rollout_feedback_backward(actions, gains, mu0, S0, include_time, time0, J_bar=ones, want_initial=False)
         return {"J": J, "grad": back["actions_bar"], "gains_grad": back.get("gains_bar")}
 
     def objective_grad_host(self, actions, mu0, S0, include_time=False, time0=0.0):

@@ -396,7 +396,7 @@ int gpmpc_moments_linear_backward(gpmpc_t* h, const double* mu_dev, const double
  * "moments_linear_chunk_points" (points of gpmpc_moments_linear / candidates of gpmpc_rollout_linear per internal chunk: 0 auto),
  * "moments_linear_backward_chunk_points" (the same for gpmpc_moments_linear_backward / gpmpc_rollout_linear_backward /
  * gpmpc_rollout_linear_feedback_backward), "rollout_feedback_chunk_points" (candidates of gpmpc_rollout_feedback per internal
- * chunk: 0 auto), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
+ * chunk: 0 auto), "rollout_feedback_backward_chunk_points" (the same for gpmpc_rollout_feedback_backward), "lqr_gains_chunk_points" (candidates of gpmpc_lqr_gains per internal chunk: 0 auto),
  * "ilqr_chunk_points" (candidates of gpmpc_ilqr_* per internal chunk: 0 auto),
  * "sparse_chunk_points" (memory points of gpmpc_prepare_sparse per internal chunk: 0 auto, else a multiple of 64),
  * "select_inducing_max_mb" (cap on the workspace of gpmpc_select_inducing in MiB, >= 1; 4096 unless set).
@@ -684,6 +684,57 @@ int gpmpc_rollout_linear_feedback_backward(gpmpc_t* h, const double* actions_dev
                                            const double* cost_mu_bar_dev, const double* cost_var_bar_dev, const double* J_bar_dev,
                                            double* actions_bar_out_dev, double* gains_bar_out_dev, double* mu0_bar_out_dev,
                                            double* S0_bar_out_dev, void* stream);
+
+/*
+ * gpmpc_rollout_feedback_backward: the reverse-mode product (vector-Jacobian product) of gpmpc_rollout_feedback for B candidates:
+ * the gradients of
+ *     sum_t <mu_bar_t, mu_t> + <Sig_bar_t, Sig_t> + cost_mu_bar_t cost_mu_t + cost_var_bar_t cost_var_t  +  J_bar J
+ * (what gpmpc_rollout_feedback writes for the same inputs and the same loaded cost) with respect to each candidate's actions ubar,
+ * its gains K_t and the initial mean and covariance, per candidate.  Arguments as gpmpc_rollout_linear_feedback_backward, one for
+ * one (gains_dev (B,H,A,D) when gains_per_candidate != 0, else (H,A,D) shared); its conventions hold: outputs are overwritten, a
+ * NULL cotangent is zero, Sig_bar is symmetrised on entry, the clip is pass-through for J, the time input is not differentiated,
+ * the cost weights are wm_t = cost_mu_bar_t + J_bar / (H+1), wv_t = cost_var_bar_t + J_bar (-kappa / (2 sqrt(cost_var_t))) / (H+1).
+ * Outputs:
+ *   actions_bar_out_dev (B,H,A)  required
+ *   gains_bar_out_dev (B,H,A,D)  or NULL (not written): ALWAYS per candidate, whatever the layout of gains_dev; a shared gain's
+ *                                gradient is the sum over B -- the entry does not reduce
+ *   mu0_bar_out_dev (B,D), S0_bar_out_dev (B,D,D)  or NULL (not written); S0_bar the symmetric part, exactly symmetric
+ * Forward, per candidate and step t, with x_t = [mu_t | ubar_t | time0 + t] and G_t = [I_D ; K_t ; 0] (E x D):
+ *   Sigma_in = G_t Sigma_t G_t^T,   (M, S, V) = moments(x_t, Sigma_in),   R = Sigma_in[:D, :] (D x E),   C = R V,
+ *   mu_{t+1} = mu_t + M,   Sigma_{t+1} = Sigma_t + S + C + C^T
+ * Reverse sweep t = H-1 .. 0 with the adjoints lambda_{t+1} (D), Lambda_{t+1} (D x D, symmetric), which start from mu_bar_H,
+ * sym(Sig_bar_H) and the terminal cost partials:
+ *   M_bar = lambda_{t+1},   S_bar = Lambda_{t+1},   C_bar = 2 Lambda_{t+1}
+ *   V_bar = R^T C_bar  (E x D, time row zero),   R_bar = C_bar V^T  (D x E)
+ *   (x_bar, P) = the step formula of gpmpc_moments_backward at (x_t, Sigma_in) with (M_bar, S_bar, V_bar); P the symmetric part
+ *   Z = P + sym([R_bar ; 0])                                                              (E x E, R_bar in the first D rows)
+ *   actions_bar_t = x_bar[D:D+A] + (cost partial wrt ubar_t)
+ *   gains_bar_t   = the action rows of 2 Z G_t Sigma_t + (cost partial wrt K_t)           (A x D)
+ *   lambda_t = lambda_{t+1} + x_bar[:D] + mu_bar_t + (cost partial wrt mu_t)
+ *   Lambda_t = Lambda_{t+1} + G_t^T Z G_t + sym(Sig_bar_t + cost partial wrt Sigma_t)     (i <= j, mirrored)
+ * and mu0_bar = lambda_0, S0_bar = Lambda_0.  Stage and terminal cost partials: those of gpmpc_rollout_linear_feedback_backward
+ * (the same device code).
+ * The forward is RECOMPUTED inside the call by gpmpc_rollout_feedback's own kernels (the recomputed trajectory and model inputs
+ * have its bits) and keeps every step's V, per chunk of candidates; each reverse step runs gpmpc_moments_backward's launches over
+ * the chunk.  The call is stateless.  Bitwise contracts: a candidate's four outputs are the same bits alone and at any position of
+ * any batch; for any value of "rollout_feedback_backward_chunk_points", "moments_chunk_points" and
+ * "moments_backward_chunk_points"; and whether its gains arrive shared or per candidate.  A NULL cotangent and an all-zero one
+ * give the same bits; NULL optional outputs do not change the others' bits.  Every sum runs in an order fixed by N, E, D and A
+ * alone; no atomics.  Workspace: its own (model inputs, recomputed trajectory, every step's V, adjoints, the cotangents and results
+ * of the moment gradient), within 16 MB or one candidate's need: option "rollout_feedback_backward_chunk_points" (candidates per
+ * chunk, 0 = auto); it also uses gpmpc_moments' and gpmpc_moments_backward's workspaces and honours their chunk options.  Touches
+ * no gpmpc_last_* state.  Asynchronous on `stream`.
+ * gains_dev == NULL with gains_bar_out_dev == NULL: the zero-gain policy through these same kernels (gpmpc_rollout_backward to
+ * rounding, not bit for bit); gains_dev == NULL with gains_bar_out_dev != NULL: GPMPC_ERR_ARG.  Other errors (no output is written
+ * on an error): the argument and limit errors of gpmpc_rollout_feedback; GPMPC_ERR_ARG for actions_bar_out_dev == NULL, for A < 1,
+ * and for a cost or J cotangent without gpmpc_set_cost for this (D, A).
+ */
+int gpmpc_rollout_feedback_backward(gpmpc_t* h, const double* actions_dev, const double* gains_dev, int gains_per_candidate,
+                                    const double* mu0_host, const double* S0_host, int B, int H, int A, int include_time,
+                                    double time0, const double* mu_bar_dev, const double* Sig_bar_dev,
+                                    const double* cost_mu_bar_dev, const double* cost_var_bar_dev, const double* J_bar_dev,
+                                    double* actions_bar_out_dev, double* gains_bar_out_dev, double* mu0_bar_out_dev,
+                                    double* S0_bar_out_dev, void* stream);
 
 /*
  * gpmpc_objective_grad_host  <->  ONE call of compute_mean_lcb_trajectory (gp_mpc_controller.py:229-285) as scipy's L-BFGS-B

@@ -112,6 +112,18 @@ __host__ __device__ inline int rnd2(int x) { return (x + 1) & ~1; }
 
 constexpr int kClusterScratch = 16 * 64 / 8;     // the cooperative form's per-wavefront problem lists (16 wavefronts x 64 bytes)
 
+// Descriptor of one entry of the step's work-item list (plain and batch-major forms), two 32-bit words:
+//   lo: [0, 16) the item's code (pair slot index gq * wpp + slot, or 0xffff - a for the mean sums of output a) | [16, 24) row count
+//       of a tabulated diagonal slot + 1 (0: not tabulated; counts are <= 64) | [24, 31) Taylor degree and separable flag (s_K)
+//   hi: [0, 16) slot | [16, 22) pair of the group (G <= 48) | [22, 26) output a | [26, 30) output b (D <= 16)
+// A pull past the list's end yields lo = -1.
+__host__ __device__ inline unsigned item_desc_lo(int code, int nrows_tab, int Kraw) {
+    return (unsigned)code | ((unsigned)(nrows_tab + 1) << 16) | ((unsigned)(Kraw & 127) << 24);
+}
+__host__ __device__ inline unsigned item_desc_hi(int slot, int gq, int a, int b) {
+    return (unsigned)slot | ((unsigned)gq << 16) | ((unsigned)a << 22) | ((unsigned)b << 26);
+}
+
 __host__ __device__ inline Layout make_layout(int N, int D, int A, int E, int G, int DP, int wpp, int CM, int CH, int HA,
                                               bool x_in_lds, bool cluster = false, int lds_pairs = 0) {
     const int GL = (cluster && lds_pairs > 0) ? lds_pairs : G;      // pairs whose per-point records live in LDS (cooperative form: the member's own)
@@ -132,8 +144,12 @@ __host__ __device__ inline Layout make_layout(int N, int D, int A, int E, int G,
     L.part = o; o += rnd2(G * wpp);
     L.mom = o;  o += G * 2 * rnd2(CM);
     // pa[P], pb[P], K[G], counter, noff, off[G], mcum[16], tri[RC+1], nslot[G], nitems (ints); then the step's work-item list
-    // (16-bit entries: D mean items + at most G * wpp pair items)
-    L.ints = o; o += rnd2((2 * P + 3 * G + 8 + 16 + tri_ints(N) + 1) / 2) + rnd2((D + G * wpp + 3) / 4);
+    // (D mean items + at most G * wpp pair items).  Plain and batch-major forms of the DP = 3 unit: one 8-byte descriptor per entry (all a
+    // wavefront needs to start the item, one LDS read); cooperative form and the other units: 16-bit codes.  (8 bytes per entry against the
+    // 48-byte-or-more row records of N + CH points per pair: a pair's wpp = RC * NC / 64 entries are N / (768 CH) of its records at
+    // DP = 3 -- 1 % at config 2, 5 % at N = 2000 with 48-row chunks; no shape beyond config 3 was timed with it.)  Either way the list starts and ends on a
+    // 16-byte boundary, so that every region behind it keeps its alignment.
+    L.ints = o; o += rnd2((2 * P + 3 * G + 8 + 16 + tri_ints(N) + 1) / 2) + ((cluster || DP != 3) ? rnd2((D + G * wpp + 3) / 4) : rnd2(D + G * wpp));
     // lane map of the diagonal pairs' work items: (row chunk, column unit) per (slot, lane) + rows per slot, for up to
     // kLaneMapSlots slots (state-independent: filled once per launch)
     const int lms = cluster ? kLaneMapSlotsCluster : kLaneMapSlots;
@@ -841,8 +857,17 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     // long items (element-wise pairs) first, the short mean sums last.  Entry = pair slot index gq * wpp + slot, or
     // 0xffff - a for the mean sums of output a.  (Until round 5 the queue walked all G * wpp slots: at config 2, 36 of 69
     // pulls per step found nothing to do, each after the lane set-up of an item.)
-    unsigned short* s_items = reinterpret_cast<unsigned short*>(
+    // Plain and batch-major forms: an entry is an 8-byte descriptor (item_desc_lo / item_desc_hi) that carries what the builder knows
+    // about the item anyway -- slot, pair, outputs, evaluation form, the tabulated row count -- so that P3 starts an item from ONE
+    // LDS read (before: the code, a multiply-high division, then s_pa / s_pb / s_K and s_lrows, two more dependent round trips).
+    // The cooperative form keeps the 16-bit codes (its members take their items from s_mine; its gather walks this list).
+    [[maybe_unused]] unsigned short* s_items = reinterpret_cast<unsigned short*>(
         smem + L.ints + rnd2((2 * P + 3 * G + 8 + 16 + tri_ints(N) + 1) / 2));
+    // The DP = 3 unit alone: that is where it measured (configs 1 and 2, two workgroups per CU at B = 4096).  DP = 2 lost 0.3-0.8 %
+    // at config 3, whose few long items gain nothing from a shorter head; with the descriptor in registers the 256-thread DP = 8
+    // unit lost a wavefront of occupancy and the run-time-D DP = 4 units gained 4 bytes of scratch; no DP = 4 shape was timed.
+    constexpr bool kDesc = !CL && DP == 3;
+    [[maybe_unused]] uint2* s_desc = reinterpret_cast<uint2*>(smem + L.ints + rnd2((2 * P + 3 * G + 8 + 16 + tri_ints(N) + 1) / 2));
 
     // Lane map of a diagonal pair's work items (slot, lane) -> (row chunk | column unit << 8), -1 = no element, and the row count
     // of each slot: the triangle's enumeration does not depend on the state, so the per-item binary search over s_tri and the
@@ -900,6 +925,11 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     // that ends the next P1, summed over the launch (first lane of wavefronts 0 and 1)
     long long prof_b3 = 0, prof_chain = 0;
     int prof_chain_n = 0;
+    // the work queue of P3 per wavefront and item class (0 element-wise, 1 separable, 2 mean sums): pull -> first trip (head),
+    // first -> last trip (loop), last trip -> next pull (tail), summed over the launch
+    long long prof_ih[3] = {0, 0, 0}, prof_il[3] = {0, 0, 0}, prof_it[3] = {0, 0, 0};
+    int prof_in[3] = {0, 0, 0}, prof_icls = -1;
+    long long prof_ipull = 0, prof_ifirst = 0, prof_ilast = 0;
 #endif
     // ---- init -----------------------------------------------------------------------
     if constexpr (TILED) {
@@ -1613,7 +1643,20 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         start += (clm < cls || (clm == cls && m < lane)) ? nsm : 0;
                         total_items += nsm;
                     }
-                    for (int k = 0; k < ns; ++k) s_items[start + k] = (unsigned short)(cls == 2 ? code0 : code0 + k);
+                    if constexpr (!kDesc) {
+                        for (int k = 0; k < ns; ++k) s_items[start + k] = (unsigned short)(cls == 2 ? code0 : code0 + k);
+                    } else {
+                        // one descriptor per entry: the pair's outputs and evaluation form, which this lane knows anyway, and the row
+                        // count of a tabulated diagonal slot travel with the code (item_desc_lo / item_desc_hi)
+                        int pa = 0, pb = 0, Kr = 0;
+                        if (cls < 2) { pa = s_pa[q0 + lane]; pb = s_pb[q0 + lane]; Kr = s_K[lane]; }
+                        const bool tab = cls == 0 && pa == pb && use_lmap;
+                        for (int k = 0; k < ns; ++k) {
+                            const int code = cls == 2 ? code0 : code0 + k;
+                            const int nrt = tab ? s_lrows[k] : -1;
+                            s_desc[start + k] = make_uint2(item_desc_lo(code, nrt, Kr), item_desc_hi(k, lane, pa, pb));
+                        }
+                    }
                     if (lane == 0) *s_nitems = total_items;
                     return total_items;
                 };
@@ -1818,30 +1861,78 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
 #if defined(GPMPC_PROF_ON)
             const long long prof_p3 = __builtin_readcyclecounter();
 #endif
-            auto pull_item = [&]() -> int {
-                int pulled = 0;
-                if (lane == 0) {
-                    pulled = __hip_atomic_fetch_add(s_counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    pulled = (pulled < total) ? (int)s_items[pulled] : -1;
-                }
-                return __builtin_amdgcn_readfirstlane(pulled);       // wave-uniform (SGPR) work item
+            // Plain and batch-major forms of the DP = 3 unit (kDesc): the queue.  A pull is one LDS atomic and one 8-byte read (the entry's descriptor).  A long
+            // (element-wise) item claims its wavefront's next entry right behind its element loop (q_claim_late), so that the atomic's
+            // round trip runs under the item's reduction and store; the descriptor read follows them.  A wavefront that holds a claim
+            // takes that entry and no other, and it leaves when its claim is past the list's end, so nothing claimed outlives the
+            // group (the counter is reset for the next group behind this phase's barrier).
+            // (Measured and not adopted: the claim at the HEAD of the current item, the descriptor read before its element loop --
+            //  the claimed entry then waits for the whole item while other wavefronts run dry: config 2 + 5 %)
+            [[maybe_unused]] int q_nidx = 0;                          // lane 0: the index this wavefront has claimed
+            [[maybe_unused]] bool q_claimed = false;
+            [[maybe_unused]] int wq_hi = 0;                           // second word of the current item's descriptor (wave-uniform)
+            auto q_claim = [&]() -> int {
+                // (an opaque copy of the counter's address: with an address it can prove uniform the compiler rewrites the one-lane
+                //  atomic for any number of active lanes -- lane count, one atomic, broadcast -- and waits for the result on the spot)
+                typedef __attribute__((address_space(3))) int* lds_iptr;
+                lds_iptr cq = (lds_iptr)s_counter;
+                asm volatile("" : "+v"(cq));
+                int i = 0;
+                if (lane == 0) i = __hip_atomic_fetch_add(cq, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                return i;
             };
+            [[maybe_unused]] auto q_claim_late = [&] { q_nidx = q_claim(); q_claimed = true; };
             // cooperative form: no queue -- the j-th item this member owns (listed beside the per-point pass) goes to wavefront j mod NW
             [[maybe_unused]] int cl_next = wave;
             [[maybe_unused]] const int cl_count = CL ? (int)s_mine[0] : 0;
             auto next_item = [&]() -> int {
-                if constexpr (!CL) return pull_item();
-                else {
+                if constexpr (!CL && !kDesc) {
+                    int pulled = 0;
+                    if (lane == 0) {
+                        pulled = __hip_atomic_fetch_add(s_counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        pulled = (pulled < total) ? (int)s_items[pulled] : -1;
+                    }
+                    return __builtin_amdgcn_readfirstlane(pulled);       // wave-uniform (SGPR) work item
+                } else if constexpr (kDesc) {
+                    if (!q_claimed) q_nidx = q_claim();
+                    q_claimed = false;
+                    uint2 d = make_uint2(~0u, 0u);                       // past the list's end: -1
+                    if (lane == 0 && q_nidx < total) d = s_desc[q_nidx];
+                    wq_hi = __builtin_amdgcn_readfirstlane((int)d.y);
+                    return __builtin_amdgcn_readfirstlane((int)d.x);       // wave-uniform (SGPR) work item
+                } else {
                     if (cl_next >= cl_count) return -1;
                     const int code = __builtin_amdgcn_readfirstlane((int)s_mine[1 + cl_next]);
                     cl_next += NW;
                     return code;
                 }
             };
-            for (int wq = next_item(); wq >= 0; wq = next_item()) {
-                if (wq >= 0xffff - 15) {
+#if defined(GPMPC_PROF_ON)
+            prof_icls = -1;
+            auto next_item_prof = [&]() -> int {
+                const long long now_ = __builtin_readcyclecounter();
+                if (prof_icls >= 0) {
+                    prof_ih[prof_icls] += prof_ifirst - prof_ipull; prof_il[prof_icls] += prof_ilast - prof_ifirst;
+                    prof_it[prof_icls] += now_ - prof_ilast; ++prof_in[prof_icls];
+                }
+                prof_icls = -1;
+                prof_ipull = now_;
+                return next_item();
+            };
+#define GPMPC_NEXT_ITEM next_item_prof
+#define GPMPC_ITEM_FIRST(cls) do { prof_icls = (cls); prof_ifirst = __builtin_readcyclecounter(); prof_ilast = prof_ifirst; } while (0)
+#define GPMPC_ITEM_LAST() do { prof_ilast = __builtin_readcyclecounter(); } while (0)
+#else
+#define GPMPC_NEXT_ITEM next_item
+#define GPMPC_ITEM_FIRST(cls) do {} while (0)
+#define GPMPC_ITEM_LAST() do {} while (0)
+#endif
+            for (int wq = GPMPC_NEXT_ITEM(); wq >= 0; wq = GPMPC_NEXT_ITEM()) {
+                const int wi = kDesc ? (wq & 0xffff) : wq;          // the item's code
+                if (wi >= 0xffff - 15) {
                     // s1[a][0] = sum_p lb, s1[a][1+d] = sum_p lb nu_d  (fixed order)
-                    const int a = 0xffff - wq;
+                    const int a = 0xffff - wi;
+                    GPMPC_ITEM_FIRST(2);
                     for (int dd = 0; dd <= D; ++dd) {
                         double v = 0.0;
                         if (dd == 0) { for (int pt = lane; pt < N; pt += 64) v += a_lb[a * N + pt]; }
@@ -1852,14 +1943,22 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                             if constexpr (CL) publish(x_mean + a * (D + 1) + dd, v);
                         }
                     }
+                    GPMPC_ITEM_LAST();
                     continue;
                 }
-                const int wi = wq;
-                const int gq = p.magic_wpp ? (int)__umulhi((unsigned)wi, p.magic_wpp) : wi;   // wi / wpp (magic 0: wpp == 1)
-                const int slot = wi - gq * wpp;
-                const int a = __builtin_amdgcn_readfirstlane(s_pa[q0 + gq]);
-                const int b = __builtin_amdgcn_readfirstlane(s_pb[q0 + gq]);
-                const int Kraw = __builtin_amdgcn_readfirstlane(s_K[gq]);
+                int gq, slot, a, b, Kraw;
+                [[maybe_unused]] int desc_nrows = -1;
+                if constexpr (!kDesc) {
+                    gq = p.magic_wpp ? (int)__umulhi((unsigned)wi, p.magic_wpp) : wi;   // wi / wpp (magic 0: wpp == 1)
+                    slot = wi - gq * wpp;
+                    a = __builtin_amdgcn_readfirstlane(s_pa[q0 + gq]);
+                    b = __builtin_amdgcn_readfirstlane(s_pb[q0 + gq]);
+                    Kraw = __builtin_amdgcn_readfirstlane(s_K[gq]);
+                } else {
+                    // all of it from the descriptor (item_desc_lo / item_desc_hi)
+                    slot = wq_hi & 0xffff; gq = (wq_hi >> 16) & 63; a = (wq_hi >> 22) & 15; b = (wq_hi >> 26) & 15;
+                    Kraw = (wq >> 24) & 127; desc_nrows = ((wq >> 16) & 255) - 1;
+                }
                 const int K = Kraw & 63;
                 const bool diag = (a == b);
                 if (Kraw & 64) {
@@ -1871,6 +1970,7 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         // three state dimensions: compile-time monomial structure, items = (side, band of the x0 exponent)
                         const int KS = K <= 3 ? 3 : K;                                   // K <= 6 on this path (P1)
                         const int nbands = sep3_bands(KS);
+                        GPMPC_ITEM_FIRST(1);
                         for (int itm = slot; itm < 2 * nbands; itm += wpp) {
                             const int side = itm >= nbands, band = itm - side * nbands;
                             const double* rec0 = a_rows + (size_t)sl3 * NR * RS;
@@ -1882,10 +1982,12 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                             else if (K == 5) sep3_item<5>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);
                             else sep3_item<6>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);      // K <= 6 on this path (P1)
                         }
+                        GPMPC_ITEM_LAST();
                         continue;
                     }
                     const int C = s_mcum[K];
                     const int NBk = (C + 7) >> 3;
+                    GPMPC_ITEM_FIRST(1);
                     for (int blk = slot; blk < 2 * NBk; blk += wpp) {
                         const int side = blk >= NBk;
                         const int al0 = (blk - side * NBk) * 8;
@@ -1924,6 +2026,7 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         const int mm = lane >> 2;
                         if ((lane & 3) == 0 && lane < 32 && al0 + mm < C) s_mom[(gq * 2 + side) * rnd2(CM) + al0 + mm] = tot;
                     }
+                    GPMPC_ITEM_LAST();
                     continue;
                 }
                 const int flat = slot * 64 + lane;
@@ -1935,7 +2038,8 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                     valid = packed >= 0;
                     r = valid ? (packed & 255) : 0;
                     jc = valid ? (packed >> 8) : 0;
-                    nrows_tab = __builtin_amdgcn_readfirstlane(s_lrows[slot]);
+                    if constexpr (!kDesc) nrows_tab = __builtin_amdgcn_readfirstlane(s_lrows[slot]);
+                    else nrows_tab = desc_nrows;
                 } else if (diag) {
                     // only the (row chunk, column unit) combinations that contain an element i <= j are enumerated:
                     // s_tri[r] = number of such combinations in chunks < r (lanes binary-search their chunk)
@@ -1984,6 +2088,7 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         for (int d = 0; d < DP; ++d) w1[d] = (d < D) ? a_nu[d * N + jl] * (c_ils2[b * E + d] * m1) : 0.0;
                         const double kb1 = a_kb[sle * N + jl] * m1;
                         double acc0, acc1;
+                        GPMPC_ITEM_FIRST(0);
                         if (K == 0) {
                             item_exp2<DP>(rec, nrows, w, w1, kbj, kb1, diag, trows, c_exptab, acc0, acc1);
                             acc = acc0 * (diag ? 2.0 : p.beta[b * N + j]) + (valid1 ? acc1 * (diag ? 2.0 : p.beta[b * N + j + 1]) : 0.0);
@@ -2004,9 +2109,11 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                             acc = fma(acc0, kbj, acc1 * kb1) * (diag ? 2.0 : 1.0);
                         }
                     } else if (K == 0) {
+                        GPMPC_ITEM_FIRST(0);
                         acc = item_exp<DP, REC>(rec, nrows, w, kbj, diag, Tp, N, c_exptab);
                         acc *= diag ? 2.0 : p.beta[b * N + j];
                     } else {
+                        GPMPC_ITEM_FIRST(0);
                         if (K <= 2) acc = item_taylor<DP, 2, REC>(rec, nrows, w, diag, Tp, N);
                         else if (K == 3) acc = item_taylor<DP, 3, REC>(rec, nrows, w, diag, Tp, N);
                         else if (K == 4) acc = item_taylor<DP, 4, REC>(rec, nrows, w, diag, Tp, N);
@@ -2019,7 +2126,11 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         else acc = item_taylor<DP, 14, REC>(rec, nrows, w, diag, Tp, N);
                         acc *= diag ? 2.0 * kbj : kbj;
                     }
+                    GPMPC_ITEM_LAST();
+                    if constexpr (kDesc) q_claim_late();        // the next entry's claim runs under this item's reduction
                     acc = valid ? acc : 0.0;
+                } else {
+                    GPMPC_ITEM_FIRST(0);                        // (an item without rows: all of it is head and tail)
                 }
                 acc = wave_sum(acc);
                 if (lane == 0) {
@@ -2027,6 +2138,9 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                     if constexpr (CL) publish(wi, acc);
                 }
             }
+#undef GPMPC_NEXT_ITEM
+#undef GPMPC_ITEM_FIRST
+#undef GPMPC_ITEM_LAST
 #if defined(GPMPC_PROF_ON) && defined(GPMPC_PROF_BARRIER)
             if constexpr (CL) __syncthreads();           // prof A/B: "items" then ends when the member's LAST wavefront is done
 #endif
@@ -2165,6 +2279,10 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && prof_chain_n > 0)      // wavefront 0; two streams: the pair problems' wavefront too
         printf("PROF chain wave %d: end of P3 -> arrival at the P1 barrier %lld cycles over %d intervals\n", (int)(threadIdx.x >> 6), prof_chain, prof_chain_n);
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) printf("PROF P3 wave %d left the queue after %lld\n", (int)(threadIdx.x >> 6), prof_left);
+    if (blockIdx.x == 0 && (threadIdx.x & 63) == 0)
+        printf("PROF items wave %2d: element-wise n %d head %lld loop %lld tail %lld | separable n %d head %lld loop %lld tail %lld | mean n %d head %lld loop %lld tail %lld\n",
+               (int)(threadIdx.x >> 6), prof_in[0], prof_ih[0], prof_il[0], prof_it[0], prof_in[1], prof_ih[1], prof_il[1], prof_it[1],
+               prof_in[2], prof_ih[2], prof_il[2], prof_it[2]);
     if (CL && threadIdx.x == 0 && (blockIdx.x & 7) == 0)
         printf("PROF member %2d xcc %d same_xcd %d\n", member, (int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)), (int)same_xcd);
     if (CL && threadIdx.x == 0 && (blockIdx.x & 7) == 0)

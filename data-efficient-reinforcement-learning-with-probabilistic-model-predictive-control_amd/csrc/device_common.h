@@ -24,16 +24,36 @@ __device__ inline double dpp_shifted(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// NV independent wavefront sums issued step by step side by side: every value goes through the SAME six DPP adds in the same
+// order whatever NV is (so its bits do not depend on its neighbours); a tree on its own is six dependent DPP adds, NV of them
+// fill each other's issue gaps.
+template <int NV>
+__device__ inline void wave_sum_n(double (&v)[NV]) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x111, 0xf>(v[k]);      // row_shr:1
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x112, 0xf>(v[k]);      // row_shr:2
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x114, 0xf>(v[k]);      // row_shr:4
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x118, 0xf>(v[k]);      // row_shr:8
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x142, 0xa>(v[k]);      // row_bcast:15 -> rows 1, 3
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += dpp_shifted<0x143, 0xc>(v[k]);      // row_bcast:31 -> rows 2, 3
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int lo = __builtin_amdgcn_readlane(__double2loint(v[k]), 63);
+        const int hi = __builtin_amdgcn_readlane(__double2hiint(v[k]), 63);
+        v[k] = __hiloint2double(hi, lo);
+    }
+}
+
+// One wavefront sum: the tree above for a single value (ONE copy of the order the bit fixtures depend on).
 __device__ inline double wave_sum(double v) {
-    v += dpp_shifted<0x111, 0xf>(v);      // row_shr:1
-    v += dpp_shifted<0x112, 0xf>(v);      // row_shr:2
-    v += dpp_shifted<0x114, 0xf>(v);      // row_shr:4
-    v += dpp_shifted<0x118, 0xf>(v);      // row_shr:8
-    v += dpp_shifted<0x142, 0xa>(v);      // row_bcast:15 -> rows 1, 3
-    v += dpp_shifted<0x143, 0xc>(v);      // row_bcast:31 -> rows 2, 3
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-    return __hiloint2double(hi, lo);
+    double t[1] = {v};
+    wave_sum_n(t);
+    return t[0];
 }
 
 // Wavefront sum by an xor butterfly over offsets 32, 16, ..., 1: every lane ends with the total.  Fixed order.

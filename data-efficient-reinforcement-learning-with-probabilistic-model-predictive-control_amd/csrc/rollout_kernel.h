@@ -56,6 +56,15 @@ __device__ inline double lds_b64(const double* p) {
     asm volatile("" : "+v"(q));
     return *q;
 }
+// LDS-typed operands of code the compiler cannot see the kernel's `smem` from (a function that is not inlined): a 32-bit address, so
+// every access is a ds_* instruction with an immediate offset instead of a FLAT one on a 64-bit per-lane address.
+typedef __attribute__((address_space(3))) double* lds_ptr;
+typedef __attribute__((address_space(3))) int* lds_iptr;
+// a wave-uniform LDS address that arrived in a vector register (function arguments do), back in a scalar one
+template <class P>
+__device__ inline P lds_uniform(P p) {
+    return (P)(uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(uintptr_t)p);
+}
 
 // Row records of the pairwise pass (one per memory point and output pair, broadcast from LDS to every lane of a wavefront).
 //   RowRecPacked<DP>  : ea_i | ra_i | g_i (DP), stride DP + 2 -- the staged records of rollout_stream_kernel.h;
@@ -685,13 +694,37 @@ struct Sep3Canon {
     }
 };
 
+// The canonical indices g + 4 w ... g + 4 w + 3 of a band as the bytes of one word (every index is below cum(6) = 84): the
+// scatter of a reduction picks its index from four such literals by lane, with no table in memory behind the reduction.
+template <int KS, int B>
+constexpr unsigned sep3_canon_word(int g, int w) {
+    const Sep3Canon<KS, B> c{};
+    unsigned r = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int m = g + 4 * w + k;
+        if (m < sep3_count(B, KS)) r |= (unsigned)c.v[m] << (8 * k);
+    }
+    return r;
+}
+template <int KS, int B, int G>
+__device__ inline int sep3_canon_of(int mq) {
+    constexpr unsigned w0 = sep3_canon_word<KS, B>(G, 0), w1 = sep3_canon_word<KS, B>(G, 1);
+    constexpr unsigned w2 = sep3_canon_word<KS, B>(G, 2), w3 = sep3_canon_word<KS, B>(G, 3);
+    const int ws = mq >> 2;
+    const unsigned w = ws == 0 ? w0 : (ws == 1 ? w1 : (ws == 2 ? w2 : w3));
+    return (int)((w >> (8 * (mq & 3))) & 255u);
+}
+
 // One (side, band) item: lanes own points; every monomial of the band costs one FMA per point (x1^j, x2^k tabulated per
 // point, wt x0^i x1^j formed once per (i, j)); the lane partials are reduced 8 at a time and scattered to the
 // canonical positions of this (pair, side) in `mom`.
 // (side 0: rows, x = g_i from the row records, weight rec[1]; side 1: columns, x = nu_j / l_b^2, weight kb)
+// Every operand is in LDS and wave-uniform (N, side and the addresses in scalar registers): one loop per side, its loads at immediate
+// offsets off one address per array.  `do_claim`: the wavefront's next queue entry is claimed (one-lane atomic on *cq, result in
+// `claimed`) between the point loop and the reduction, whose ~57 vector instructions cover the atomic's round trip.
 template <int KS, int B>
-__device__ inline void sep3_band(int lane, int N, int side, const double* rec0, int RS, const double* kb, const double* nu,
-                                 const double* il, double* mom) {
+__device__ inline void sep3_band(int lane, int N, int side, lds_cptr rec0, lds_cptr kb, lds_cptr nu, lds_cptr il, lds_ptr mom,
+                                 lds_iptr cq, int do_claim, int& claimed) {
     constexpr int NBm = sep3_count(B, KS);
     if constexpr (NBm > 0) {
         constexpr int NP = (NBm + 7) & ~7;
@@ -700,18 +733,7 @@ __device__ inline void sep3_band(int lane, int N, int side, const double* rec0, 
         double acc[NP];
 #pragma unroll
         for (int m = 0; m < NP; ++m) acc[m] = 0.0;
-        for (int pt = lane; pt < N; pt += 64) {
-            double x0, x1, x2, wt;
-            if (side == 0) {
-                // lanes own points: per-lane 16-byte reads at the record stride of 48 bytes are conflict-free (the start banks of
-                // a 16-lane group are the 16 multiples of 4)
-                double r[RowRecAligned<3>::RS];
-                RowRecAligned<3>::load<RowRecAligned<3>::RS>(rec0 + (size_t)pt * RS, r);
-                wt = r[RowRecAligned<3>::RA]; x0 = r[0]; x1 = r[1]; x2 = r[2];
-            } else {
-                wt = kb[pt];
-                x0 = nu[pt] * il[0]; x1 = nu[N + pt] * il[1]; x2 = nu[2 * N + pt] * il[2];
-            }
+        auto point = [&](double wt, double x0, double x1, double x2) {
             double py[KS + 1], pz[KS + 1];
             py[0] = 1.0; pz[0] = 1.0;
 #pragma unroll
@@ -730,40 +752,83 @@ __device__ inline void sep3_band(int lane, int N, int side, const double* rec0, 
                 }
                 wx *= x0;
             }
+        };
+        // a scalar trip count with the lanes past N masked inside a trip: the accumulators are zeroed once, ahead of the loop
+        const int trips = (N + 63) >> 6;
+        if (side == 0) {
+            // lanes own points: per-lane 16-byte reads at the record stride of 48 bytes are conflict-free (the start banks of
+            // a 16-lane group are the 16 multiples of 4)
+            typedef const __attribute__((address_space(3))) lds_d2* lds_c2ptr;
+            constexpr int RS3 = RowRecAligned<3>::RS;
+            static_assert(RS3 == 6 && RowRecAligned<3>::RA == 4 && RowRecAligned<3>::G == 0, "three 16-byte reads per record");
+            // (g0 g1 | g2 ea | ra: the weight as an 8-byte read of its own, so that no destination overlaps another's and the three
+            //  reads of a record issue back to back)
+            lds_cptr r = rec0 + lane * RS3;
+            for (int t = 0, pt = lane; t < trips; ++t, pt += 64, r += 64 * RS3) {
+                if (pt < N) {
+                    const lds_d2 t0 = *(lds_c2ptr)r, t1 = *(lds_c2ptr)(r + 2);
+                    point(r[RowRecAligned<3>::RA], t0.x, t0.y, t1.x);
+                }
+            }
+        } else {
+            const double il0 = il[0], il1 = il[1], il2 = il[2];
+            lds_cptr k0 = kb + lane, n0 = nu + lane, n1 = nu + N + lane, n2 = nu + 2 * N + lane;
+            for (int t = 0, pt = lane; t < trips; ++t, pt += 64, k0 += 64, n0 += 64, n1 += 64, n2 += 64) {
+                if (pt < N) point(*k0, *n0 * il0, *n1 * il1, *n2 * il2);
+            }
+        }
+        if (do_claim) {
+            // (an opaque copy of the counter's address, as in the kernel's q_claim: the atomic stays one lane's)
+            asm volatile("" : "+v"(cq));
+            if (lane == 0) claimed = __hip_atomic_fetch_add(cq, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         // lane partials -> totals, sixteen (eight) at a time on the permlane / DPP exchange network (wave_reduce16: 57 vector
         // instructions, no LDS round trip; the ds_bpermute butterflies of wave_sum8 took ~70 instructions and six dependent LDS
         // round trips per EIGHT values -- the reductions were more than half of a low-degree item)
-        static constexpr Sep3Canon<KS, B> canon{};
         const int mq = lane >> 2;
-#pragma unroll
-        for (int g16 = 0; g16 + 16 <= NP; g16 += 16) {
-            const double(&grp)[16] = *reinterpret_cast<const double(*)[16]>(&acc[g16]);
+        static_assert(NP <= 16, "a band is one reduction: at most 16 monomials");
+        if constexpr (NP == 16) {
+            const int at = sep3_canon_of<KS, B, 0>(mq);
+            const double(&grp)[16] = *reinterpret_cast<const double(*)[16]>(&acc[0]);
             const double tot = wave_reduce16(grp);
-            if ((lane & 3) == 0 && g16 + mq < NBm) mom[canon.v[g16 + mq]] = tot;
+            if ((lane & 3) == 0 && mq < NBm) mom[at] = tot;
         }
         if constexpr (NP % 16 != 0) {
             constexpr int g8 = NP - 8;
+            const int at = sep3_canon_of<KS, B, g8>(mq & 7);
             const double(&grp)[8] = *reinterpret_cast<const double(*)[8]>(&acc[g8]);
             const double tot = wave_reduce8(grp);
-            if ((lane & 3) == 0 && lane < 32 && g8 + mq < NBm) mom[canon.v[g8 + mq]] = tot;
+            if ((lane & 3) == 0 && lane < 32 && g8 + mq < NBm) mom[at] = tot;
         }
     }
 }
 
-// Not inlined: the band code wants ~90 VGPRs of its own, next to the ~60 the work-queue loop keeps live.
+// Not inlined: the band code wants ~90 VGPRs of its own, next to the ~60 the work-queue loop keeps live.  Arguments of a call
+// arrive in vector registers; the wave-uniform ones go back to scalar registers here, so that the band switch and the side are
+// scalar branches.  Returns (lane 0) the queue index claimed when `do_claim` is set.
 template <int KS>
-__device__ __attribute__((noinline)) void sep3_item(int band, int lane, int N, int side, const double* rec0, int RS,
-                                                     const double* kb, const double* nu, const double* il, double* mom) {
+__device__ __attribute__((noinline)) int sep3_item(int band, int lane, int N, int side, lds_cptr rec0, lds_cptr kb, lds_cptr nu,
+                                                    lds_cptr il, lds_ptr mom, lds_iptr cq, int do_claim) {
+    band = __builtin_amdgcn_readfirstlane(band);
+    N = __builtin_amdgcn_readfirstlane(N);
+    side = __builtin_amdgcn_readfirstlane(side);
+    do_claim = __builtin_amdgcn_readfirstlane(do_claim);
+    rec0 = lds_uniform(rec0); kb = lds_uniform(kb); nu = lds_uniform(nu); il = lds_uniform(il); mom = lds_uniform(mom);
+    // band < sep3_bands(KS) at every call (the caller's loop bound).  A band without monomials would do nothing, the claim included,
+    // while the caller takes `claimed` as its wavefront's next entry: stated here, so that it cannot become a silent second
+    // execution of entry 0.
+    if (band < 0 || band >= sep3_bands(KS)) __builtin_unreachable();
+    int claimed = 0;
     switch (band) {
-        case 0: sep3_band<KS, 0>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        case 1: sep3_band<KS, 1>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        case 2: sep3_band<KS, 2>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        case 3: sep3_band<KS, 3>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        case 4: sep3_band<KS, 4>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        case 5: sep3_band<KS, 5>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
-        default: sep3_band<KS, 6>(lane, N, side, rec0, RS, kb, nu, il, mom); break;
+        case 0: sep3_band<KS, 0>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        case 1: sep3_band<KS, 1>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        case 2: sep3_band<KS, 2>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        case 3: sep3_band<KS, 3>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        case 4: sep3_band<KS, 4>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        case 5: sep3_band<KS, 5>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
+        default: sep3_band<KS, 6>(lane, N, side, rec0, kb, nu, il, mom, cq, do_claim, claimed); break;
     }
+    return claimed;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -910,7 +975,9 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
     double* c_xr = smem + L.c_xr;
     double* c_act = smem + L.c_act;
     double* c_exptab = smem + L.c_exptab;
-    const double* Xs = p.x_in_lds ? (smem + L.c_X) : p.Xt;     // X^T (E, N): LDS copy or HBM/L2
+    // X^T (E, N): LDS copy or HBM/L2.  (Measured and not adopted: a typed read on either side of a scalar branch on p.x_in_lds,
+    // ds_read / global_load for the FLAT loads of this one pointer -- config 2 + 0.75 %)
+    const double* Xs = p.x_in_lds ? (smem + L.c_X) : p.Xt;
     double* c_monow = smem + L.c_monow;
     int* c_monoe = reinterpret_cast<int*>(smem + L.c_monoe);
     const double* act = p.actions + (size_t)c * H * A;
@@ -1933,14 +2000,42 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                     // s1[a][0] = sum_p lb, s1[a][1+d] = sum_p lb nu_d  (fixed order)
                     const int a = 0xffff - wi;
                     GPMPC_ITEM_FIRST(2);
-                    for (int dd = 0; dd <= D; ++dd) {
-                        double v = 0.0;
-                        if (dd == 0) { for (int pt = lane; pt < N; pt += 64) v += a_lb[a * N + pt]; }
-                        else { for (int pt = lane; pt < N; pt += 64) v = fma(a_lb[a * N + pt], a_nu[(dd - 1) * N + pt], v); }
-                        v = wave_sum(v);
+                    if constexpr (DX > 0 && DP <= 4) {
+                        // one walk over the points: lb loaded once, an accumulator per sum (each in its own order over pt, as when
+                        // every sum walked the points by itself), then the D + 1 trees side by side under the late claim
+                        // (state dimension known at compile time only: with a run-time D the DP = 4 unit's widest kernel took 4 bytes
+                        //  more scratch for the D + 1 live accumulators)
+                        double v[DP + 1];
+#pragma unroll
+                        for (int dd = 0; dd <= DP; ++dd) v[dd] = 0.0;
+                        for (int pt = lane; pt < N; pt += 64) {
+                            const double lb = a_lb[a * N + pt];
+                            v[0] += lb;
+#pragma unroll
+                            for (int dd = 1; dd <= DP; ++dd)
+                                if (dd <= D) v[dd] = fma(lb, a_nu[(dd - 1) * N + pt], v[dd]);
+                        }
+                        if constexpr (kDesc) q_claim_late();
+                        wave_sum_n(v);
                         if (lane == 0) {
-                            s_s1[a * (D + 1) + dd] = v;
-                            if constexpr (CL) publish(x_mean + a * (D + 1) + dd, v);
+#pragma unroll
+                            for (int dd = 0; dd <= DP; ++dd) {
+                                if (dd <= D) {
+                                    s_s1[a * (D + 1) + dd] = v[dd];
+                                    if constexpr (CL) publish(x_mean + a * (D + 1) + dd, v[dd]);
+                                }
+                            }
+                        }
+                    } else {
+                        for (int dd = 0; dd <= D; ++dd) {
+                            double v = 0.0;
+                            if (dd == 0) { for (int pt = lane; pt < N; pt += 64) v += a_lb[a * N + pt]; }
+                            else { for (int pt = lane; pt < N; pt += 64) v = fma(a_lb[a * N + pt], a_nu[(dd - 1) * N + pt], v); }
+                            v = wave_sum(v);
+                            if (lane == 0) {
+                                s_s1[a * (D + 1) + dd] = v;
+                                if constexpr (CL) publish(x_mean + a * (D + 1) + dd, v);
+                            }
                         }
                     }
                     GPMPC_ITEM_LAST();
@@ -1973,14 +2068,23 @@ __global__ __launch_bounds__(NT, (rollout_min_waves<DP, CL>())) void rollout_ker
                         GPMPC_ITEM_FIRST(1);
                         for (int itm = slot; itm < 2 * nbands; itm += wpp) {
                             const int side = itm >= nbands, band = itm - side * nbands;
-                            const double* rec0 = a_rows + (size_t)sl3 * NR * RS;
-                            const double* kbp = a_kb + sl3 * N;
-                            const double* il = c_ils2 + b * E;
-                            double* mom = s_mom + (gq * 2 + side) * rnd2(CM);
-                            if (K <= 3) sep3_item<3>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);
-                            else if (K == 4) sep3_item<4>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);
-                            else if (K == 5) sep3_item<5>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);
-                            else sep3_item<6>(band, lane, N, side, rec0, RS, kbp, a_nu, il, mom);      // K <= 6 on this path (P1)
+                            static_assert(RS == RowRecAligned<3>::RS, "sep3_band reads the aligned records of DP = 3");
+                            const lds_cptr rec0 = (lds_cptr)(a_rows + (size_t)sl3 * NR * RS);
+                            const lds_cptr kbp = (lds_cptr)(a_kb + sl3 * N);
+                            const lds_cptr il = (lds_cptr)(c_ils2 + b * E);
+                            const lds_cptr nup = (lds_cptr)a_nu;
+                            const lds_ptr mom = (lds_ptr)(s_mom + (gq * 2 + side) * rnd2(CM));
+                            // the entry's last band claims the wavefront's next entry under its reduction (never at the head: section 8)
+                            const int claim = (kDesc && itm + wpp >= 2 * nbands) ? 1 : 0;
+                            const lds_iptr cq = (lds_iptr)s_counter;
+                            int got;
+                            if (K <= 3) got = sep3_item<3>(band, lane, N, side, rec0, kbp, nup, il, mom, cq, claim);
+                            else if (K == 4) got = sep3_item<4>(band, lane, N, side, rec0, kbp, nup, il, mom, cq, claim);
+                            else if (K == 5) got = sep3_item<5>(band, lane, N, side, rec0, kbp, nup, il, mom, cq, claim);
+                            else got = sep3_item<6>(band, lane, N, side, rec0, kbp, nup, il, mom, cq, claim);      // K <= 6 on this path (P1)
+                            if constexpr (kDesc) {
+                                if (claim) { q_nidx = got; q_claimed = true; }
+                            }
                         }
                         GPMPC_ITEM_LAST();
                         continue;
